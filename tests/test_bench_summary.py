@@ -39,3 +39,17 @@ def test_replica_witness_mode_follows_the_cores_of_a_rank(monkeypatch):
     assert nvk.shape == (60 + 12 * 10,) and npr.shape == (96,) and nin.shape == (18, 6)
     nvk5, npr5, nin5, _ = bench.aggregator_inputs(5)
     assert nvk5.shape == (60 + 12 * 6,) and nin5.shape == (10, 6)
+
+
+def test_dumped_outputs_hold_the_limbs_exactly(tmp_path):
+    """bench.py --dump-outputs: every u64 limb as its two 32-bit words, low word first, in float64 - exact, shape kept but for the words."""
+    import numpy as np
+    limbs = np.array([0, 1, 2**32 - 1, 2**32, 2**64 - 1, 0x0123456789ABCDEF], dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "out"), {"proof": limbs, "primary_inputs": limbs.reshape(2, 3)})
+    w = np.load(tmp_path / "out" / "proof.npy")
+    assert w.dtype == np.float64 and w.shape == (12,)
+    back = w.astype(np.uint64)
+    assert ((back[0::2] | (back[1::2] << np.uint64(32))) == limbs).all()
+    assert np.load(tmp_path / "out" / "primary_inputs.npy").shape == (2, 6)
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.dump_outputs is None and plain.steps == 3

@@ -22,14 +22,14 @@ def _bench(*args):
 
 
 def test_key_partitioned_prover_across_two_processes():
-    line = _bench("--gpus", "2", "--workload", "prover", "--log-n", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    line = _bench("--gpus", "2", "--workload", "prover", "--log-n", "16", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert line["last_proof_verifies"] is True
     assert "rehearsal" in line                       # the line must not pass for a two-GPU measurement
 
 
 def test_point_partitioned_msm_across_two_processes():
-    line = _bench("--gpus", "2", "--log-n", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline")
+    line = _bench("--gpus", "2", "--log-n", "16", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0
     assert line["config"]["terms_per_gpu"] == 1 << 16
     assert line["combined_result_matches_closed_form"] is True        # sum over BOTH ranks' slices = (sum s_i k_i) G

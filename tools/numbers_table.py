@@ -66,4 +66,4 @@ for what, r4, key, (va, vb) in rows:
     print("| %s | %s | %s | %s | %s |" % (what, va, vb, r4, key))
 za = a["zeth_shaped"]
 print("| ... result bits of the nine-input streams' last proofs / the C restatement proving the identical nine-input batch (one whole proof, limb-identical) | %s (VALID nested proofs) / %s proofs/s | 0 (invalid by construction) / - | 0 / - | `zeth_shaped.result_bits`, `.cpu_baseline` |" % (za["result_bits"], za["cpu_baseline"]["value"]))
-print("| N > 1 | `python bench.py --gpus N`: configs[3] / [4] legs with `leg_wall_s`, the partitioned leg set up by `zkhip_groth16_setup_slice` (§8); two ranks rehearsed on one GPU; **RCCL has still not seen more than one rank** | | | §8 |")
+print("| N > 1 | `python bench.py --gpus N --full`: configs[3] / [4] legs with `leg_wall_s`, the partitioned leg set up by `zkhip_groth16_setup_slice` (§8); two ranks rehearsed on one GPU; **RCCL has still not seen more than one rank** | | | §8 |")

@@ -9,15 +9,15 @@ val_line() { python3 -c "import json,sys; d=json.loads([l for l in sys.stdin if 
 for rep in 1 2 3; do
   for v in 0 1; do
     export ZKHIP_SLOTS_CLEAR=$v
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm stream  clear=$v" >> $OUT/ab.txt
-    python3 bench.py --serial --steps 6 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm serial  clear=$v" >> $OUT/ab.txt
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm stream  clear=$v" >> $OUT/ab.txt
+    python3 bench.py --full --serial --steps 6 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm serial  clear=$v" >> $OUT/ab.txt
   done
 done
 for rep in 1 2; do
   for v in 0 1; do
     export ZKHIP_SLOTS_CLEAR=$v
-    python3 bench.py --workload prover --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | val_line "prover 2^20  clear=$v" >> $OUT/ab.txt
-    python3 bench.py --workload aggregator --steps 800 --warmup 80 --no-cpu-baseline 2>/dev/null | val_line "wrapping    clear=$v" >> $OUT/ab.txt
+    python3 bench.py --full --workload prover --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | val_line "prover 2^20  clear=$v" >> $OUT/ab.txt
+    python3 bench.py --full --workload aggregator --steps 800 --warmup 80 --no-cpu-baseline 2>/dev/null | val_line "wrapping    clear=$v" >> $OUT/ab.txt
   done
 done
 cat $OUT/ab.txt

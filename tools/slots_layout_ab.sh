@@ -23,16 +23,16 @@ val_line() { python3 -c "import json,sys; d=json.loads([l for l in sys.stdin if 
 for rep in 1 2 3; do
   for v in $VARIANTS; do
     setlib $v
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm stream  $v" >> $OUT/ab.txt
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm stream  $v" >> $OUT/ab.txt
   done
 done
 for rep in 1 2; do
   for v in $VARIANTS; do
     setlib $v
-    python3 bench.py --workload prover --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | val_line "prover 2^20  $v" >> $OUT/ab.txt
-    python3 bench.py --workload aggregator --steps 800 --warmup 80 --no-cpu-baseline 2>/dev/null | val_line "wrapping    $v" >> $OUT/ab.txt
-    python3 bench.py --workload aggregator --serial --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | val_line "wrapping one proof at a time $v" >> $OUT/ab.txt
-    python3 bench.py --serial --steps 6 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm one at a time $v" >> $OUT/ab.txt
+    python3 bench.py --full --workload prover --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | val_line "prover 2^20  $v" >> $OUT/ab.txt
+    python3 bench.py --full --workload aggregator --steps 800 --warmup 80 --no-cpu-baseline 2>/dev/null | val_line "wrapping    $v" >> $OUT/ab.txt
+    python3 bench.py --full --workload aggregator --serial --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | val_line "wrapping one proof at a time $v" >> $OUT/ab.txt
+    python3 bench.py --full --serial --steps 6 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | msm_line "msm one at a time $v" >> $OUT/ab.txt
   done
 done
 cat $OUT/ab.txt

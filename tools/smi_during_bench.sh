@@ -9,7 +9,7 @@ cd $ROOT
 SMI=$!
 export ZKHIP_BENCH_MARKS=$OUT/marks.log
 for k in 1 2; do
-  timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench$k.log 2>&1
+  timeout -k 10 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench$k.log 2>&1
 done
 touch $OUT/stop
 wait $SMI
