@@ -99,6 +99,15 @@ int zkhip_set_crs_precompute(int on);
    non-adjacent form: an eighth fewer point additions per scalar, but measured slower once the tables outgrow the TLB (DESIGN.md
    section 5) - off by default; 0: one level per window; -1: the environment's ZKHIP_TABLE_NAF decides.  Results are identical. */
 int zkhip_set_table_naf(int on);
+/* model = 1 (default): the window tables of G1 base sets built from now on by zkhip_bases_precompute[_ex] (one level per window) get a
+   second, precomputed form on G1's 2-isogenous twisted Edwards curve, and single MSMs over such a set add in that model (fewer field
+   products per addition); 0: XYZZ only; -1: the environment's ZKHIP_TABLE_MODEL (xyzz | edwards) decides.
+   The Edwards form needs every base to be a point of ORDER r on G1's curve; building it checks that (2 [1/2 mod r] P = P), and a set
+   that fails (a G2 set, points outside the subgroup) stays XYZZ, as does a set whose Edwards form (1.5 x the table's memory) would
+   leave less than a quarter of the device's memory free.  Results are identical. */
+int zkhip_set_table_model(int model);
+/* 1: single MSMs over this set accumulate in the Edwards model, 0: XYZZ */
+int zkhip_bases_table_model(const zkhip_bases* b);
 /* Table-backed keys of up to 2^20 points per query vector: the five MSMs of a proof go through one launch sequence
  * (default on; off = one launch sequence per MSM, 2 or 5 of them in flight).  A tuning / comparison switch. */
 int zkhip_set_batch_msms(int on);

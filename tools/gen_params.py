@@ -77,6 +77,28 @@ def field(name, p, nl, n64, extra=""):
     return s
 
 
+def edwards_params():
+    """The twisted Edwards curve (a = -1) that G1's curve y^2 = x^3 - 1 is 2-isogenous to.
+    With X = x - 1 the curve is y^2 = X (X^2 + 3X + 3); Velu's quotient by (0, 0) is E': Y^2 = X (X^2 - 6X - 3); -3 = s^2 is a square, so
+    u = X'/s, v = Y'/s^2 is the Montgomery curve s v^2 = u^3 + A u^2 + u, A = -6/s; then a_E = (A + 2)/s, d_E = (A - 2)/s, and with
+    t^2 = -a_E, x_e = t u / v, y_e = (u - 1)/(u + 1) lands on -x_e^2 + y_e^2 = 1 + d x_e^2 y_e^2, d = -d_E / a_E.
+    chi: G1 -> Edwards, written out:  x_e = t s y / (3 - X^2),  y_e = (y^2 - s X^2) / (y^2 + s X^2).
+    psi: Edwards -> G1 (the dual isogeny after the inverse maps), psi(chi(P)) = 2P:  x = 1 + c1 / x_e^2,  y = c2 y_e / (x_e (1 - y_e^2)),
+    c1 = -3 t^2 / 4, c2 = 3 t / 2."""
+    q = Q
+    inv = lambda a: pow(a % q, q - 2, q)
+    s = pow(-3 % q, (q + 1) // 4, q)          # q = 3 mod 4: the principal square root
+    assert s * s % q == q - 3
+    A = -6 * inv(s) % q
+    aE = (A + 2) * inv(s) % q
+    dE = (A - 2) * inv(s) % q
+    t = pow(-aE % q, (q + 1) // 4, q)
+    assert t * t % q == -aE % q
+    d = -dE * inv(aE) % q
+    assert pow(d, (q - 1) // 2, q) == 1       # d is a square: the formulas are complete only on the odd-order part (DESIGN.md section 4)
+    return {"s": s, "A": A, "t": t, "d": d, "c1": -3 * t * t * inv(4) % q, "c2": 3 * t * inv(2) % q, "half_r": pow(2, -1, R)}
+
+
 def main():
     out = "// GENERATED by tools/gen_params.py - do not edit.\n"
     out += "// BW6-761 field constants (moduli: reference client/test_commands/test_bw6_761_groth16_contract.py:26-27).\n"
@@ -92,6 +114,15 @@ def main():
     extra_q += "  static constexpr int FINAL_EXP_LIMBS = %d;\n" % nfe
     extra_q += arr("FINAL_EXP", limbs(fe, nfe, 64), "uint64_t", 3, "0x%016xull")
     extra_q += arr("R_ORDER64", limbs(R, 6, 64), "uint64_t", 3, "0x%016xull")
+    # G1's 2-isogenous twisted Edwards curve (edwards_params; ec_edw.cuh), device Montgomery form
+    ep = edwards_params()
+    mont = lambda v: limbs(v * (1 << (B * 27)) % Q, 27, B)
+    extra_q += arr("EDW_D2", mont(2 * ep["d"]))                     # 2d
+    extra_q += arr("EDW_S", mont(ep["s"]))                          # s = sqrt(-3)
+    extra_q += arr("EDW_TS", mont(ep["t"] * ep["s"]))               # t s
+    extra_q += arr("EDW_C1", mont(ep["c1"]))                        # -3 t^2 / 4
+    extra_q += arr("EDW_C2", mont(ep["c2"]))                        # 3 t / 2
+    extra_q += arr("EDW_THREE", mont(3))
     out += field("FqParams", Q, 27, 12, extra_q)
     Rabi_r = 1 << 384
     two_adic = pow(FR_GEN, (R - 1) >> 46, R)
@@ -99,6 +130,8 @@ def main():
     extra_r = "  static constexpr int TWO_ADICITY = 46;\n"
     extra_r += arr("GEN64", limbs(FR_GEN * Rabi_r % R, 6, 64), "uint64_t", 3, "0x%016xull")
     extra_r += arr("ROOT_2_46_64", limbs(two_adic * Rabi_r % R, 6, 64), "uint64_t", 3, "0x%016xull")
+    # 1/2 mod r = (r + 1) / 2 as an integer in 29-bit limbs: the scalar that halves the bases of an Edwards table (msm.hip k_half_bases)
+    extra_r += arr("HALF_RAW", limbs(pow(2, -1, R), 14, B))
     out += field("FrParams", R, 14, 6, extra_r)
     out += "}  // namespace zkhip\n"
     print(out, end="")

@@ -9,6 +9,7 @@
 namespace zkhip {
 
 struct AffPacked;
+struct EdwPacked;
 
 #define MSM_MAX_AFF_LEVELS 4
 #define MSM_MAX_JOBS 5   // MSMs sharing one launch sequence (the five query vectors of a proof)
@@ -21,6 +22,8 @@ struct MsmJob {
   size_t table_stride;           // distance between table levels, in points
   size_t n_finite;               // upper bound on the bases of this job that are not the point at infinity (0: unknown, use n):
                                  // sizes the slices of the accumulation to the entries that can actually occur
+  const EdwPacked* edw = nullptr;  // the same table in precomputed Edwards form (msm_table_edw), or null: a single MSM over a one-level-
+                                   // per-window table then accumulates on G1's 2-isogenous Edwards curve (ec_edw.cuh)
 };
 
 #define ZK_PRIO_BOARD_WORDS (8 * 8 * 2 * 16 * 4 * 16)
@@ -93,8 +96,9 @@ int msm_time_base_reset();
 void msm_plan_free(MsmCtx* ctx);
 int msm_bases_convert(const uint64_t* d_bases_abi, size_t n, AffPacked* d_out, uint8_t* d_inf_flags, char* errbuf, size_t errlen);
 // table_stride: distance (in points) between the levels of a precomputed table (merged plans only)
+// edw: the table in precomputed Edwards form (or null)
 int msm_launch(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
-               int scalars_montgomery, size_t table_stride);
+               int scalars_montgomery, size_t table_stride, const EdwPacked* edw = nullptr);
 int msm_finish(MsmCtx* ctx, uint64_t out_jac[36]);
 // The entries (non-zero digits = mixed additions of k_accumulate, no affine levels in front) of the last launch of this plan, read
 // back from the sort's histogram: a measurement aid, synchronises the device.  0: nothing launched yet.
@@ -104,12 +108,20 @@ int msm_last_entries(MsmCtx* ctx, uint64_t* out);
 int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs);
 int msm_finish_multi(MsmCtx* ctx, int K, uint64_t* out_jac);
 int msm_run(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
-            int scalars_montgomery, size_t table_stride, uint64_t out_jac[36]);
+            int scalars_montgomery, size_t table_stride, uint64_t out_jac[36], const EdwPacked* edw = nullptr);
 // levels of a window table for window size c
 static inline int msm_table_levels(int c, int naf = 0) { return naf ? 378 : (378 + c - 1) / c; }
 // d_table: levels x n points, level 0 (= the n base points) already in place; d_tinf: levels x n flags, level 0 in place.
 // Fills levels 1 .. levels-1:  table[w * n + i] = 2^(c w) P_i  in affine packed form.
 int msm_table_build(AffPacked* d_table, uint8_t* d_tinf, size_t n, int c, int naf, char* errbuf, size_t errlen);
+// The Edwards form of a one-level-per-window table over the n bases d_bases (level 0; flags d_inf): *d_out[w n + i] = chi([1/2 mod r]
+// 2^(off_w) P_i) in precomputed form (ec_edw.cuh), so that MSMs over it use XYZZ's digits.  ZKHIP_ERR_ARG when a base is not a point
+// of order r on G1's curve (a G2 set, a point outside the subgroup): the caller keeps the XYZZ path.
+int msm_table_edw(const AffPacked* d_bases, const uint8_t* d_inf, size_t n, int c, EdwPacked** d_out, char* errbuf, size_t errlen);
+// point i of an Edwards table (EdwPacked: 288 bytes; ec_edw.cuh), null stays null
+static inline const EdwPacked* msm_edw_at(const EdwPacked* t, size_t i) {
+  return t ? reinterpret_cast<const EdwPacked*>(reinterpret_cast<const char*>(t) + i * 288) : nullptr;
+}
 
 // Fq multiplications per second of the whole device, measured now: dependent fp_mul chains at two waves per SIMD (~25 ms)
 int msm_field_selftest(int field, const uint32_t* in_host, size_t n, uint32_t* out_host, char* errbuf, size_t errlen);

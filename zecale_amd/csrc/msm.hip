@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ec_affine.cuh"
+#include "ec_edw.cuh"
 #include "host_field.hpp"
 #include "msm.h"
 #include "wait.h"
@@ -370,17 +371,19 @@ __global__ void __launch_bounds__(256) k_scan_add(uint32_t* __restrict__ out, co
 // position p of bucket b starts at weight G(p) = goff[b] for p = offsets[b], goff[b] + 1 + 8 (p - offsets[b] - 1) otherwise; slice t
 // holds the entries with t A <= G(p) < (t + 1) A.  The slot array's ZZ rows are zero-filled beforehand (all-zero ZZ = infinity), so
 // empty buckets need no work.
+// The Edwards accumulation (ec_edw.cuh) opens every run at the identity and ADDS its first entry: there every entry weighs
+// ZK_W_NEXT (wf = ZK_W_NEXT below), the XYZZ accumulation passes wf = ZK_W_FIRST.
 #define ZK_W_NEXT 8u
 #define ZK_W_FIRST 1u
-__global__ void __launch_bounds__(256) k_slice_weights(const uint32_t* __restrict__ counts, uint32_t* __restrict__ w, size_t nb) {
+__global__ void __launch_bounds__(256) k_slice_weights(const uint32_t* __restrict__ counts, uint32_t* __restrict__ w, size_t nb, uint32_t wf) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i > nb) return;
   const uint32_t c = i < nb ? counts[i] : 0u;
-  w[i] = c ? ZK_W_NEXT * c - (ZK_W_NEXT - ZK_W_FIRST) : 0u;
+  w[i] = c ? ZK_W_NEXT * c - (ZK_W_NEXT - wf) : 0u;
 }
 // first position p with G(p) >= x (M if there is none); *b_out: a bucket at or before the one that holds p
 __device__ __forceinline__ uint32_t slice_pos(const uint32_t* __restrict__ goff, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                              uint32_t nb, uint32_t M, uint64_t x, uint32_t* b_out) {
+                                              uint32_t nb, uint32_t M, uint64_t x, uint32_t* b_out, uint32_t wf) {
   if (x >= (uint64_t)goff[nb]) { *b_out = nb - 1; return M; }
   uint32_t lo = 0, hi = nb;   // last b with goff[b] <= x: a non-empty bucket (an empty one repeats the value of the next non-empty one)
   while (hi - lo > 1) {
@@ -390,13 +393,14 @@ __device__ __forceinline__ uint32_t slice_pos(const uint32_t* __restrict__ goff,
   *b_out = lo;
   const uint32_t g = goff[lo], off = offsets[lo], cnt = counts[lo];
   if ((uint64_t)g >= x) return off;
-  const uint32_t j = (uint32_t)((x - g - ZK_W_FIRST + (ZK_W_NEXT - 1)) / ZK_W_NEXT) + 1u;      // first j >= 1 with g + 1 + 8 (j - 1) >= x
+  const uint32_t j = (uint32_t)((x - g - wf + (ZK_W_NEXT - 1)) / ZK_W_NEXT) + 1u;      // first j >= 1 with g + wf + 8 (j - 1) >= x
   return off + (j < cnt ? j : cnt);
 }
 // slice of the entry at position p of bucket b
-__device__ __forceinline__ uint32_t slice_of(const uint32_t* __restrict__ goff, const uint32_t* __restrict__ offsets, uint32_t b, uint32_t p, uint32_t A) {
+__device__ __forceinline__ uint32_t slice_of(const uint32_t* __restrict__ goff, const uint32_t* __restrict__ offsets, uint32_t b, uint32_t p, uint32_t A,
+                                             uint32_t wf) {
   const uint32_t off = offsets[b];
-  const uint64_t G = (uint64_t)goff[b] + (p == off ? 0u : ZK_W_FIRST + (uint64_t)ZK_W_NEXT * (p - off - 1));
+  const uint64_t G = (uint64_t)goff[b] + (p == off ? 0u : wf + (uint64_t)ZK_W_NEXT * (p - off - 1));
   return (uint32_t)(G / A);
 }
 __device__ __forceinline__ uint32_t bucket_of(const uint32_t* __restrict__ offsets, uint32_t nb, uint32_t pos) {
@@ -453,22 +457,28 @@ __device__ __forceinline__ uint32_t slice_weight(uint32_t G, uint32_t T, uint32_
 
 // entries == nullptr: the sorted list IS the dense point array bp.p[0] (the output of the batched-affine levels, k_affine_level):
 // entry k is point k, never negated; a point may be the level encoding of infinity (skipped).
-template <int NJ>
-__global__ void __launch_bounds__(256, 2) k_accumulate(BasePtrs bp, int bshift, const uint32_t* __restrict__ entries,
-                                                        const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ goff,
-                                                        uint32_t nb, uint32_t S_host, int tight, uint32_t T, uint32_t* __restrict__ slots,
-                                                        uint32_t stride, uint32_t* __restrict__ fix_cnt /* [2] */, uint2* __restrict__ fix_short, uint2* __restrict__ fix_long,
-                                                        uint64_t* __restrict__ dbg_times /* null, or [waves][4]: tools/acc_probe.py */, int prio_mode,
-                                                        uint32_t* prio_board /* null, or one word per hardware wave slot */, uint32_t prio_tag) {
+// EDW: bp.p[0] is a table of precomputed Edwards points (ec_edw.cuh) and the slots receive Edwards points (X | Y | Z | T in the
+// X | Y | ZZ | ZZZ words; k_slots_edw_to_xyzz maps them back): every run starts at the identity, so every entry is one addition.
+// Single MSMs only (NJ = 1), never dense.  Two kernels share this body: k_accumulate<NJ> (XYZZ) and k_accumulate_edw.
+#define ZK_ACC_PARAMS                                                                                                                   \
+  BasePtrs bp, int bshift, const uint32_t* __restrict__ entries, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,   \
+      const uint32_t* __restrict__ goff, uint32_t nb, uint32_t S_host, int tight, uint32_t T, uint32_t* __restrict__ slots, uint32_t stride,      \
+      uint32_t* __restrict__ fix_cnt /* [2] */, uint2* __restrict__ fix_short, uint2* __restrict__ fix_long,                                  \
+      uint64_t* __restrict__ dbg_times /* null, or [waves][4]: tools/acc_probe.py */, int prio_mode,                                        \
+      uint32_t* prio_board /* null, or one word per hardware wave slot */, uint32_t prio_tag
+template <int NJ, bool EDW>
+__device__ __forceinline__ void accumulate_impl(ZK_ACC_PARAMS) {
+  static_assert(!EDW || NJ == 1, "the Edwards accumulation serves single MSMs");
+  constexpr uint32_t wf = EDW ? ZK_W_NEXT : ZK_W_FIRST;
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t dbg_t0 = dbg_times ? wall_clock64() : 0;
   const uint32_t M = offsets[nb - 1] + counts[nb - 1];
   const uint32_t A = slice_weight(goff[nb], T, S_host, tight);
   if (t >= T) return;
   uint32_t b, b1_;
-  const uint32_t pos0 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)t * A, &b);
+  const uint32_t pos0 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)t * A, &b, wf);
   if (pos0 >= M) return;
-  const uint32_t pos1 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)(t + 1) * A, &b1_);
+  const uint32_t pos1 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)(t + 1) * A, &b1_, wf);
   while (offsets[b] + counts[b] <= pos0) b++;          // (the slice may start right behind the last entry of the bucket the search found)
   {
     // A bucket cut by slice boundaries leaves an L piece (slice t0, where it starts) and F pieces in the slices t0+1 .. t1.  The
@@ -477,9 +487,9 @@ __global__ void __launch_bounds__(256, 2) k_accumulate(BasePtrs bp, int bshift, 
     // wave and list.
     uint32_t span = 0, tF0 = 0;
     if (offsets[b] < pos0) {
-      const uint32_t t0 = slice_of(goff, offsets, b, offsets[b], A);
+      const uint32_t t0 = slice_of(goff, offsets, b, offsets[b], A, wf);
       tF0 = t0 + 1;
-      span = slice_of(goff, offsets, b, offsets[b] + counts[b] - 1, A) - t0;       // number of F pieces
+      span = slice_of(goff, offsets, b, offsets[b] + counts[b] - 1, A, wf) - t0;       // number of F pieces
       if (t != tF0) span = 0;
     }
     const bool is_short = span >= 2 && span <= 4, is_long = span > 4;
@@ -528,28 +538,55 @@ __global__ void __launch_bounds__(256, 2) k_accumulate(BasePtrs bp, int bshift, 
     board_other = prio_board + simd + ((hw & 15u) ^ 1u);
   }
   uint32_t k = pos0, iter = 0;
-  while (k < pos1) {
-    if (prio_mode) {
-      uint32_t other = 0;
-      if (board_mine) {
-        if ((threadIdx.x & 63u) == 0) __hip_atomic_store(board_mine, (prio_tag << 16) | (iter < 0xfffeu ? iter : 0xfffeu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        other = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(board_other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      }
-      if (board_mine && (other >> 16) == prio_tag) {
-        const uint32_t oi = other & 0xffffu;
-        if (iter < oi) __builtin_amdgcn_s_setprio(3);
-        else if (iter == oi) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      } else {
-        const uint32_t kk = (uint32_t)__builtin_amdgcn_readfirstlane((int)k), a1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q1),
-                       a2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q2), a3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q3);
-        if (kk < a1) __builtin_amdgcn_s_setprio(3);
-        else if (kk < a2) __builtin_amdgcn_s_setprio(2);
-        else if (kk < a3) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-      }
-      iter++;
+  // one iteration's pacing: post this wave's progress, take the priority its partner's progress (or its own quarter) gives it
+  auto pace = [&]() {
+    if (!prio_mode) return;
+    uint32_t other = 0;
+    if (board_mine) {
+      if ((threadIdx.x & 63u) == 0) __hip_atomic_store(board_mine, (prio_tag << 16) | (iter < 0xfffeu ? iter : 0xfffeu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      other = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(board_other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     }
+    if (board_mine && (other >> 16) == prio_tag) {
+      const uint32_t oi = other & 0xffffu;
+      if (iter < oi) __builtin_amdgcn_s_setprio(3);
+      else if (iter == oi) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+    } else {
+      const uint32_t kk = (uint32_t)__builtin_amdgcn_readfirstlane((int)k), a1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q1),
+                     a2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q2), a3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q3);
+      if (kk < a1) __builtin_amdgcn_s_setprio(3);
+      else if (kk < a2) __builtin_amdgcn_s_setprio(2);
+      else if (kk < a3) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+    }
+    iter++;
+  };
+  if constexpr (EDW) {
+    const EdwPacked* __restrict__ etab = reinterpret_cast<const EdwPacked*>(bp.p[0]);
+    // inf: no run is open yet (an open run's slot is `acc`; LDS holds X, Z (zz), T (zzz), registers Y; it never returns to infinity)
+    while (k < pos1) {
+      pace();
+      // run boundary: close the finished run, open the next one at the identity (memory operations only)
+      if (k == bend) {
+        if (!inf) {
+          ZK_CLOSE_RUN(acc, xs, zz, zzz, ty);
+          b++;
+          while (offsets[b] + counts[b] <= k) b++;     // next non-empty bucket
+        }
+        bend = offsets[b] + counts[b];
+        const bool starts = (k == offsets[b]), ends = (bend <= pos1);
+        acc.voff = ((starts && ends) ? b : (!starts ? nb + t : nb + T + t)) * ZK_SLOT_PITCH;
+        edw_set_identity(xs, zz, zzz, ty);
+        inf = false;
+      }
+      // ---- one addition (bases at infinity never reach the entry list: k_digit_pass drops them)
+      const uint32_t e = e_next;
+      if (k + 1 < pos1) e_next = entries[k + 1];        // fetched a whole addition ahead of its use
+      k++;
+      edw_madd_lds_regy(xs, zz, zzz, ty, etab + (e & 0x7fffffffu), (e >> 31) != 0);
+    }
+  } else while (k < pos1) {
+    pace();
     // ---- run boundaries and run openings: memory operations only.  The lanes that are in the middle of a run wait here for the few
     // that close one and open the next; whoever leaves this loop with k < pos1 has an addition to do.
     for (;;) {
@@ -606,6 +643,41 @@ __global__ void __launch_bounds__(256, 2) k_accumulate(BasePtrs bp, int bshift, 
     dbg_times[4 * wave + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_ID: wave, SIMD, CU, SH, SE
     dbg_times[4 * wave + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);      // XCC_ID
   }
+}
+template <int NJ>
+__global__ void __launch_bounds__(256, 2) k_accumulate(ZK_ACC_PARAMS) {
+  accumulate_impl<NJ, false>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
+                             dbg_times, prio_mode, prio_board, prio_tag);
+}
+__global__ void __launch_bounds__(256, 2) k_accumulate_edw(ZK_ACC_PARAMS) {
+  accumulate_impl<1, true>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
+                           dbg_times, prio_mode, prio_board, prio_tag);
+}
+
+// psi for the slots the Edwards accumulation wrote: [0, n) of the slot array, in place (ec_edw.cuh edw_to_xyzz_mem).  A slot whose
+// Z words are zero was not written (k_slots_clear_zz): it stays XYZZ's infinity.  One lane per slot: a throughput-bound launch.
+__global__ void __launch_bounds__(256, 2) k_slots_edw_to_xyzz(uint32_t* __restrict__ slots, uint32_t stride, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const XyzzRef r = make_slot_ref(slots, stride, i);
+  if (mem_is_inf(r)) return;
+  edw_to_xyzz_mem(r);
+}
+
+// chi for every entry of a window table (levels x n points): the precomputed Edwards table.  Entries at infinity hold zeros; *bad
+// counts the points that are not on G1's curve or have even order (the base set then stays on the XYZZ path).
+__global__ void __launch_bounds__(256) k_table_edw(const AffPacked* __restrict__ tab, const uint8_t* __restrict__ tinf, EdwPacked* __restrict__ out,
+                                                   size_t total, uint32_t* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  if (tinf[i]) {
+    uint32_t* w = reinterpret_cast<uint32_t*>(out + i);
+#pragma unroll
+    for (int k = 0; k < 72; k++) w[k] = 0u;
+    return;
+  }
+  const AffPacked* p = tab + i;
+  if (!edw_from_affine(aff_ld_x(p), aff_ld_y(p, false), out + i)) atomicAdd(bad, 1u);
 }
 
 // ---- batched-affine levels ------------------------------------------------------------------------------------------------
@@ -864,7 +936,8 @@ __global__ void __launch_bounds__(256, 2) k_fixup_fold(const uint32_t* __restric
 
 // final stitch: the slice in which a cut bucket STARTS owns it: bucket = L[t0] + F[t0+1] (folded).
 __global__ void __launch_bounds__(256, 2) k_fixup(const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ goff,
-                                                   uint32_t nb, uint32_t S_host, int tight, uint32_t T, uint32_t* __restrict__ slots, uint32_t stride) {
+                                                   uint32_t nb, uint32_t S_host, int tight, uint32_t T, uint32_t* __restrict__ slots, uint32_t stride,
+                                                   uint32_t wf) {
   // the L piece goes to the CU (X, ZZ, ZZZ in LDS, Y in registers, as in k_accumulate / k_sum_lds), the F piece is added to it
   // there and the sum is stored once: ten coordinate loads and four stores per cut bucket (a copy into the bucket's slot followed by
   // an addition in memory - rounds 1-3 - moved fourteen and eight)
@@ -874,9 +947,9 @@ __global__ void __launch_bounds__(256, 2) k_fixup(const uint32_t* __restrict__ o
   const uint32_t A = slice_weight(goff[nb], T, S_host, tight);
   if (t >= T) return;
   uint32_t b0_, b1_;
-  const uint32_t pos0 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)t * A, &b0_);
+  const uint32_t pos0 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)t * A, &b0_, wf);
   if (pos0 >= M) return;
-  const uint32_t pos1 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)(t + 1) * A, &b1_);
+  const uint32_t pos1 = slice_pos(goff, offsets, counts, nb, M, (uint64_t)(t + 1) * A, &b1_, wf);
   uint32_t b = bucket_of(offsets, nb, pos1 - 1);
   uint32_t bend = offsets[b] + counts[b];
   if (bend <= pos1 || offsets[b] < pos0) return;      // not cut at this slice's end, or started earlier
@@ -1190,6 +1263,52 @@ __global__ void __launch_bounds__(256, 2) k_table_build(AffPacked* __restrict__ 
     table[(size_t)w * n + i] = o;
     tinf[(size_t)w * n + i] = is_inf;
   }
+}
+
+// The Edwards table holds chi of the HALVED table points (msm_table_edw): H_i = [1/2 mod r] P_i, one lane per base, double-and-add
+// over the bits of (r + 1) / 2 on an XYZZ accumulator in memory (work: 108 words per lane, limb-major, stride cn).  The same lane
+// checks what the Edwards path needs of its base: y^2 = x^3 - 1 (a G2 set fails here, before any other work), and 2 H = P, which holds
+// iff r P = O - order r, not merely odd order.  *bad counts the bases that fail; a base at infinity gives H = O.
+__global__ void __launch_bounds__(256, 2) k_half_bases(const AffPacked* __restrict__ bases, const uint8_t* __restrict__ inf, AffPacked* __restrict__ out,
+                                                        size_t i0, uint32_t cn, uint32_t* __restrict__ work, uint32_t* __restrict__ bad) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cn) return;
+  const size_t i = i0 + t;
+  AffPacked o;
+#pragma unroll
+  for (int k = 0; k < 24; k++) { o.x[k] = 0; o.y[k] = 0; }
+  if (inf[i]) { out[i] = o; return; }
+  const AffPacked* p = bases + i;
+  const Fq x = aff_ld_x(p), y = aff_ld_y(p, false), one = fp_one<FqParams>();
+  const Fq rhs = fp_sub<FqParams, 4>(fp_add(fp_mul(y, y), one), fp_mul(fp_mul(x, x), x));        // y^2 + 1 - x^3 [7]
+  if (!fp_is_zero_2p(fp_cond_sub_kp<FqParams, 2>(fp_cond_sub_kp<FqParams, 4>(rhs)))) { atomicAdd(bad, 1u); out[i] = o; return; }
+  const XyzzRef acc = make_ref(work, cn, t);
+  mem_st(acc, CX, x); mem_st(acc, CY, y); mem_st(acc, CZZ, one); mem_st(acc, CZZZ, one);
+  constexpr int TOP = 375;                               // (r + 1) / 2 < 2^376, bit 375 set
+#pragma unroll 1
+  for (int j = TOP - 1; j >= 0; j--) {
+    dbl_mem(acc);
+    if ((FrParams::HALF_RAW[j / 29] >> (j % 29)) & 1u) {
+      if (mem_is_inf(acc)) { mem_st(acc, CX, x); mem_st(acc, CY, y); mem_st(acc, CZZ, one); mem_st(acc, CZZZ, one); }
+      else madd_mem(acc, p, false);
+    }
+  }
+  const Fq zz = mem_ld(acc, CZZ), zzz = mem_ld(acc, CZZZ);
+  bool ok = !fp_is_zero_2p(zz);
+  if (ok) {
+    const Fq tinv = fp_inv<FqParams>(fp_mul(zz, zzz));                                       // 1 / (ZZ ZZZ)
+    const Fq hx = fp_cond_sub_p(fp_mul(mem_ld(acc, CX), fp_mul(tinv, zzz)));                   // X / ZZ
+    const Fq hy = fp_cond_sub_p(fp_mul(mem_ld(acc, CY), fp_mul(tinv, zz)));                    // Y / ZZZ
+    fp_pack32<FqParams>(hx, o.x);
+    fp_pack32<FqParams>(hy, o.y);
+    dbl_mem(acc);                                                                             // 2 H == P ?
+    const Fq dzz = mem_ld(acc, CZZ);
+    const Fq ex = fp_sub<FqParams, 16>(fp_mul(x, dzz), mem_ld(acc, CX));                      // X [<= 10]
+    const Fq ey = fp_sub<FqParams, 8>(fp_mul(y, mem_ld(acc, CZZZ)), mem_ld(acc, CY));         // Y [<= 4]
+    ok = !fp_is_zero_2p(dzz) && fp_is_zero_2p(fp_canon(ex)) && fp_is_zero_2p(fp_canon(ey));
+  }
+  if (!ok) atomicAdd(bad, 1u);
+  out[i] = o;
 }
 
 // ---- the multiplier's own peak on THIS device, now (bench.py's fq_mul_frac divides by it) ----------------------------------------
@@ -1592,8 +1711,8 @@ int msm_bases_convert(const uint64_t* d_bases_abi, size_t n, AffPacked* d_out, u
 
 // d_bases: packed device-form points; d_scalars: n x 6 u64 (device memory).  Result: Jacobian, ABI form (host).
 int msm_run(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
-            int scalars_montgomery, size_t table_stride, uint64_t out_jac[36]) {
-  int rc = msm_launch(ctx, d_bases, d_inf_flags, d_scalars, n, scalars_montgomery, table_stride);
+            int scalars_montgomery, size_t table_stride, uint64_t out_jac[36], const EdwPacked* edw) {
+  int rc = msm_launch(ctx, d_bases, d_inf_flags, d_scalars, n, scalars_montgomery, table_stride, edw);
   if (rc != ZKHIP_OK) return rc;
   return msm_finish(ctx, out_jac);
 }
@@ -1601,8 +1720,8 @@ int msm_run(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, c
 // Enqueue one MSM on the context's streams and return without waiting (the prover keeps two contexts
 // in flight so that the latency-bound reduction of one MSM overlaps the accumulation of the next).
 int msm_launch(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
-               int scalars_montgomery, size_t table_stride) {
-  MsmJob job{d_bases, d_inf_flags, d_scalars, n, scalars_montgomery, table_stride, 0};
+               int scalars_montgomery, size_t table_stride, const EdwPacked* edw) {
+  MsmJob job{d_bases, d_inf_flags, d_scalars, n, scalars_montgomery, table_stride, 0, edw};
   return msm_launch_multi(ctx, 1, &job);
 }
 
@@ -1624,6 +1743,11 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   WindowPlan plan;
   memset(&plan, 0, sizeof plan);
   for (int w = 0; w < Wd; w++) { plan.off[w] = ctx->win_off[w]; plan.bits[w] = ctx->win_bits[w]; }
+  // the Edwards accumulation (ec_edw.cuh): a single MSM over a one-level-per-window table that has its Edwards form, no batched-affine
+  // levels in front.  The digits are XYZZ's (the table holds chi of the HALVED points); the slots go back to XYZZ right after the
+  // accumulation, everything after that is unchanged.
+  const bool edw = merged == 1 && K == 1 && ctx->K == 1 && ctx->aff_levels == 0 && jobs[0].edw != nullptr;
+  const uint32_t wf = edw ? ZK_W_NEXT : ZK_W_FIRST;
   DigitJobs dj;
   memset(&dj, 0, sizeof dj);
   size_t n_max = 0;
@@ -1657,6 +1781,7 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   sb = nblk(nb, 1024);                                            // (the batched-affine levels below scan arrays of nb counters)
   BasePtrs bp;
   for (int k = 0; k < MSM_MAX_JOBS; k++) bp.p[k] = jobs[k < K ? k : 0].bases;
+  if (edw) bp.p[0] = reinterpret_cast<const AffPacked*>(jobs[0].edw);     // (k_accumulate_edw reads it as EdwPacked)
   const int bshift = merged ? c - 1 : 31;     // bucket -> job
   ctx->acc_gen = time_base_gen();
   if (ctx->aff_levels > 0) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));     // the timed accumulation includes the affine levels
@@ -1702,7 +1827,7 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   // slice weights: goff = exclusive scan of (8 count - 7) over the non-empty buckets of the list k_accumulate sums (nb + 1 values)
   {
     const unsigned gb = nblk(nb + 1, 1024);
-    hipLaunchKernelGGL(k_slice_weights, dim3(nblk(nb + 1, 256)), dim3(256), 0, st, cur_cnt, ctx->goff, nb);
+    hipLaunchKernelGGL(k_slice_weights, dim3(nblk(nb + 1, 256)), dim3(256), 0, st, cur_cnt, ctx->goff, nb, wf);
     hipLaunchKernelGGL(k_scan_local, dim3(gb), dim3(256), 0, st, ctx->goff, ctx->goff, ctx->block_tot, nb + 1);
     hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)gb);
     hipLaunchKernelGGL(k_scan_add, dim3(gb), dim3(256), 0, st, ctx->goff, ctx->block_tot, nb + 1);
@@ -1749,13 +1874,21 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   const uint32_t* acc_entries = dense ? nullptr : ctx->entries;
   static const int acc_prio = env_int("ZKHIP_ACC_PRIO", 1, 0, 2);      // 2: by quarters of the slice only (no board)
   const uint32_t prio_tag = (++ctx->prio_seq & 0x7fffu) + 1u;     // (see k_accumulate: the wave that is behind asks for priority; 0 = the arbiter's own order)
-  if (ctx->K == 1 || dense)
+  if (edw)
+    hipLaunchKernelGGL(k_accumulate_edw, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off, cur_cnt, ctx->goff,
+                       (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
+  else if (ctx->K == 1 || dense)
     hipLaunchKernelGGL(k_accumulate<1>, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off, cur_cnt, ctx->goff,
                        (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
   else
     hipLaunchKernelGGL(k_accumulate<MSM_MAX_JOBS>, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off,
                        cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
   HIP_TRY(hipEventRecord(ctx->ev_acc1, st));
+  // psi: the Edwards slots (buckets, then the F and L pieces of the T_run slices) back to XYZZ
+  if (edw) {
+    const uint32_t n_conv = (uint32_t)nb + 2u * T_run;
+    hipLaunchKernelGGL(k_slots_edw_to_xyzz, dim3(nblk(n_conv, 256)), dim3(256), 0, st, ctx->buckets, ctx->slot_stride, n_conv);
+  }
   ctx->last_S = S_run; ctx->last_T = T_run; ctx->last_tight = tight;
   // fold the F pieces of the buckets that have several (lists made by k_accumulate), then L + F for every cut bucket
   if (T_run > 2) {
@@ -1771,7 +1904,7 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
                             (uint32_t)nb, ctx->buckets, ctx->slot_stride);
   }
   hipLaunchKernelGGL(k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run,
-                     ctx->buckets, ctx->slot_stride);
+                     ctx->buckets, ctx->slot_stride, wf);
   HIP_TRY(hipGetLastError());
 
   // ---- bucket reduction -------------------------------------------------------------------------------
@@ -1971,6 +2104,60 @@ int msm_table_build(AffPacked* d_table, uint8_t* d_tinf, size_t n, int c, int na
     return ZKHIP_ERR_HIP;
   }
   return ZKHIP_OK;
+}
+
+int msm_table_edw(const AffPacked* d_bases, const uint8_t* d_inf, size_t n, int c, EdwPacked** d_out, char* errbuf, size_t errlen) {
+  *d_out = nullptr;
+  if (n == 0) return ZKHIP_OK;
+  const size_t levels = (size_t)msm_table_levels(c, 0), chunk = n < ((size_t)1 << 21) ? n : ((size_t)1 << 21);
+  AffPacked* half = nullptr;
+  uint8_t* hinf = nullptr;
+  uint32_t *work = nullptr, *d_bad = nullptr, bad = 0;
+  EdwPacked* et = nullptr;
+  int rc = ZKHIP_OK;
+  hipError_t e = hipMalloc(&d_bad, 4);
+  if (e == hipSuccess) e = hipMemset(d_bad, 0, 4);
+  if (e == hipSuccess) e = hipMalloc(&half, levels * n * sizeof(AffPacked));
+  if (e == hipSuccess) e = hipMalloc(&hinf, levels * n);
+  if (e == hipSuccess) e = hipMemcpy(hinf, d_inf, n, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMalloc(&work, chunk * 108 * 4);
+  // level 0: H_i = [1/2] P_i, checked; the set is rejected (ZKHIP_ERR_ARG) before anything else is computed if a base fails
+  for (size_t i0 = 0; e == hipSuccess && i0 < n; i0 += chunk) {
+    const uint32_t cn = (uint32_t)(n - i0 < chunk ? n - i0 : chunk);
+    hipLaunchKernelGGL(k_half_bases, dim3(nblk(cn, 256)), dim3(256), 0, 0, d_bases, d_inf, half, i0, cn, work, d_bad);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && bad) {
+    if (errbuf) snprintf(errbuf, errlen, "msm_table_edw: %u bases are not points of order r on G1's curve", bad);
+    rc = ZKHIP_ERR_ARG;
+  }
+  if (e == hipSuccess && rc == ZKHIP_OK) {
+    if (work) { (void)hipFree(work); work = nullptr; }
+    // levels w >= 1: 2^(off_w) H_i = [1/2] 2^(off_w) P_i, by the table build itself; then chi of every entry
+    rc = msm_table_build(half, hinf, n, c, 0, errbuf, errlen);
+    if (rc == ZKHIP_OK) {
+      e = hipMemset(d_bad, 0, 4);
+      if (e == hipSuccess) e = hipMalloc(&et, levels * n * sizeof(EdwPacked));
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_table_edw, dim3(nblk(levels * n, 256)), dim3(256), 0, 0, half, hinf, et, levels * n, d_bad);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);      // (synchronises)
+      if (e == hipSuccess && bad) {                // (order-r points never hit chi's exceptional points: a failed check above)
+        if (errbuf) snprintf(errbuf, errlen, "msm_table_edw: %u table points without an Edwards image", bad);
+        rc = ZKHIP_ERR_ARG;
+      }
+    }
+  }
+  if (e != hipSuccess) {
+    if (errbuf) snprintf(errbuf, errlen, "msm_table_edw: %s", hipGetErrorString(e));
+    rc = ZKHIP_ERR_HIP;
+  }
+  for (void* q : {(void*)half, (void*)hinf, (void*)work, (void*)d_bad}) if (q) (void)hipFree(q);
+  if (rc == ZKHIP_OK) *d_out = et;
+  else if (et) (void)hipFree(et);
+  return rc;
 }
 
 // out[i] = k_i * base for i < n.  base: ABI affine (host); d_scalars, d_out: device memory.

@@ -36,6 +36,8 @@ struct zkhip_bases {
   size_t n_finite;   // bases that are not the point at infinity (counted at upload)
   int device;        // the GPU that holds them
   int plain_c = 0;   // plain base set: window of the MSMs over it (zkhip_bases_set_window; 0: by the number of terms)
+  EdwPacked* d_edw = nullptr;   // zkhip_bases_precompute[_ex] of a G1 set, one level per window: the table in precomputed Edwards form
+                                // (same shape as d_pts; msm.h msm_table_edw) - single MSMs over it accumulate on the Edwards curve
 };
 
 struct zkhip_r1cs {
@@ -352,17 +354,28 @@ static bool naf_tables_wanted(size_t total_points) {
   const int on = cur >= 0 ? cur : env_on;
   return on && naf_tables_fit(total_points);
 }
-static int bases_precompute_mode(zkhip_bases* b, int c, int naf);
+// Which point model the single MSMs over a one-level-per-window table accumulate in: G1's 2-isogenous twisted
+// Edwards curve (default; the table gets a second, precomputed Edwards form at precompute time), or XYZZ (ZKHIP_TABLE_MODEL=xyzz,
+// zkhip_set_table_model(0): A/B runs).  A set whose points are not of order r on G1's curve (G2) stays XYZZ whatever is asked.
+static std::atomic<int> g_table_model{-1};     // -1: the environment decides (default Edwards)
+int zkhip_set_table_model(int model) { g_table_model.store(model < 0 ? -1 : (model ? 1 : 0)); return ZKHIP_OK; }
+static bool edw_tables_wanted() {
+  static const int env_model = [] { const char* e = getenv("ZKHIP_TABLE_MODEL"); return (e && strcmp(e, "xyzz") == 0) ? 0 : 1; }();
+  const int cur = g_table_model.load();
+  return (cur >= 0 ? cur : env_model) != 0;
+}
+int zkhip_bases_table_model(const zkhip_bases* b) { return (b && b->d_edw) ? 1 : 0; }
+static int bases_precompute_mode(zkhip_bases* b, int c, int naf, bool edw = false);
 int zkhip_bases_precompute(zkhip_bases* b, int c) {
   if (!b) return fail(ZKHIP_ERR_ARG, "null pointer");
-  return bases_precompute_mode(b, c, naf_tables_wanted(b->len) ? 1 : 0);
+  return bases_precompute_mode(b, c, naf_tables_wanted(b->len) ? 1 : 0, edw_tables_wanted());
 }
 int zkhip_bases_precompute_ex(zkhip_bases* b, int c, int table_naf) {
   if (!b) return fail(ZKHIP_ERR_ARG, "null pointer");
   const int naf = table_naf < 0 ? (naf_tables_wanted(b->len) ? 1 : 0) : ((table_naf && naf_tables_fit(b->len)) ? 1 : 0);
-  return bases_precompute_mode(b, c, naf);
+  return bases_precompute_mode(b, c, naf, edw_tables_wanted());
 }
-static int bases_precompute_mode(zkhip_bases* b, int c, int naf) {
+static int bases_precompute_mode(zkhip_bases* b, int c, int naf, bool edw) {
   if (!b) return fail(ZKHIP_ERR_ARG, "null pointer");
   BIND(b);
   std::lock_guard<std::mutex> lk(g.dev[b->device].mu);
@@ -384,6 +397,22 @@ static int bases_precompute_mode(zkhip_bases* b, int c, int naf) {
   if (rc != ZKHIP_OK) { if (tab) (void)hipFree(tab); if (tinf) (void)hipFree(tinf); return rc; }
   (void)hipFree(b->d_pts); (void)hipFree(b->d_inf);
   b->d_pts = tab; b->d_inf = tinf; b->table_c = c; b->table_naf = naf;
+  // the Edwards form (one level per window only, and not for tables forced onto batched-affine levels: their accumulation is XYZZ's).
+  // It costs 1.5 x the table's memory for good (288-byte entries) and as much again while it is built (the halved table); it is built
+  // only when that leaves a quarter of the device's memory free for plans and other sets.  A set that is not of order r on G1's curve
+  // keeps the XYZZ path; any other failure is an error.
+  if (edw && !naf && msm_forced_aff_levels() <= 0) {
+    size_t mem_free = 0, mem_total = 0;
+    const size_t need = levels * b->len * (sizeof(AffPacked) + 1 + 288) + ((size_t)1 << 21) * 432;
+    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_free >= need + mem_total / 4) {
+      EdwPacked* et = nullptr;
+      char e_err[256];
+      rc = msm_table_edw(tab, tinf, b->len, c, &et, e_err, sizeof e_err);
+      if (rc == ZKHIP_OK) b->d_edw = et;
+      else if (rc == ZKHIP_ERR_HIP) { snprintf(t_err, sizeof t_err, "Edwards table: %s", e_err); return rc; }
+    }
+    (void)hipGetLastError();
+  }
   return ZKHIP_OK;
 }
 int zkhip_bases_table_window(const zkhip_bases* b) { return b ? b->table_c : 0; }
@@ -400,6 +429,7 @@ void zkhip_bases_free(zkhip_bases* b) {
   (void)bind_dev(b->device);
   if (b->d_pts) (void)hipFree(b->d_pts);
   if (b->d_inf) (void)hipFree(b->d_inf);
+  if (b->d_edw) (void)hipFree(b->d_edw);
   delete b;
 }
 
@@ -413,7 +443,7 @@ int zkhip_msm_dev(const zkhip_bases* bases, size_t offset, const void* d_scalars
   int rc = ensure_ctx(&ps.ctx[0], &ps.ready[0], len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
   if (rc != ZKHIP_OK) return rc;
   rc = msm_run(&ps.ctx[0], bases->d_pts + offset, bases->d_inf ? bases->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len,
-               scalars_montgomery, bases->len, out_jac);
+               scalars_montgomery, bases->len, out_jac, msm_edw_at(bases->d_edw, offset));
   if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", ps.ctx[0].errbuf);
   else { ps.last_acc_ctx = &ps.ctx[0]; ps.last_accumulate_ms = ps.ctx[0].last_accumulate_ms; ps.last_acc_interval[0] = ps.ctx[0].last_acc_begin_ms; ps.last_acc_interval[1] = ps.ctx[0].last_acc_end_ms; t_prove_dev = bases->device; }
   return rc;
@@ -440,7 +470,7 @@ int zkhip_msm_submit(const zkhip_bases* bases, size_t offset, const void* d_scal
   const int prev = ps.last_submit_slot;
   cx->acc_gate = (gate && prev >= 0 && prev != slot && ps.ready[prev]) ? ps.ctx[prev].ev_acc1 : nullptr;
   rc = msm_launch(cx, bases->d_pts + offset, bases->d_inf ? bases->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len,
-                  scalars_montgomery, bases->len);
+                  scalars_montgomery, bases->len, msm_edw_at(bases->d_edw, offset));
   cx->acc_gate = nullptr;                   // (the event belongs to another context: never kept beyond this launch)
   if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", cx->errbuf);
   else if (len) ps.last_submit_slot = slot;
@@ -2115,7 +2145,8 @@ static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const voi
     API_HIP(hipMemcpyAsync(st->d_stage[slot], h_scalars, len * 48, hipMemcpyHostToDevice, cx->stream));
     d_scalars = st->d_stage[slot];
   }
-  rc = msm_launch(cx, b->d_pts + offset, b->d_inf ? b->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len, scalars_montgomery, b->len);
+  rc = msm_launch(cx, b->d_pts + offset, b->d_inf ? b->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len, scalars_montgomery, b->len,
+                  msm_edw_at(b->d_edw, offset));
   if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cx->errbuf); return rc; }
   st->ticket_of[slot] = st->next_ticket;
   *ticket = st->next_ticket++;

@@ -17,7 +17,7 @@ EXPORTS = [
     "zkhip_bases_precompute", "zkhip_bases_table_window", "zkhip_set_crs_precompute", "zkhip_crs_table_window", "zkhip_set_batch_msms",
     "zkhip_msm", "zkhip_msm_dev", "zkhip_msm_raw", "zkhip_msm_submit", "zkhip_msm_collect",
     "zkhip_device_alloc", "zkhip_device_free", "zkhip_device_copy_in", "zkhip_last_accumulate_ms", "zkhip_last_accumulate_entries", "zkhip_prover_last_accumulate_entries",
-    "zkhip_prover_set_streaming", "zkhip_set_table_naf", "zkhip_fixed_base_mul", "zkhip_fixed_base_mul_dev", "zkhip_ntt", "zkhip_ntt_dev",
+    "zkhip_prover_set_streaming", "zkhip_set_table_naf", "zkhip_set_table_model", "zkhip_bases_table_model", "zkhip_fixed_base_mul", "zkhip_fixed_base_mul_dev", "zkhip_ntt", "zkhip_ntt_dev",
     "zkhip_r1cs_upload", "zkhip_r1cs_upload_ex", "zkhip_r1cs_set_domain", "zkhip_r1cs_free", "zkhip_r1cs_log_domain", "zkhip_r1cs_domain_size",
     "zkhip_domain_size", "zkhip_step_domain_size", "zkhip_domain_is_valid", "zkhip_groth16_setup_ex", "zkhip_dispatcher_outstanding", "zkhip_r1cs_is_satisfied", "zkhip_qap_h",
     "zkhip_crs_upload", "zkhip_crs_free", "zkhip_groth16_prove", "zkhip_last_prove_timings", "zkhip_groth16_verify",
@@ -246,6 +246,11 @@ def set_table_naf(on):
     _check(load().zkhip_set_table_naf(int(on)))
 
 
+def set_table_model(model):
+    """point model of the single MSMs over window tables built from now on (zkhip_set_table_model): 1 Edwards, 0 XYZZ, -1 environment"""
+    _check(load().zkhip_set_table_model(int(model)))
+
+
 def set_crs_precompute(on):
     """Whether Crs uploads build window tables for the five query vectors (default: on)."""
     _check(load().zkhip_set_crs_precompute(int(bool(on))))
@@ -282,6 +287,12 @@ class Bases:
     @property
     def table_window(self):
         return load().zkhip_bases_table_window(self.handle)
+
+    @property
+    def table_model(self):
+        """1: single MSMs over this set accumulate on G1's 2-isogenous Edwards curve, 0: in XYZZ"""
+        load().zkhip_bases_table_model.argtypes = [ctypes.c_void_p]
+        return load().zkhip_bases_table_model(self.handle)
 
     def set_window(self, c):
         """Plain base set: window of the MSMs over it (0 = by the number of terms); an option of this handle."""
