@@ -531,6 +531,43 @@ int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n,
  * tables freed at once (run under the CPU AddressSanitizer build); a delta of small order (`small_order_g1`, e.g. (1, 0)) whose
  * fixed-base table must be refused in favour of variable-base products.  g1 / g2: the curve generators, 24 limbs each. */
 int zkhip_internal_tail_selftest(const uint64_t g1[24], const uint64_t g2[24], const uint64_t small_order_g1[24], int rounds);
+/* Test hooks of the GPU witness generator (no counterpart).  A laid-out straight-line program over Fr as witness.hip interprets it
+ * (witness_tape.h has the instruction codes): positions [0, chain_start) in levels of whole 64-position chunks, run by k_witness,
+ * positions [chain_start, n_pos) in execution order, run by k_witness_chain; operands >= 0 name an earlier position, < 0 the
+ * constant -1 - index; assignment entry i is the value at out_ref[i]. */
+typedef struct zkhip_witness_program {
+  const uint8_t* code;
+  const int32_t* a;
+  const int32_t* b;
+  size_t n_pos;
+  const uint32_t* level_start; /* n_levels + 1 positions, the last one = chain_start */
+  size_t n_levels;
+  uint32_t chain_start;
+  const int32_t* out_ref;
+  size_t n_vars;
+  const uint64_t* consts; /* n_consts x 6 limbs, ABI form */
+  size_t n_consts;
+  size_t n_inputs;
+} zkhip_witness_program;
+/* Runs a caller's program through the product's own upload, launch and kernels: `batches` (0 .. 256) input vectors of n_inputs x 6
+ * limbs (ABI form), `witnesses_per_workgroup` 1, 2 or 4, `segment_chunks` chunks of the levelled part per launch (1 .. 2^20).
+ * z_out: batches x n_vars x 6 limbs (ABI form, canonical); flags_out: one word per batch, non-zero where a WT_INV met zero.
+ * The program is VALIDATED on the host first - every level whole chunks; a levelled operand in an earlier level, a chain operand
+ * earlier in the chain and not before chain_start; constant, input and out_ref indices in range; bit index below 384; k of
+ * WT_SUBK + k in 1 .. 11; no WT_SUB, no unknown code - and refused with ZKHIP_ERR_ARG before anything is uploaded, so an accepted
+ * program cannot address outside its buffers.  batches = 0 validates only and needs no device.  The VALUE contract (bounds of the
+ * lazy reduction: sums up to 2^12 r, subtrahends up to 2^k r, inversion operands up to 4 r) is the caller's: breaking it gives
+ * wrong values, never a wrong address. */
+int zkhip_internal_witness_run_program(const zkhip_witness_program* p, const uint64_t* inputs, size_t batches, int witnesses_per_workgroup,
+                                       unsigned segment_chunks, uint64_t* z_out, uint32_t* flags_out);
+/* HOST ONLY: the recorded program of the circuit, as zkhip_gpu_witness_run uploads it (pointers into the handle, valid until
+ * zkhip_aggregator_free). */
+int zkhip_internal_witness_tape(zkhip_aggregator* a, zkhip_witness_program* out);
+/* zkhip_gpu_witness_run_batched (app = null) or zkhip_gpu_witness_run_batched_app (nested_vk = null) with the launch's two tuning
+ * knobs given by the caller instead of ZKHIP_WITNESS_WPG / ZKHIP_WITNESS_SEGMENT: 0 = the process-wide default. */
+int zkhip_internal_gpu_witness_run(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk,
+                                   const uint64_t* const* nested_proofs, const uint64_t* const* nested_inputs, void* d_z_out,
+                                   uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup, unsigned segment_chunks);
 
 /* replaces: libff::Fr<wppT>::random_element() as r1cs_gg_ppzksnark_prover draws the proof's randomisers r, s (reached from
  * aggregator_circuit.tcc:168) and the generator its toxic waste: one field element uniform in Fr, 6 Montgomery limbs, from the

@@ -1,7 +1,8 @@
 """The DEVICE build's multiplier bodies (fp29.cuh -> fp29_chain.cuh: every column one dependent chain of v_mad_u64_u32 in asm
 blocks) on raw limbs, through the C ABI's test hook, against big integers: the counterpart of tests/test_fp29_host.py (which checks
 the C++ bodies g++ compiles).  The cases are the ones that decide whether a 64-bit column accumulator holds: every limb at 2^29 - 1,
-the top limb at the lazy bound 2^10 p, mixtures of full and random limbs, zeros and ones."""
+the top limb at the lazy bound - 2^10 p for Fq, 2^12 r for Fr, which is what the witness tape allows an operand of WT_MUL
+(witness_tape.cpp, CAP = 4096) - mixtures of full and random limbs, zeros and ones."""
 import random
 
 import numpy as np
@@ -16,8 +17,8 @@ def _val(limbs):
     return sum(int(v) << (29 * i) for i, v in enumerate(limbs))
 
 
-def _cases(p, nl, rng, n_random):
-    top_max = (p << 10) >> (29 * (nl - 1))              # top limb of values below 2^10 p
+def _cases(p, nl, rng, n_random, log_bound=10):
+    top_max = (p << log_bound) >> (29 * (nl - 1))       # top limb of values below 2^10 p (Fq) / 2^12 r (Fr)
     full = [(1 << 29) - 1] * (nl - 1)
     Rdev = 1 << (29 * nl)
     cases = [[full + [top_max - 1]] * 4, [[0] * nl] * 4, [[1] + [0] * (nl - 1)] * 4,
@@ -38,7 +39,7 @@ def _cases(p, nl, rng, n_random):
 @pytest.mark.parametrize("field,p,nl", [(0, R.Q_MOD, 27), (1, R.R_MOD, 14)])
 def test_device_multiplier_bodies_on_raw_limbs(zk, field, p, nl):
     rng = random.Random(29 + field)
-    cases = _cases(p, nl, rng, 600)
+    cases = _cases(p, nl, rng, 600, 10 if field == 0 else 12)
     got = zk.field_selftest(field, np.array(cases, dtype=np.uint32))
     Rdev = 1 << (29 * nl)
     rinv = pow(Rdev, -1, p)

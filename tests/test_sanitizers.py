@@ -29,7 +29,8 @@ def test_gpu_witness_program_on_the_cpu_under_asan_ubsan(tmp_path):
     """The GPU witness generator's PROGRAM without a GPU (tools/sanitize/tape_check.cpp): the tape builder (recording, balanced
     sums, bounds for the lazy reduction, levels by kind, the key-hash chain) runs under ASan + UBSan; the tape's structure and the
     bounds the device relies on are re-derived independently; interpreted with the host field arithmetic it must reproduce the host
-    generator's assignment limb for limb - for the valid batch and for a batch with a bumped (invalid) nested input."""
+    generator's assignment limb for limb - for the valid batch and for a batch with a bumped (invalid) nested input; and the same for
+    the other circuit shapes the device runs (tests/test_witness_gpu.py): batches of 1 and 3, nine inputs per nested proof."""
     import bench
     nvk_l, npr, nin, _ = bench.aggregator_inputs()
     exe = tmp_path / "tape_check"
@@ -44,6 +45,14 @@ def test_gpu_witness_program_on_the_cpu_under_asan_ubsan(tmp_path):
         inp = tmp_path / (name + ".bin")
         np.concatenate([nvk_l, npr, inputs.reshape(-1)]).astype(np.uint64).tofile(inp)
         out = subprocess.run([str(exe), str(inp)], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+        assert out.returncode == 0, out.stdout + out.stderr
+        assert "differences=0" in out.stdout and "FAIL" not in out.stdout, out.stdout
+        assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr
+    from tests.test_witness_gpu import _batch
+    for num_proofs, k, bump in ((1, 1, False), (3, 1, True), (2, 9, False)):
+        inp = tmp_path / ("shape_%d_%d.bin" % (num_proofs, k))
+        np.concatenate([x.reshape(-1) for x in _batch(num_proofs, k, bump)]).astype(np.uint64).tofile(inp)
+        out = subprocess.run([str(exe), str(inp), str(num_proofs), str(k)], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
         assert out.returncode == 0, out.stdout + out.stderr
         assert "differences=0" in out.stdout and "FAIL" not in out.stdout, out.stdout
         assert "ERROR" not in out.stderr and "runtime error" not in out.stderr, out.stderr

@@ -1,4 +1,5 @@
-// CPU check of the GPU witness generator's PROGRAM (witness_tape.cpp), no GPU involved: the tape of the batch-2 circuit is built,
+// CPU check of the GPU witness generator's PROGRAM (witness_tape.cpp), no GPU involved: the tape of a circuit (batch 2, one input per
+// nested proof, unless the shape is given: tape_check INPUT [NUM_PROOFS INPUTS_PER_PROOF]) is built,
 // its structure is verified - every operand defined in an earlier level (levelled part) or earlier in the chain (key-hash part),
 // the static bounds the device relies on recomputed independently (a - b + 2^k r only with b below 2^k r, nothing above 2^12 r,
 // inversions fed below 4 r) - and it is interpreted with the host field arithmetic; the assignment it produces must equal the host
@@ -17,21 +18,24 @@ using namespace zkhip;
 #define FAIL(...) do { printf("FAIL: " __VA_ARGS__); printf("\n"); return 1; } while (0)
 
 int main(int argc, char** argv) {
-  if (argc < 2) return 2;
+  if (argc != 2 && argc != 4) return 2;
+  const size_t num_proofs = argc == 4 ? (size_t)atoi(argv[2]) : 2, per_proof = argc == 4 ? (size_t)atoi(argv[3]) : 1;
+  if (num_proofs < 1 || num_proofs > 8 || per_proof < 1 || per_proof > 32) return 2;
+  const size_t vk_w = 60 + 12 * (per_proof + 1), pr_w = 48 * num_proofs;      // nested key | nested proofs | nested inputs
   FILE* f = fopen(argv[1], "rb");
-  std::vector<uint64_t> in(84 + 96 + 12);
+  std::vector<uint64_t> in(vk_w + pr_w + 6 * per_proof * num_proofs);
   if (!f || fread(in.data(), 8, in.size(), f) != in.size()) { puts("bad input"); return 2; }
   fclose(f);
   zkhip_aggregator* a = nullptr;
-  if (zkhip_aggregator_new(2, 1, &a) != 0) return 3;
+  if (zkhip_aggregator_new(num_proofs, per_proof, &a) != 0) return 3;
   zkhip_r1cs_desc d;
   zkhip_aggregator_get_r1cs(a, &d);
   std::vector<uint64_t> z(d.n_vars * 6);
-  if (zkhip_aggregator_witness(a, in.data(), in.data() + 84, in.data() + 180, z.data()) != 0) return 4;
+  if (zkhip_aggregator_witness(a, in.data(), in.data() + vk_w, in.data() + vk_w + pr_w, z.data()) != 0) return 4;
 
   WitnessTape T;
   std::string err;
-  if (witness_tape_build(2, 1, &T, &err) != 0) FAIL("tape build: %s", err.c_str());
+  if (witness_tape_build(num_proofs, per_proof, &T, &err) != 0) FAIL("tape build: %s", err.c_str());
   if (T.n_vars != d.n_vars || T.n_inputs * 6 != in.size()) FAIL("tape shape: %zu variables, %zu inputs", T.n_vars, T.n_inputs);
   const size_t n = T.code.size(), cs = T.chain_start;
   if (cs % 64 || T.level_start.empty() || T.level_start.back() != cs) FAIL("layout: chain_start %zu, last level end %u", cs, T.level_start.back());

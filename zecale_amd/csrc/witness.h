@@ -30,9 +30,16 @@ int witness_prog_upload(const WitnessTape& T, WitnessProgDev* out, char* err, si
 void witness_prog_free(WitnessProgDev* pd);
 // the program of `a` on the calling thread's current device (recorded and uploaded on first use)
 int witness_prog(zkhip_aggregator* a, WitnessProg* out, const WitnessTape** tape, char* err, size_t errlen);
-// one workgroup per batch; inputs: batches x n_inputs x 6 u64 (ABI form: nested key | proofs | inputs); values: batches x n_pos x 16 u32 (witness_value_bytes);
+// the recorded program alone (host code: no device needed); it lives as long as `a`
+int witness_tape_of(zkhip_aggregator* a, const WitnessTape** tape, char* err, size_t errlen);
+// the process-wide defaults of witness_launch's two knobs: ZKHIP_WITNESS_WPG (1 | 2 | 4, default 4) and ZKHIP_WITNESS_SEGMENT
+// (64 .. 2^20 chunks, default 2,048), each read once
+uint32_t witness_env_wpg();
+uint32_t witness_env_segment();
+// wpg: witnesses per workgroup, a wave each (1, 2 or 4; anything else = 4); seg: chunks of the levelled program per launch (>= 1);
+// inputs: batches x n_inputs x 6 u64 (ABI form: nested key | proofs | inputs); values: batches x n_pos x 16 u32 (witness_value_bytes);
 // z: batches x n_vars x 6 u64 (ABI form); flags: one word per batch, set when an inversion met zero (cleared by the caller)
 constexpr size_t witness_value_bytes = 64;      // one value slot
 void witness_launch(const WitnessProg& P, const uint64_t* d_inputs, uint32_t* d_values, uint64_t* d_z, uint32_t* d_flags, uint32_t batches,
-                    hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join);
+                    uint32_t wpg, uint32_t seg, hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join);
 }  // namespace zkhip

@@ -31,7 +31,7 @@ typedef Fp<FrParams> FrD;
 
 // A value slot: the 14 limbs of the device form as they are (no packing: an addition is then 14 adds and a carry pass), padded
 // to 16 words = 64 bytes.  Values are LAZILY reduced: the tape builder tracks an upper bound (a multiple of r) for every value,
-// picks the subtraction's K r accordingly and inserts a reduction where a bound would pass 256 r (witness_tape.cpp).
+// picks the subtraction's K r accordingly and inserts a reduction where a bound would pass 2^12 r (witness_tape.cpp, CAP).
 constexpr int WSLOT = 16;
 struct WVal { uint4 q[4]; };
 __device__ __forceinline__ FrD w_from(const WVal& v) {
@@ -125,7 +125,8 @@ __device__ __forceinline__ bool w_exec(uint32_t c, int32_t rb, const FrD& x, con
 // program being static, almost all of it is taken off the critical path:
 //   * the instruction words are fetched three chunks ahead;
 //   * the last RING results wait in an LDS ring (slot = position mod RING; 1,024 = the last 16 chunks held nine operands in ten);
-//   * an older operand is loaded from the value array one chunk ahead (its store is many chunks old).
+//   * an older operand is loaded from the value array one chunk ahead.  Its store is at least RING / 64 - 1 chunks old when the load
+//     is issued (three with the 256-entry ring, fifteen with 1,024) and was made by this same wave: see ring_lo.
 // (A witness is cut into several launches of a few milliseconds so that the kernels of the provers that share a hardware queue
 // with it are not held up for its whole duration.)
 struct WIns { uint32_t code; int32_t a, b; };
@@ -167,6 +168,8 @@ constexpr int WIT_PRIO = ZK_WITNESS_PRIO;
 template <uint32_t WPG, uint32_t WIT_RING>
 __global__ void __launch_bounds__(64 * WPG) k_witness(WitnessProg P, uint32_t c0, uint32_t c1, const uint64_t* __restrict__ inputs /* batches x n_inputs x 6, ABI */,
                                                        uint32_t* __restrict__ values /* batches x n_pos x 16 */, uint32_t* __restrict__ flags, uint32_t n_batches) {
+  // a ring of fewer than four chunks would let the chunk-ahead prefetch reach a store with fewer than three fences behind it (ring_lo)
+  static_assert(WIT_RING >= 256 && WIT_RING % 64 == 0, "k_witness: the ring holds at least four whole chunks");
   __shared__ uint4 ring_all[WPG * WIT_RING * 4];
   __shared__ uint4 subk[WT_SUBK_LEVELS * 4];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -186,7 +189,17 @@ __global__ void __launch_bounds__(64 * WPG) k_witness(WitnessProg P, uint32_t c0
   uint32_t bad = 0;
   // one chunk: `cur` with its prefetched operands (cx, cy); `nxt` is the chunk after it, whose operands are requested here
   auto step = [&](uint32_t j, const WIns& cur, WVal& cx, WVal& cy, const WIns& nxt, WVal& nx, WVal& ny) {
-    // chunk i finds in the ring what this launch wrote and chunk i itself does not overwrite: positions from ring_lo(i) on
+    // chunk i finds in the ring what this launch wrote and chunk i itself does not overwrite: positions from ring_lo(i) on.
+    // Everything below ring_lo(i) comes from the value array, and its load is issued during chunk i - 1 (w_prefetch with
+    // ring_lo(j + 1)), as a rule by ANOTHER LANE than the one that stored it.  Why that load sees the store: a position below
+    // ring_lo(j + 1) either precedes c0 * 64 - written by an earlier launch on the same stream, complete before this kernel began -
+    // or is below (j + 2) * 64 - WIT_RING, i.e. it belongs to chunk j + 1 - WIT_RING / 64 of THIS wave or an older one: with
+    // WIT_RING >= 256 (the static_assert above) that is chunk j - 3 at the latest.  Its store was issued in step(j - 3); every
+    // step() ends with a release fence at wavefront scope and a wave barrier, and the loads and stores of one wave go to one address
+    // through the same L1 / L2 path in the order the wave issued them: a load issued three fences after the store cannot overtake
+    // it.  No other wave ever writes this batch's values while the launch runs, so wavefront scope is all that is needed - whatever
+    // the number of witnesses per workgroup.  (tests/test_witness_programs_gpu.py puts operands on both sides of this boundary for
+    // 1, 2 and 4 witnesses per workgroup and odd and even segment starts.)
     auto ring_lo = [&](uint32_t i) { const uint32_t w = (i + 1) * 64; return max(c0 * 64, w > WIT_RING ? w - WIT_RING : 0u); };
     w_prefetch(P, vals, nxt, ring_lo(j + 1), nx, ny);
     const uint32_t lim = ring_lo(j);
@@ -278,7 +291,7 @@ __global__ void __launch_bounds__(256) k_witness_out(WitnessProg P, const uint32
   const int32_t ref = P.out_ref[i];
   FrD v = w_from(w_ld(reinterpret_cast<const uint4*>(ref >= 0 ? vals + (size_t)ref * WSLOT : P.consts + (size_t)(-1 - ref) * WSLOT)));
   uint64_t w[6];
-  fp_to_abi<FrParams>(v, w);                                       // (a full reduction: any bound below 2^10 r)
+  fp_to_abi<FrParams>(v, w);                                       // (a full reduction for every bound the tape allows: v <= 2^12 r times a constant below r stays below R r, R = 2^406)
   uint64_t* z = z_out + ((size_t)batch * P.n_vars + i) * 6;
 #pragma unroll
   for (int k = 0; k < 6; k++) z[k] = w[k];
@@ -343,7 +356,7 @@ int witness_prog_upload(const WitnessTape& T, WitnessProgDev* out, char* err, si
   }
   if (e == hipSuccess) e = hipMalloc(&d_c64, nc * 48 + 48);
   if (e == hipSuccess) e = hipMemcpy(d_c64, T.consts.data(), nc * 48, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
+  if (e == hipSuccess && nc) {               // (a program without constants: an empty grid is an invalid launch)
     hipLaunchKernelGGL(k_witness_consts, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, 0, d_c64, (uint32_t*)pd.bufs[5], (uint32_t)nc);
     e = hipDeviceSynchronize();
   }
@@ -361,8 +374,8 @@ int witness_prog_upload(const WitnessTape& T, WitnessProgDev* out, char* err, si
 }
 
 // the program of `a` on the calling thread's current device (built and uploaded on first use)
-int witness_prog(zkhip_aggregator* a, WitnessProg* out, const WitnessTape** tape, char* err, size_t errlen) {
-  std::lock_guard<std::mutex> lk(a->gpu_mu);
+// the recorded program of `a` (built on first use; host code, a->gpu_mu held)
+static int tape_locked(zkhip_aggregator* a, GpuWitnessState** out, char* err, size_t errlen) {
   if (!a->gpu_state) { a->gpu_state = new GpuWitnessState(); a->gpu_release = gpu_release; }
   GpuWitnessState* st = (GpuWitnessState*)a->gpu_state;
   if (!st->built) {
@@ -371,6 +384,23 @@ int witness_prog(zkhip_aggregator* a, WitnessProg* out, const WitnessTape** tape
     if (st->tape.n_vars != a->n_vars) { snprintf(err, errlen, "witness tape: %zu variables, the circuit has %zu", st->tape.n_vars, a->n_vars); return ZKHIP_ERR_STATE; }
     st->built = true;
   }
+  *out = st;
+  return ZKHIP_OK;
+}
+
+int witness_tape_of(zkhip_aggregator* a, const WitnessTape** tape, char* err, size_t errlen) {
+  std::lock_guard<std::mutex> lk(a->gpu_mu);
+  GpuWitnessState* st = nullptr;
+  int rc = tape_locked(a, &st, err, errlen);
+  if (rc == ZKHIP_OK) *tape = &st->tape;
+  return rc;
+}
+
+int witness_prog(zkhip_aggregator* a, WitnessProg* out, const WitnessTape** tape, char* err, size_t errlen) {
+  std::lock_guard<std::mutex> lk(a->gpu_mu);
+  GpuWitnessState* st = nullptr;
+  int rc0 = tape_locked(a, &st, err, errlen);
+  if (rc0 != ZKHIP_OK) return rc0;
   int device = 0;
   if (hipGetDevice(&device) != hipSuccess) { snprintf(err, errlen, "hipGetDevice failed"); return ZKHIP_ERR_HIP; }
   auto it = st->dev.find(device);
@@ -385,19 +415,30 @@ int witness_prog(zkhip_aggregator* a, WitnessProg* out, const WitnessTape** tape
   return ZKHIP_OK;
 }
 
+// The two tuning knobs as the product's entry points pass them to witness_launch (read once per process).
+// chunks per launch: a few milliseconds (ZKHIP_WITNESS_SEGMENT: 64 .. 2^20, default 2,048)
+uint32_t witness_env_segment() {
+  static const uint32_t seg_env = [] { const char* e = getenv("ZKHIP_WITNESS_SEGMENT"); int v = e ? atoi(e) : 0; return (uint32_t)(v >= 64 && v <= (1 << 20) ? v : 2048); }();
+  return seg_env;
+}
+// witnesses per workgroup (see k_witness): 4 by default; ZKHIP_WITNESS_WPG = 1 | 2 | 4 (1: rounds 3-5's form, a 64 KiB ring per witness)
+uint32_t witness_env_wpg() {
+  static const int wpg = [] { const char* e = getenv("ZKHIP_WITNESS_WPG"); const int v = e ? atoi(e) : 4; return (v == 1 || v == 2 || v == 4) ? v : 4; }();
+  return (uint32_t)wpg;
+}
+
 void witness_launch(const WitnessProg& P, const uint64_t* d_inputs, uint32_t* d_values, uint64_t* d_z, uint32_t* d_flags, uint32_t batches,
-                    hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join) {
+                    uint32_t wpg, uint32_t seg, hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  if (wpg != 1 && wpg != 2) wpg = 4;
+  if (seg < 1) seg = 1;
   // the key-hash chain on a second stream, next to the levelled program; the assignment is gathered when both are done
   (void)hipEventRecord(ev_fork, st);
   (void)hipStreamWaitEvent(st_chain, ev_fork, 0);
   if (P.chain_start < P.n_pos) hipLaunchKernelGGL(k_witness_chain, dim3(batches), dim3(64), 0, st_chain, P, P.chain_start, d_inputs, d_values, d_flags);
   (void)hipEventRecord(ev_join, st_chain);
-  static const uint32_t seg_env = [] { const char* e = getenv("ZKHIP_WITNESS_SEGMENT"); int v = e ? atoi(e) : 0; return (uint32_t)(v >= 64 && v <= (1 << 20) ? v : 2048); }();
-  const uint32_t n_chunks = P.chain_start / 64, seg = seg_env;       // chunks per launch: a few milliseconds (tuning knob: ZKHIP_WITNESS_SEGMENT)
-  // witnesses per workgroup (see k_witness): 4 by default; ZKHIP_WITNESS_WPG = 1 | 2 | 4 (1: rounds 3-5's form, a 64 KiB ring per witness)
-  static const int wpg = [] { const char* e = getenv("ZKHIP_WITNESS_WPG"); const int v = e ? atoi(e) : 4; return (v == 1 || v == 2 || v == 4) ? v : 4; }();
+  const uint32_t n_chunks = P.chain_start / 64;
   for (uint32_t c0 = 0; c0 < n_chunks; c0 += seg) {
-    const uint32_t c1 = c0 + seg < n_chunks ? c0 + seg : n_chunks;
+    const uint32_t c1 = n_chunks - c0 > seg ? c0 + seg : n_chunks;
     if (wpg == 4) hipLaunchKernelGGL((k_witness<4, 256>), dim3((batches + 3) / 4), dim3(256), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
     else if (wpg == 2) hipLaunchKernelGGL((k_witness<2, 512>), dim3((batches + 1) / 2), dim3(128), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
     else hipLaunchKernelGGL((k_witness<1, 1024>), dim3(batches), dim3(64), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);

@@ -14,7 +14,7 @@ enum : uint8_t {
   WT_INPUT = 1,   // a: index of the input element (nested key | nested proofs | nested inputs, 6 limbs each)
   WT_ADD = 2,     // a + b, NOT reduced: the builder tracks an upper bound (a multiple of r) for every value
   WT_SUB = 3,     // a - b as recorded; the laid-out program holds WT_SUBK + log2 K instead
-  WT_MUL = 4,     // Montgomery product: below 2r whatever the operands' bounds (they stay below 2^10 r)
+  WT_MUL = 4,     // Montgomery product: below 2r whatever the operands' bounds (they stay below 2^12 r each: a b < 2^24 r^2 < 2^406 r)
   WT_INV = 5,     // inversion of a value that is never zero for well-formed inputs (the device raises a flag if it is)
   WT_INV0 = 6,    // inversion that maps 0 to 0 by design (the is-zero gadget's hint)
   WT_BIT = 7,     // bit b of the canonical integer of a, as a field element

@@ -1931,7 +1931,8 @@ void zkhip_gpu_witness_free(zkhip_gpu_witness* w) {
 // memory, contiguous; primary_inputs: n x n_primary x 6 limbs (host, may be null); degenerate[i] = 1 where an inversion met zero
 // (that batch's assignment is unusable: use the host generator).
 static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
-                                const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate) {
+                                const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate,
+                                uint32_t wpg, uint32_t seg /* witness_launch's knobs: the product passes witness_env_wpg() / _segment() */) {
   if (!w || (!app && !nested_vk) || !nested_proofs || !nested_inputs || !d_z_out || !degenerate) return fail(ZKHIP_ERR_ARG, "null pointer");
   if (n < 1 || n > w->max_batches) return fail(ZKHIP_ERR_ARG, "more batches than the work space holds");
   BIND(w);
@@ -1961,7 +1962,7 @@ static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app,
   uint64_t* h_prim = h_flags + w->max_batches;
   API_HIP(hipMemcpyAsync(w->d_in, w->h_in, n * w->in_words * 8, hipMemcpyHostToDevice, w->st));
   API_HIP(hipMemsetAsync(w->d_flag, 0, n * 4, w->st));
-  witness_launch(prog, w->d_in, w->d_vals, (uint64_t*)d_z_out, w->d_flag, (uint32_t)n, w->st, w->st2, w->ev_fork, w->ev_join);
+  witness_launch(prog, w->d_in, w->d_vals, (uint64_t*)d_z_out, w->d_flag, (uint32_t)n, wpg, seg, w->st, w->st2, w->ev_fork, w->ev_join);
   API_HIP(hipGetLastError());
   API_HIP(hipMemcpyAsync(h_flags, w->d_flag, n * 4, hipMemcpyDeviceToHost, w->st));
   for (size_t i = 0; i < n; i++)
@@ -1975,14 +1976,24 @@ static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app,
 
 int zkhip_gpu_witness_run_batched(zkhip_gpu_witness* w, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
                                   const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate) {
-  return gpu_witness_run_impl(w, nullptr, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate);
+  return gpu_witness_run_impl(w, nullptr, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witness_env_wpg(), witness_env_segment());
 }
 // the same for batches of ONE registered application: MASKED assignments (zeros at the application's constant positions), ready for
 // zkhip_prover_prove_app_dev
 int zkhip_gpu_witness_run_batched_app(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_proofs,
                                       const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate) {
   if (!app) return fail(ZKHIP_ERR_ARG, "null pointer");
-  return gpu_witness_run_impl(w, app, n, nullptr, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate);
+  return gpu_witness_run_impl(w, app, n, nullptr, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witness_env_wpg(), witness_env_segment());
+}
+// Test hook: either of the two above with witness_launch's knobs given by the caller (0 = the process-wide default)
+int zkhip_internal_gpu_witness_run(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
+                                   const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup,
+                                   unsigned segment_chunks) {
+  if (witnesses_per_workgroup != 0 && witnesses_per_workgroup != 1 && witnesses_per_workgroup != 2 && witnesses_per_workgroup != 4)
+    return fail(ZKHIP_ERR_ARG, "witnesses per workgroup: 0 (default), 1, 2 or 4");
+  if (segment_chunks > (1u << 20)) return fail(ZKHIP_ERR_ARG, "segment: at most 2^20 chunks");
+  return gpu_witness_run_impl(w, app, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate,
+                              witnesses_per_workgroup ? (uint32_t)witnesses_per_workgroup : witness_env_wpg(), segment_chunks ? segment_chunks : witness_env_segment());
 }
 
 int zkhip_gpu_witness_run(zkhip_gpu_witness* w, const uint64_t* nested_vk, const uint64_t* nested_proofs, const uint64_t* nested_inputs,
@@ -2018,6 +2029,122 @@ int zkhip_gpu_witness_stats(zkhip_aggregator* a, size_t out[6]) {
   int rc = witness_prog(a, &P, &T, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
   out[0] = T->n_recorded; out[1] = T->code.size(); out[2] = T->level_start.size() - 1; out[3] = T->n_mul; out[4] = T->n_inv; out[5] = T->consts.size() / 6;
+  return ZKHIP_OK;
+}
+
+// ---- test hooks of the witness interpreter ----------------------------------------------------------------------------------
+// The structural rules of tools/sanitize/tape_check.cpp: a program that passes cannot address outside its buffers on the device -
+// every operand is a constant in range or an earlier position of the same part, every input and bit index is in range, the
+// levelled part is whole chunks (k_witness fetches 64 positions at a time), every code is one w_exec knows.
+static const char* witness_program_check(const zkhip_witness_program* p) {
+  if (!p) return "null program";
+  const size_t n = p->n_pos, cs = p->chain_start;
+  if (n > (1u << 26) || p->n_consts > (1u << 26) || p->n_inputs > (1u << 26) || p->n_vars > (1u << 26) || p->n_levels > (1u << 26)) return "program too large";
+  if ((n && (!p->code || !p->a || !p->b)) || !p->level_start || (p->n_vars && !p->out_ref) || (p->n_consts && !p->consts)) return "null array";
+  if (n < 1 || p->n_vars < 1) return "empty program";
+  if (cs > n || cs % 64) return "chain_start is not a chunk boundary inside the program";
+  if (p->level_start[0] != 0 || p->level_start[p->n_levels] != cs) return "the levels do not cover [0, chain_start)";
+  std::vector<uint32_t> level_begin(cs, 0);
+  for (size_t l = 0; l < p->n_levels; l++) {
+    const uint32_t b = p->level_start[l], e = p->level_start[l + 1];
+    if (b % 64 || e % 64 || b > e || e > cs) return "a level is not a whole number of 64-position chunks";
+    for (uint32_t q = b; q < e; q++) level_begin[q] = b;
+  }
+  std::vector<uint8_t> defined(n, 0);
+  for (size_t q = 0; q < n; q++) {
+    const uint8_t c = p->code[q];
+    if (c == WT_NOP) continue;
+    const bool chain = q >= cs;
+    auto ref_ok = [&](int32_t r) -> bool {
+      if (r < 0) return (size_t)(-1 - (int64_t)r) < p->n_consts;
+      if ((size_t)r >= q || !defined[r]) return false;
+      return chain ? (size_t)r >= cs : (size_t)r < level_begin[q];
+    };
+    if (c == WT_INPUT) {
+      if (p->a[q] < 0 || (size_t)p->a[q] >= p->n_inputs) return "input index out of range";
+    } else if (c == WT_ADD || c == WT_MUL || c >= WT_SUBK) {
+      if (c >= WT_SUBK && (c - WT_SUBK < 1 || c - WT_SUBK > 11)) return "a - b + 2^k r with k outside 1 .. 11";
+      if (!ref_ok(p->a[q]) || !ref_ok(p->b[q])) return "operand not defined before its reader (an earlier level / earlier in the chain)";
+    } else if (c == WT_RED || c == WT_INV || c == WT_INV0 || c == WT_BIT) {
+      if (!ref_ok(p->a[q])) return "operand not defined before its reader (an earlier level / earlier in the chain)";
+      if (c == WT_BIT && (p->b[q] < 0 || p->b[q] >= 384)) return "bit index outside 0 .. 383";
+    } else {
+      return c == WT_SUB ? "plain WT_SUB in a laid-out program" : "unknown instruction code";
+    }
+    defined[q] = 1;
+  }
+  for (size_t i = 0; i < p->n_vars; i++) {
+    const int32_t r = p->out_ref[i];
+    if (r < 0 ? (size_t)(-1 - (int64_t)r) >= p->n_consts : ((size_t)r >= n || !defined[r])) return "assignment entry reads an undefined position or constant";
+  }
+  return nullptr;
+}
+
+int zkhip_internal_witness_run_program(const zkhip_witness_program* p, const uint64_t* inputs, size_t batches, int witnesses_per_workgroup, unsigned segment_chunks,
+                                       uint64_t* z_out, uint32_t* flags_out) {
+  if (const char* why = witness_program_check(p)) return fail(ZKHIP_ERR_ARG, why);
+  if (witnesses_per_workgroup != 1 && witnesses_per_workgroup != 2 && witnesses_per_workgroup != 4) return fail(ZKHIP_ERR_ARG, "witnesses per workgroup: 1, 2 or 4");
+  if (segment_chunks < 1 || segment_chunks > (1u << 20)) return fail(ZKHIP_ERR_ARG, "segment: 1 .. 2^20 chunks");
+  if (batches > 256) return fail(ZKHIP_ERR_ARG, "at most 256 batches");
+  if (batches == 0) return ZKHIP_OK;                                      // validated, nothing to run: no device needed
+  if ((p->n_inputs && !inputs) || (p->n_vars && !z_out) || !flags_out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  BIND_CUR();
+  WitnessTape T;
+  T.code.assign(p->code, p->code + p->n_pos); T.a.assign(p->a, p->a + p->n_pos); T.b.assign(p->b, p->b + p->n_pos);
+  T.level_start.assign(p->level_start, p->level_start + p->n_levels + 1);
+  T.chain_start = p->chain_start;
+  T.out_ref.assign(p->out_ref, p->out_ref + p->n_vars);
+  T.consts.assign(p->consts, p->consts + p->n_consts * 6);
+  T.n_vars = p->n_vars; T.n_inputs = p->n_inputs;
+  struct Dev {            // released on every exit path
+    WitnessProgDev pd;
+    void *in = nullptr, *vals = nullptr, *z = nullptr, *flags = nullptr;
+    hipStream_t st = nullptr, st2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    ~Dev() {
+      witness_prog_free(&pd);
+      for (void* q : {in, vals, z, flags}) if (q) (void)hipFree(q);
+      if (st) (void)hipStreamDestroy(st);
+      if (st2) (void)hipStreamDestroy(st2);
+      if (ev_fork) (void)hipEventDestroy(ev_fork);
+      if (ev_join) (void)hipEventDestroy(ev_join);
+    }
+  } d;
+  int rc = witness_prog_upload(T, &d.pd, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  const size_t in_bytes = batches * p->n_inputs * 48, z_bytes = batches * p->n_vars * 48;
+  API_HIP(hipMalloc(&d.in, in_bytes + 64));
+  API_HIP(hipMalloc(&d.vals, batches * p->n_pos * witness_value_bytes + 64));
+  API_HIP(hipMalloc(&d.z, z_bytes + 64));
+  API_HIP(hipMalloc(&d.flags, batches * 4 + 64));
+  API_HIP(hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking));
+  API_HIP(hipStreamCreateWithFlags(&d.st2, hipStreamNonBlocking));
+  API_HIP(hipEventCreateWithFlags(&d.ev_fork, hipEventDisableTiming));
+  API_HIP(hipEventCreateWithFlags(&d.ev_join, hipEventDisableTiming));
+  if (in_bytes) API_HIP(hipMemcpyAsync(d.in, inputs, in_bytes, hipMemcpyHostToDevice, d.st));
+  API_HIP(hipMemsetAsync(d.flags, 0, batches * 4, d.st));
+  witness_launch(d.pd.prog, (const uint64_t*)d.in, (uint32_t*)d.vals, (uint64_t*)d.z, (uint32_t*)d.flags, (uint32_t)batches, (uint32_t)witnesses_per_workgroup,
+                 segment_chunks, d.st, d.st2, d.ev_fork, d.ev_join);
+  API_HIP(hipGetLastError());
+  if (z_bytes) API_HIP(hipMemcpyAsync(z_out, d.z, z_bytes, hipMemcpyDeviceToHost, d.st));
+  API_HIP(hipMemcpyAsync(flags_out, d.flags, batches * 4, hipMemcpyDeviceToHost, d.st));
+  API_HIP(hipStreamSynchronize(d.st));
+  API_HIP(hipStreamSynchronize(d.st2));
+  return ZKHIP_OK;
+}
+
+// Host only: the recorded program of the circuit (pointers into the aggregator's own copy, valid until it is freed)
+int zkhip_internal_witness_tape(zkhip_aggregator* a, zkhip_witness_program* out) {
+  if (!a || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  const WitnessTape* T = nullptr;
+  int rc = witness_tape_of(a, &T, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  out->code = T->code.data(); out->a = T->a.data(); out->b = T->b.data(); out->n_pos = T->code.size();
+  out->level_start = T->level_start.data(); out->n_levels = T->level_start.size() - 1;
+  out->chain_start = T->chain_start;
+  out->out_ref = T->out_ref.data(); out->n_vars = T->n_vars;
+  out->consts = T->consts.data(); out->n_consts = T->consts.size() / 6;
+  out->n_inputs = T->n_inputs;
   return ZKHIP_OK;
 }
 

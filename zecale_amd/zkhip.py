@@ -31,7 +31,7 @@ EXPORTS = [
     "zkhip_groth16_setup", "zkhip_groth16_setup_slice", "zkhip_keypair_crs_desc", "zkhip_keypair_vk", "zkhip_keypair_free", "zkhip_keypair_write", "zkhip_keypair_read",
     "zkhip_jac_to_affine", "zkhip_jac_add", "zkhip_to_canonical",
     "zkhip_last_accumulate_interval", "zkhip_crs_upload_ex", "zkhip_crs_upload_slice_ex", "zkhip_bases_precompute_ex", "zkhip_crs_table_kind", "zkhip_crs_finite_terms",
-    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_tail_selftest", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
+    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_witness_run_program", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
     "zkhip_msm_stream_new", "zkhip_msm_stream_submit", "zkhip_msm_stream_submit_host", "zkhip_msm_stream_collect", "zkhip_msm_stream_last_accumulate_ms",
     "zkhip_msm_stream_last_accumulate_interval", "zkhip_msm_stream_free", "zkhip_prover_new_slice", "zkhip_prover_prove_partial",
     "zkhip_dispatcher_new", "zkhip_dispatcher_size", "zkhip_dispatcher_submit", "zkhip_dispatcher_wait", "zkhip_dispatcher_stats", "zkhip_dispatcher_free",
@@ -73,6 +73,13 @@ class CrsDesc(ctypes.Structure):
     _fields_ = [("n_vars", ctypes.c_size_t), ("n_primary", ctypes.c_size_t), ("domain_size", ctypes.c_size_t)] + [
         (k, ctypes.c_void_p) for k in ("alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2",
                                        "a_query", "b_g2_query", "b_g1_query", "h_query", "l_query")]
+
+
+class WitnessProgram(ctypes.Structure):
+    """zkhip_witness_program: a laid-out program of the GPU witness interpreter (include/zkhip.h)."""
+    _fields_ = [("code", ctypes.c_void_p), ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("n_pos", ctypes.c_size_t), ("level_start", ctypes.c_void_p),
+                ("n_levels", ctypes.c_size_t), ("chain_start", ctypes.c_uint32), ("out_ref", ctypes.c_void_p), ("n_vars", ctypes.c_size_t),
+                ("consts", ctypes.c_void_p), ("n_consts", ctypes.c_size_t), ("n_inputs", ctypes.c_size_t)]
 
 
 _lib = None
@@ -722,6 +729,50 @@ class AggregatorCircuit:
         _check(load().zkhip_aggregator_witness_gpu(self.handle, _p(vk), _p(pr), _p(inp), _p(z)))
         return z
 
+    def witness_gpu_batched(self, batches, wpg=None, segment=None, app=None):
+        """batches: list of (nested_vk, nested_proofs, nested_inputs) -> (assignments u64 [n, n_vars, 6], degenerate bool [n], primary
+        inputs) from ONE launch sequence of the circuit's generic program (what zkhip_gpu_witness_run_batched runs), or of `app`'s own
+        program (zkhip_gpu_witness_run_batched_app: nested_vk is ignored and the assignments are masked), through the test hook
+        zkhip_internal_gpu_witness_run.  wpg (witnesses per workgroup: 1, 2, 4) and segment (chunks per
+        launch) reach witness_launch as given; None = the process-wide default.  A degenerate batch's assignment is unusable."""
+        lib = load()
+        n, m, l = len(batches), self.num_variables, self.num_primary_inputs()
+        c = lambda a: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        k = self.inputs_per_nested_proof
+        vks, prs, ins = [c(b[0]) for b in batches], [c(b[1]) for b in batches], [c(b[2]) for b in batches]
+        assert all(v.size == 60 + 12 * (k + 1) for v in vks) and all(x.size == 48 * self.num_proofs for x in prs) and all(x.size == 6 * k * self.num_proofs for x in ins)
+        gw = ctypes.c_void_p()
+        lib.zkhip_gpu_witness_new_batched.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        _check(lib.zkhip_gpu_witness_new_batched(self.handle, n, ctypes.byref(gw)))
+        dz = ctypes.c_void_p()
+        try:
+            _check(lib.zkhip_device_alloc(n * m * 48, ctypes.byref(dz)))
+            arr = lambda xs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in xs])
+            prim = np.zeros((n, l, 6), dtype=np.uint64)
+            deg = (ctypes.c_int * n)()
+            lib.zkhip_internal_gpu_witness_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                           c_u64p_t, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint]
+            _check(lib.zkhip_internal_gpu_witness_run(gw, app.handle if app is not None else None, n, None if app is not None else arr(vks), arr(prs), arr(ins), dz,
+                                                      _p(prim), deg, int(wpg or 0), int(segment or 0)))
+            z = np.zeros((n, m, 6), dtype=np.uint64)
+            lib.zkhip_device_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+            _check(lib.zkhip_device_copy_out(z.ctypes.data, dz, n * m * 48))
+            return z, np.array([bool(deg[i]) for i in range(n)]), prim
+        finally:
+            if dz:
+                lib.zkhip_device_free(dz)
+            lib.zkhip_gpu_witness_free(gw)
+
+    def witness_tape(self):
+        """Test hook, host only: the recorded program of the circuit as the GPU generator uploads it (a dict of numpy copies, the
+        layout of witness_run_program)."""
+        wp = WitnessProgram()
+        _check(load().zkhip_internal_witness_tape(self.handle, ctypes.byref(wp)))
+        cp = lambda ptr, n, dt: np.frombuffer(ctypes.string_at(ptr, n * np.dtype(dt).itemsize), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+        return dict(code=cp(wp.code, wp.n_pos, np.uint8), a=cp(wp.a, wp.n_pos, np.int32), b=cp(wp.b, wp.n_pos, np.int32),
+                    level_start=cp(wp.level_start, wp.n_levels + 1, np.uint32), chain_start=int(wp.chain_start), out_ref=cp(wp.out_ref, wp.n_vars, np.int32),
+                    consts=cp(wp.consts, wp.n_consts * 6, np.uint64).reshape(-1, 6), n_inputs=int(wp.n_inputs))
+
     def gpu_witness_stats(self):
         out = (ctypes.c_size_t * 6)()
         _check(load().zkhip_gpu_witness_stats(self.handle, out))
@@ -1215,6 +1266,31 @@ def field_selftest(field, limbs_in):
     lib.zkhip_internal_field_selftest.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     _check(lib.zkhip_internal_field_selftest(int(field), x.ctypes.data, x.shape[0], out.ctypes.data))
     return out
+
+
+def witness_run_program(prog, inputs, wpg=4, segment=2048):
+    """Test hook: a caller's program through the GPU witness generator's own upload, launch and kernels
+    (zkhip_internal_witness_run_program).  prog: dict with code u8 [n], a / b i32 [n], level_start u32 [levels + 1], chain_start,
+    out_ref i32 [n_vars], consts u64 [c, 6] (ABI form), n_inputs; inputs: u64 [batches, n_inputs, 6] (ABI form).  The library
+    validates the program first and raises ZkhipError (code -1) for one that breaks a structural rule; zero batches validates only
+    and needs no device.  Returns (assignments u64 [batches, n_vars, 6], flags u32 [batches])."""
+    arrs = dict(code=np.ascontiguousarray(prog["code"], dtype=np.uint8), a=np.ascontiguousarray(prog["a"], dtype=np.int32), b=np.ascontiguousarray(prog["b"], dtype=np.int32),
+                level_start=np.ascontiguousarray(prog["level_start"], dtype=np.uint32), out_ref=np.ascontiguousarray(prog["out_ref"], dtype=np.int32),
+                consts=np.ascontiguousarray(prog["consts"], dtype=np.uint64).reshape(-1, 6))
+    n = arrs["code"].size
+    assert arrs["a"].size == n and arrs["b"].size == n and arrs["level_start"].size >= 1
+    x = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(-1, int(prog["n_inputs"]), 6) if int(prog["n_inputs"]) else np.zeros((len(inputs), 0, 6), dtype=np.uint64)
+    ptr = lambda k: arrs[k].ctypes.data if arrs[k].size else None
+    wp = WitnessProgram(ptr("code"), ptr("a"), ptr("b"), n, arrs["level_start"].ctypes.data, arrs["level_start"].size - 1, int(prog["chain_start"]),
+                        ptr("out_ref"), arrs["out_ref"].size, ptr("consts"), arrs["consts"].shape[0], int(prog["n_inputs"]))
+    batches = x.shape[0]
+    z = np.zeros((batches, arrs["out_ref"].size, 6), dtype=np.uint64)
+    flags = np.zeros(max(batches, 1), dtype=np.uint32)
+    lib = load()
+    lib.zkhip_internal_witness_run_program.argtypes = [ctypes.POINTER(WitnessProgram), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    _check(lib.zkhip_internal_witness_run_program(ctypes.byref(wp), x.ctypes.data if x.size else None, batches, int(wpg), int(segment), z.ctypes.data if z.size else None,
+                                                  flags.ctypes.data))
+    return z, flags[:batches]
 
 
 def measure_fq_mul_rate():
