@@ -123,6 +123,9 @@ def main():
     extra_q += arr("EDW_C1", mont(ep["c1"]))                        # -3 t^2 / 4
     extra_q += arr("EDW_C2", mont(ep["c2"]))                        # 3 t / 2
     extra_q += arr("EDW_THREE", mont(3))
+    # psi's constants once more in the host's form: the window result of an Edwards launch is mapped back on the host (msm.hip edw_abi_to_jac)
+    extra_q += arr("EDW_C1_64", limbs(ep["c1"] * Rabi_q % Q, 12, 64), "uint64_t", 3, "0x%016xull")
+    extra_q += arr("EDW_C2_64", limbs(ep["c2"] * Rabi_q % Q, 12, 64), "uint64_t", 3, "0x%016xull")
     out += field("FqParams", Q, 27, 12, extra_q)
     Rabi_r = 1 << 384
     two_adic = pow(FR_GEN, (R - 1) >> 46, R)

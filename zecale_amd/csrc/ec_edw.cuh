@@ -3,10 +3,10 @@
 // G1 of BW6-761 (y^2 = x^3 - 1) has all three 2-torsion points rational, so it is 2-isogenous to a twisted Edwards curve, and that
 // curve scales to a = -1 (tools/gen_params.py: edwards_params).  chi maps G1 to it, psi maps back, psi(chi(P)) = 2P, both are group
 // homomorphisms.  So for points P_i of G1 (order r; not merely odd order: 2 [1/2 mod r] P = P needs r P = O)
-//     sum k_i P_i = psi( sum k_i chi(H_i) ),   H_i = [1/2 mod r] P_i,
-// and psi of a bucket is a bucket of the original sum.  The Edwards table holds chi of the HALVED table points (msm.hip k_half_bases,
-// msm_table_edw), so the digits are XYZZ's own; the accumulation adds chi-images, every slot is mapped back by psi right after it
-// (k_slots_edw_to_xyzz), and everything downstream - stitching, reduction, the host - stays XYZZ, bit for bit the same code.
+//     sum k_i P_i = psi( sum k_i chi(H_i) ),   H_i = [1/2 mod r] P_i.
+// The Edwards table holds chi of the HALVED table points (msm.hip k_half_bases, msm_table_edw), so the digits are XYZZ's own.  The
+// accumulation adds chi-images, the stitching and the bucket reduction add and double Edwards points (below), and psi is applied
+// ONCE, on the host, to the one point per window that leaves the device (msm.hip edw_abi_to_jac).
 //
 // The accumulator is in extended coordinates (X : Y : Z : T), x = X/Z, y = Y/Z, T = XY/Z; the identity is (0 : 1 : 1 : 0).
 // Table points are stored precomputed, (y - x, y + x, 2 d x y), so a mixed addition is SEVEN products and no squaring (Hisil, Wong,
@@ -84,43 +84,170 @@ __device__ __forceinline__ void edw_set_identity(uint32_t* xs, uint32_t* zs, uin
   ty = fp_one<FqParams>();
 }
 
-// psi, in place: a slot that holds an Edwards point (X : Y : Z : T) in its X | Y | ZZ | ZZZ words receives the XYZZ point psi(P).
-// With W = Z^2 - Y^2 and lambda = X W:  ZZ = lambda^2, ZZZ = lambda^3, X' = (X^2 + c1 Z^2) W^2, Y' = c2 Y Z^2 ZZ
-// (x = 1 + c1 Z^2 / X^2, y = c2 Y Z^2 / (X W): tools/gen_params.py edwards_params).  The identity (X = 0) gives ZZ = 0: XYZZ's
-// infinity.  Twelve products in a rolled loop (one multiplier body), four temporaries; every output [2].
-__device__ __forceinline__ void edw_to_xyzz_mem(const XyzzRef& r) {
-  Fq T0, T1, T2, T3;
+// ---- full additions and doublings: the stitching and the bucket reduction of an Edwards launch (msm.hip, point model EDW) ----
+// Every array the reduction touches holds extended points in the X | Y | ZZ | ZZZ words (X | Y | Z | T).  A slot or item whose Z
+// words are ZERO is EMPTY - nothing was ever accumulated there (k_slots_clear_zz, pt_set_inf) - and counts as the neutral element:
+// every operation below that reads memory tests for it first and copies the other operand or returns, because an all-zero "point"
+// would turn every sum it enters into zeros.  The true identity (0 : Y : Y : 0), which P + (-P) produces, is an ordinary point.
+// Unified addition add-2008-hwcd-3 (k = 2d), nine products:
+//     A = (Y1 - X1)(Y2 - X2), B = (Y1 + X1)(Y2 + X2), C = 2d T1 T2, D = 2 Z1 Z2, E = B - A, F = D - C, G = D + C, H = B + A,
+//     X3 = E F, Y3 = G H, T3 = E H, Z3 = F G
+// P + P and P + (-P) go through it (the trees do add equal points); like the mixed addition it is exact on the image of the
+// order-r subgroup (d is a square).  9 x 1,458 = 13,122 v_mad_u64_u32 instead of the 18,981 of add_lds_regy / add_mem_s.
+// Doubling dbl-2008-hwcd for a = -1, four squarings and four products:
+//     A = X^2, B = Y^2, C = 2 Z^2, E = (X + Y)^2 - A - B, G = B - A, F = G - C, H = -A - B, then the same four output products.
+// Bounds: stored coordinates are products [2]; sums and differences of two of them [4]; A, B, C [2]; D [4]; E, H [4]; F, G [6]
+// (doubling: E [6], G [4], F [8], H [4]).
+
+__device__ __forceinline__ bool edw_is_empty(const XyzzRef& r) { return fp_is_zero_2p(mem_ld(r, CZZ)); }
+
+// acc += B: the accumulator on the CU as in edw_madd_lds_regy (X packed in LDS `xs`, Z in `zs`, T in `ts`, Y in registers), B a
+// point in memory (not empty) - the counterpart of add_lds_regy.  One multiplier body in a rolled loop of nine steps.
+__device__ __forceinline__ void edw_add_lds_regy(uint32_t* xs, uint32_t* zs, uint32_t* ts, Fq& ty, const XyzzRef& B) {
+  Fq T0, T1, T2, T3;      // (not initialised: every one is written by the step before the first that reads it)
 #pragma unroll 1
-  for (int step = 0; step < 12; step++) {
+  for (int step = 0; step < 9; step++) {
     Fq a, b;
     switch (step) {
-      case 0: a = mem_ld(r, CX); b = a; break;                                   // X^2
-      case 1: a = mem_ld(r, CZZ); b = a; break;                                  // Z^2
-      case 2: a = mem_ld(r, CY); b = a; break;                                   // Y^2
-      case 3: a = mem_ld(r, CX); b = T2; break;                                  // lambda = X W
-      case 4: a = T2; b = T2; break;                                             // W^2
-      case 5: a = T1; b = fp_const<FqParams>(FqParams::EDW_C1); break;           // c1 Z^2
-      case 6: a = T0; b = T2; break;                                             // X' = (X^2 + c1 Z^2) W^2
-      case 7: a = T3; b = T3; break;                                             // ZZ = lambda^2
-      case 8: a = T0; b = T3; break;                                             // ZZZ = ZZ lambda
-      case 9: a = mem_ld(r, CY); b = T1; break;                                  // Y Z^2
-      case 10: a = T3; b = T0; break;                                            // Y Z^2 ZZ
-      default: a = T3; b = fp_const<FqParams>(FqParams::EDW_C2); break;         // Y' = c2 Y Z^2 ZZ
+      case 0: a = fp_sub<FqParams, 2>(ty, lds_ld_packed(xs)); b = fp_sub<FqParams, 2>(mem_ld(B, CY), mem_ld(B, CX)); break;   // A
+      case 1: a = fp_add(ty, lds_ld_packed(xs)); b = fp_add(mem_ld(B, CY), mem_ld(B, CX)); break;                               // B
+      case 2: a = lds_ld(ts); b = mem_ld(B, CZZZ); break;                                                 // T1 T2
+      case 3: a = T2; b = fp_const<FqParams>(FqParams::EDW_D2); break;                                    // C = 2d T1 T2
+      case 4: a = lds_ld(zs); b = mem_ld(B, CZZ); break;                                                  // Z1 Z2
+      case 5: a = T1; b = T2; break;                                                                      // X3 = E F
+      case 6: a = T1; b = T0; break;                                                                      // T3 = E H
+      case 7: a = T3; b = T0; break;                                                                      // Y3 = G H
+      default: a = T2; b = T3; break;                                                                     // Z3 = F G
     }
-    Fq v = fp_mul(a, b);
+    Fq r = fp_mul(a, b);
     switch (step) {
-      case 0: T0 = v; break;
-      case 1: T1 = v; break;
-      case 2: T2 = fp_sub<FqParams, 2>(T1, v); break;                            // W [4]
-      case 3: T3 = v; break;
-      case 4: T2 = v; break;
-      case 5: T0 = fp_add(T0, v); break;                                         // X^2 + c1 Z^2 [4]
-      case 6: mem_st(r, CX, v); break;                                           // (X is not read after step 3)
-      case 7: T0 = v; mem_st(r, CZZ, v); break;                                  // (Z: not read after step 1)
-      case 8: mem_st(r, CZZZ, v); break;                                         // (T is never read)
-      case 9: T3 = v; break;
-      case 10: T3 = v; break;
-      default: mem_st(r, CY, v); break;
+      case 0: T0 = r; break;                                                                              // A
+      case 1: T1 = fp_sub<FqParams, 2>(r, T0); T0 = fp_add(r, T0); break;                                 // E = B - A, H = B + A [4]
+      case 2: T2 = r; break;
+      case 3: T2 = r; break;                                                                              // C
+      case 4: {
+        const Fq D = fp_dbl(r);                                                                           // [4]
+        T3 = fp_add(D, T2);                                                                               // G = D + C [6]
+        T2 = fp_sub<FqParams, 2>(D, T2);                                                                  // F = D - C [6]
+        break;
+      }
+      case 5: lds_st_packed(xs, r); break;
+      case 6: lds_st(ts, r); break;
+      case 7: ty = r; break;
+      default: lds_st(zs, r); break;
+    }
+  }
+}
+
+// A (memory) += B (memory), one lane; either may be empty; A is updated in place, B is not written - the counterpart of add_mem_s.
+__device__ __forceinline__ void edw_add_mem(const XyzzRef& A, const XyzzRef& B) {
+  if (edw_is_empty(B)) return;
+  if (edw_is_empty(A)) { mem_copy(A, B); return; }
+  Fq T0, T1, T2, T3;
+#pragma unroll 1
+  for (int step = 0; step < 9; step++) {
+    Fq a, b;
+    switch (step) {
+      case 0: a = fp_sub<FqParams, 2>(mem_ld(A, CY), mem_ld(A, CX)); b = fp_sub<FqParams, 2>(mem_ld(B, CY), mem_ld(B, CX)); break;   // A
+      case 1: a = fp_add(mem_ld(A, CY), mem_ld(A, CX)); b = fp_add(mem_ld(B, CY), mem_ld(B, CX)); break;                               // B
+      case 2: a = mem_ld(A, CZZZ); b = mem_ld(B, CZZZ); break;                                            // T1 T2
+      case 3: a = T2; b = fp_const<FqParams>(FqParams::EDW_D2); break;                                    // C
+      case 4: a = mem_ld(A, CZZ); b = mem_ld(B, CZZ); break;                                              // Z1 Z2
+      case 5: a = T1; b = T2; break;                                                                      // X3 = E F
+      case 6: a = T1; b = T0; break;                                                                      // T3 = E H
+      case 7: a = T3; b = T0; break;                                                                      // Y3 = G H
+      default: a = T2; b = T3; break;                                                                     // Z3 = F G
+    }
+    Fq r = fp_mul(a, b);
+    switch (step) {
+      case 0: T0 = r; break;
+      case 1: T1 = fp_sub<FqParams, 2>(r, T0); T0 = fp_add(r, T0); break;                                 // E, H [4]
+      case 2: T2 = r; break;
+      case 3: T2 = r; break;
+      case 4: {
+        const Fq D = fp_dbl(r);
+        T3 = fp_add(D, T2);                                                                               // G [6]
+        T2 = fp_sub<FqParams, 2>(D, T2);                                                                  // F [6]
+        break;
+      }
+      case 5: mem_st(A, CX, r); break;                                                                    // (A is not read after step 4)
+      case 6: mem_st(A, CZZZ, r); break;
+      case 7: mem_st(A, CY, r); break;
+      default: mem_st(A, CZZ, r); break;
+    }
+  }
+}
+
+// The last round of a quad addition or doubling: E, F, G, H are known to all four lanes; lane q computes coordinate q:
+// q0 X3 = E F, q1 Y3 = G H, q2 Z3 = F G, q3 T3 = E H
+#define ZK_EDW_QUAD_OUT_A(q, E, F, G, H) (((q) == 0 || (q) == 3) ? (E) : ((q) == 1) ? (G) : (F))
+#define ZK_EDW_QUAD_OUT_B(q, E, F, G, H) (((q) == 0) ? (F) : ((q) == 2) ? (G) : (H))
+
+// A += B by the four lanes of a quad (all four pass the same A and B; either may be empty) - the counterpart of add_mem_quad, a
+// chain of three products instead of four.  One multiplier body in a rolled loop.
+//   round 1: q0 A = (Y1 - X1)(Y2 - X2), q1 B = (Y1 + X1)(Y2 + X2), q2 T1 T2, q3 Z1 Z2
+//   round 2: q2 C = 2d (T1 T2)                                      (the other lanes' products are not used)
+//   round 3: the four output products, lane q stores coordinate q
+__device__ __forceinline__ void edw_add_mem_quad(const XyzzRef& A, const XyzzRef& B, uint32_t q) {
+  if (edw_is_empty(B)) return;
+  if (edw_is_empty(A)) { mem_st_lane(A, q, mem_ld_lane(B, q)); return; }   // lane q copies coordinate q
+  Fq E = fp_zero<FqParams>(), F = E, G = E, H = E, keep = E;
+#pragma unroll 1
+  for (int round = 0; round < 3; round++) {
+    Fq a, b;
+    if (round == 0) {
+      const uint32_t c = (q < 2) ? CX : (q == 2) ? CZZZ : CZZ;         // q0, q1: X (Y joins below); q2: T; q3: Z
+      const Fq u1 = mem_ld_lane(A, c), u2 = mem_ld_lane(B, c);
+      const Fq y1 = mem_ld(A, CY), y2 = mem_ld(B, CY);
+      a = (q == 0) ? fp_sub<FqParams, 2>(y1, u1) : (q == 1) ? fp_add(y1, u1) : u1;
+      b = (q == 0) ? fp_sub<FqParams, 2>(y2, u2) : (q == 1) ? fp_add(y2, u2) : u2;
+    } else if (round == 1) {
+      a = keep; b = fp_const<FqParams>(FqParams::EDW_D2);
+    } else {
+      a = ZK_EDW_QUAD_OUT_A(q, E, F, G, H); b = ZK_EDW_QUAD_OUT_B(q, E, F, G, H);
+    }
+    const Fq r = fp_mul(a, b);
+    if (round == 0) {
+      const Fq pa = quad_bcast<0>(r), pb = quad_bcast<1>(r);
+      E = fp_sub<FqParams, 2>(pb, pa);                                  // [4]
+      H = fp_add(pb, pa);                                               // [4]
+      G = fp_dbl(quad_bcast<3>(r));                                     // D = 2 Z1 Z2 [4], parked in G
+      keep = r;                                                         // q2: T1 T2
+    } else if (round == 1) {
+      const Fq C = quad_bcast<2>(r);
+      F = fp_sub<FqParams, 2>(G, C);                                    // D - C [6]
+      G = fp_add(G, C);                                                 // D + C [6]
+    } else {
+      mem_st_lane(A, q, r);
+    }
+  }
+}
+
+// A = 2 A by a quad (A may be empty) - the counterpart of dbl_mem_quad, a chain of two products instead of three.
+//   round 1: q0 X^2, q1 Y^2, q2 Z^2, q3 (X + Y)^2;   round 2: the four output products
+__device__ __forceinline__ void edw_dbl_mem_quad(const XyzzRef& A, uint32_t q) {
+  if (edw_is_empty(A)) return;
+  Fq E = fp_zero<FqParams>(), F = E, G = E, H = E;
+#pragma unroll 1
+  for (int round = 0; round < 2; round++) {
+    Fq a, b;
+    if (round == 0) {
+      a = mem_ld_lane(A, q == 3 ? (uint32_t)CX : q);
+      if (q == 3) a = fp_add(a, mem_ld(A, CY));                         // X + Y [4]
+      b = a;
+    } else {
+      a = ZK_EDW_QUAD_OUT_A(q, E, F, G, H); b = ZK_EDW_QUAD_OUT_B(q, E, F, G, H);
+    }
+    const Fq r = fp_mul(a, b);
+    if (round == 0) {
+      const Fq xx = quad_bcast<0>(r), yy = quad_bcast<1>(r), zz = quad_bcast<2>(r), xy = quad_bcast<3>(r);
+      H = fp_add(xx, yy);                                               // A + B [4]
+      E = fp_sub<FqParams, 4>(xy, H);                                   // (X + Y)^2 - A - B [6]
+      G = fp_sub<FqParams, 2>(yy, xx);                                  // B - A [4]
+      F = fp_sub<FqParams, 4>(G, fp_dbl(zz));                           // G - C [8]
+      H = fp_sub<FqParams, 4>(fp_zero<FqParams>(), H);                  // -A - B [4]
+    } else {
+      mem_st_lane(A, q, r);
     }
   }
 }

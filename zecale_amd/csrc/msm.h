@@ -80,6 +80,7 @@ struct MsmCtx {
   int last_tight;
   bool pending;       // an MSM has been enqueued by msm_launch and not yet collected by msm_finish
   size_t pending_n;
+  bool win_edw;       // the pending launch leaves Edwards points (X : Y : Z : T) in win_host: msm_finish applies psi (msm.hip edw_abi_to_jac)
   char errbuf[256];
 };
 

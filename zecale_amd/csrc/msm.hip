@@ -458,7 +458,7 @@ __device__ __forceinline__ uint32_t slice_weight(uint32_t G, uint32_t T, uint32_
 // entries == nullptr: the sorted list IS the dense point array bp.p[0] (the output of the batched-affine levels, k_affine_level):
 // entry k is point k, never negated; a point may be the level encoding of infinity (skipped).
 // EDW: bp.p[0] is a table of precomputed Edwards points (ec_edw.cuh) and the slots receive Edwards points (X | Y | Z | T in the
-// X | Y | ZZ | ZZZ words; k_slots_edw_to_xyzz maps them back): every run starts at the identity, so every entry is one addition.
+// X | Y | ZZ | ZZZ words; the stitching and the reduction go on in that model): every run starts at the identity, so every entry is one addition.
 // Single MSMs only (NJ = 1), never dense.  Two kernels share this body: k_accumulate<NJ> (XYZZ) and k_accumulate_edw.
 #define ZK_ACC_PARAMS                                                                                                                   \
   BasePtrs bp, int bshift, const uint32_t* __restrict__ entries, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,   \
@@ -652,16 +652,6 @@ __global__ void __launch_bounds__(256, 2) k_accumulate(ZK_ACC_PARAMS) {
 __global__ void __launch_bounds__(256, 2) k_accumulate_edw(ZK_ACC_PARAMS) {
   accumulate_impl<1, true>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
                            dbg_times, prio_mode, prio_board, prio_tag);
-}
-
-// psi for the slots the Edwards accumulation wrote: [0, n) of the slot array, in place (ec_edw.cuh edw_to_xyzz_mem).  A slot whose
-// Z words are zero was not written (k_slots_clear_zz): it stays XYZZ's infinity.  One lane per slot: a throughput-bound launch.
-__global__ void __launch_bounds__(256, 2) k_slots_edw_to_xyzz(uint32_t* __restrict__ slots, uint32_t stride, uint32_t n) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const XyzzRef r = make_slot_ref(slots, stride, i);
-  if (mem_is_inf(r)) return;
-  edw_to_xyzz_mem(r);
 }
 
 // chi for every entry of a window table (levels x n points): the precomputed Edwards table.  Entries at infinity hold zeros; *bad
@@ -884,11 +874,21 @@ struct AddScratch { uint32_t* zz; uint32_t* zzz; };
 #define ADD_SCRATCH_DECL(QUADFLAG)                                                                   \
   __shared__ uint32_t s_add_zz_[(QUADFLAG) ? 1 : 27 * ZK_LDS_STRIDE], s_add_zzz_[(QUADFLAG) ? 1 : 27 * ZK_LDS_STRIDE]; \
   const AddScratch sc{s_add_zz_ + ((QUADFLAG) ? 0 : threadIdx.x), s_add_zzz_ + ((QUADFLAG) ? 0 : threadIdx.x)}
-template <bool QUAD> __device__ __forceinline__ void pt_add(const XyzzRef& a, const XyzzRef& b, uint32_t q, const AddScratch& sc) {
-  if constexpr (QUAD) add_mem_quad(a, b, q); else add_mem_s(a, b, sc.zz, sc.zzz);
+// EDW: the point model of the launch.  false: XYZZ points of G1; true: extended points of the 2-isogenous Edwards curve in the same
+// four words (ec_edw.cuh) - what k_accumulate_edw leaves in the slots.  Copies, "nothing here" (all-zero ZZ / Z words) and the
+// array layouts are the same in both models; only the additions and doublings differ.  Every kernel below exists once per model:
+// k_name (XYZZ) and k_name_edw share one body.
+template <bool QUAD, bool EDW = false> __device__ __forceinline__ void pt_add(const XyzzRef& a, const XyzzRef& b, uint32_t q, const AddScratch& sc) {
+  if constexpr (EDW) { if constexpr (QUAD) edw_add_mem_quad(a, b, q); else edw_add_mem(a, b); }
+  else if constexpr (QUAD) add_mem_quad(a, b, q); else add_mem_s(a, b, sc.zz, sc.zzz);
 }
-template <bool QUAD> __device__ __forceinline__ void pt_dbl(const XyzzRef& a, uint32_t q) {
-  if constexpr (QUAD) dbl_mem_quad(a, q); else dbl_mem(a);
+template <bool EDW> __device__ __forceinline__ void pt_dbl_quad(const XyzzRef& a, uint32_t q) {
+  if constexpr (EDW) edw_dbl_mem_quad(a, q); else dbl_mem_quad(a, q);
+}
+// full addition into an accumulator on the CU (X packed, ZZ / Z, ZZZ / T in LDS, Y in registers); true: the sum is XYZZ's infinity
+template <bool EDW> __device__ __forceinline__ bool pt_add_lds(const XyzzRef& spill, uint32_t* xs, uint32_t* zz, uint32_t* zzz, Fq& ty, const XyzzRef& B) {
+  if constexpr (EDW) { edw_add_lds_regy(xs, zz, zzz, ty, B); return false; }
+  else return add_lds_regy(spill, xs, zz, zzz, ty, B) && fp_is_zero_2p(lds_ld(zz));     // same-x path may have cancelled to infinity
 }
 template <bool QUAD> __device__ __forceinline__ void pt_copy(const XyzzRef& dst, const XyzzRef& src, uint32_t q) {
   if constexpr (QUAD) mem_st_lane(dst, q, mem_ld_lane(src, q)); else mem_copy(dst, src);
@@ -906,18 +906,19 @@ template <bool QUAD> __device__ __forceinline__ void pt_set_inf(const XyzzRef& d
 //     each, its 64 quads fold the pieces pairwise (F[t] += F[t+d] for t - first divisible by 2d) in log2(pieces) rounds d = 1, 2,
 //     4, ..., a barrier between rounds (the pieces live in global memory, coherent inside a CU).
 // Both kinds touch different buckets, so they run side by side: a proof on its own waits for the longer of the two, not their sum.
-template <bool QUAD>
-__global__ void __launch_bounds__(256, 2) k_fixup_fold(const uint32_t* __restrict__ cnt /* [2]: short, long */, const uint2* __restrict__ list_short,
-                                                        const uint2* __restrict__ list_long, uint32_t short_blocks, uint32_t nb,
-                                                        uint32_t* __restrict__ slots, uint32_t stride) {
-  ADD_SCRATCH_DECL(QUAD);
+#define ZK_FOLD_PARAMS                                                                                                             \
+  const uint32_t* __restrict__ cnt /* [2]: short, long */, const uint2* __restrict__ list_short, const uint2* __restrict__ list_long, \
+      uint32_t short_blocks, uint32_t nb, uint32_t* __restrict__ slots, uint32_t stride
+template <bool QUAD, bool EDW>
+__device__ __forceinline__ void fixup_fold_impl(ZK_FOLD_PARAMS) {
+  ADD_SCRATCH_DECL(QUAD || EDW);
   const uint32_t q = threadIdx.x & 3u;
   if (blockIdx.x < short_blocks) {
     const uint32_t n = cnt[0], per = QUAD ? 64u : 256u;
     for (uint32_t i = blockIdx.x * per + (QUAD ? threadIdx.x >> 2 : threadIdx.x); i < n; i += short_blocks * per) {
       const uint2 w = list_short[i];                    // first F slot, number of F pieces
       const XyzzRef dst = make_slot_ref(slots, stride, nb + w.x);
-      for (uint32_t j = 1; j < w.y; j++) pt_add<QUAD>(dst, make_slot_ref(slots, stride, nb + w.x + j), q, sc);
+      for (uint32_t j = 1; j < w.y; j++) pt_add<QUAD, EDW>(dst, make_slot_ref(slots, stride, nb + w.x + j), q, sc);
     }
     return;
   }
@@ -927,17 +928,25 @@ __global__ void __launch_bounds__(256, 2) k_fixup_fold(const uint32_t* __restric
 #pragma unroll 1
     for (uint32_t d = 1; d <= w.y - w.x; d <<= 1) {
       for (uint64_t t = (uint64_t)w.x + (uint64_t)quad * 2 * d; t + d <= w.y; t += (uint64_t)64 * 2 * d)
-        add_mem_quad(make_slot_ref(slots, stride, nb + (uint32_t)t), make_slot_ref(slots, stride, nb + (uint32_t)t + d), q);
+        pt_add<true, EDW>(make_slot_ref(slots, stride, nb + (uint32_t)t), make_slot_ref(slots, stride, nb + (uint32_t)t + d), q, sc);
       __threadfence_block();
       __syncthreads();
     }
   }
 }
+template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_fixup_fold(ZK_FOLD_PARAMS) {
+  fixup_fold_impl<QUAD, false>(cnt, list_short, list_long, short_blocks, nb, slots, stride);
+}
+template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_fixup_fold_edw(ZK_FOLD_PARAMS) {
+  fixup_fold_impl<QUAD, true>(cnt, list_short, list_long, short_blocks, nb, slots, stride);
+}
 
 // final stitch: the slice in which a cut bucket STARTS owns it: bucket = L[t0] + F[t0+1] (folded).
-__global__ void __launch_bounds__(256, 2) k_fixup(const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ goff,
-                                                   uint32_t nb, uint32_t S_host, int tight, uint32_t T, uint32_t* __restrict__ slots, uint32_t stride,
-                                                   uint32_t wf) {
+#define ZK_FIXUP_PARAMS                                                                                                             \
+  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ goff, uint32_t nb, uint32_t S_host, \
+      int tight, uint32_t T, uint32_t* __restrict__ slots, uint32_t stride, uint32_t wf
+template <bool EDW>
+__device__ __forceinline__ void fixup_impl(ZK_FIXUP_PARAMS) {
   // the L piece goes to the CU (X, ZZ, ZZZ in LDS, Y in registers, as in k_accumulate / k_sum_lds), the F piece is added to it
   // there and the sum is stored once: ten coordinate loads and four stores per cut bucket (a copy into the bucket's slot followed by
   // an addition in memory - rounds 1-3 - moved fourteen and eight)
@@ -967,17 +976,19 @@ __global__ void __launch_bounds__(256, 2) k_fixup(const uint32_t* __restrict__ o
   Fq ty = mem_ld(pl, CY);
   lds_st(zz, mem_ld(pl, CZZ));
   lds_st(zzz, mem_ld(pl, CZZZ));
-  if (add_lds_regy(dst, xs, zz, zzz, ty, pf) && fp_is_zero_2p(lds_ld(zz))) { mem_set_inf(dst); return; }   // same-x path: L = -F
+  if (pt_add_lds<EDW>(dst, xs, zz, zzz, ty, pf)) { mem_set_inf(dst); return; }   // same-x path: L = -F
   mem_st(dst, CX, lds_ld_packed(xs)); mem_st(dst, CY, ty); mem_st(dst, CZZ, lds_ld(zz)); mem_st(dst, CZZZ, lds_ld(zzz));
 }
+__global__ void __launch_bounds__(256, 2) k_fixup(ZK_FIXUP_PARAMS) { fixup_impl<false>(offsets, counts, goff, nb, S_host, tight, T, slots, stride, wf); }
+__global__ void __launch_bounds__(256, 2) k_fixup_edw(ZK_FIXUP_PARAMS) { fixup_impl<true>(offsets, counts, goff, nb, S_host, tight, T, slots, stride, wf); }
 
 // Segment pass of the bucket reduction.  in: n_in items (XYZZ limb-major, stride n_in), grouped in
 // runs of L.  For segment t: S_t = sum_u item[tL+u],  R_t = sum_u (u + o) item[tL+u]   (o in {0,1}).
 // The running sums live in the output arrays themselves (memory-resident accumulators).
-template <bool QUAD>
-__global__ void __launch_bounds__(256, 2) k_seg(uint32_t* __restrict__ in, size_t n_in, uint32_t in_stride, int L, int o,
-                                                 uint32_t* __restrict__ outS, uint32_t* __restrict__ outR) {
-  ADD_SCRATCH_DECL(QUAD);
+#define ZK_SEG_PARAMS uint32_t* __restrict__ in, size_t n_in, uint32_t in_stride, int L, int o, uint32_t* __restrict__ outS, uint32_t* __restrict__ outR
+template <bool QUAD, bool EDW>
+__device__ __forceinline__ void seg_impl(ZK_SEG_PARAMS) {
+  ADD_SCRATCH_DECL(QUAD || EDW);
   size_t n_out = n_in / L;
   size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x, t = QUAD ? gt >> 2 : gt;    // one lane / quad per segment
   const uint32_t q = (uint32_t)(gt & 3);
@@ -987,18 +998,22 @@ __global__ void __launch_bounds__(256, 2) k_seg(uint32_t* __restrict__ in, size_
   pt_set_inf<QUAD>(acc, q);
   for (int u = L - 1; u >= 0; u--) {
     XyzzRef it = make_ref(in, in_stride, (uint32_t)(t * L + u));
-    pt_add<QUAD>(run, it, q, sc);
-    if (u + o > 0) pt_add<QUAD>(acc, run, q, sc);
+    pt_add<QUAD, EDW>(run, it, q, sc);
+    if (u + o > 0) pt_add<QUAD, EDW>(acc, run, q, sc);
   }
 }
+template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_seg(ZK_SEG_PARAMS) { seg_impl<QUAD, false>(in, n_in, in_stride, L, o, outS, outR); }
+template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_seg_edw(ZK_SEG_PARAMS) { seg_impl<QUAD, true>(in, n_in, in_stride, L, o, outS, outR); }
 
 // out[t] = sum_u in[i(t) + u * row_len],  i(t) = (t / row_len) * (L * row_len) + (t % row_len).
 // row_len = 1: sums of L consecutive items (row sums);  row_len = R: for items laid out [g][h][R] it sums L
 // consecutive h for every (g, h / L, lo) (column sums).  in: n_in items with row stride in_stride words.
-template <bool QUAD>
-__global__ void __launch_bounds__(256, 2) k_sum(uint32_t* __restrict__ in, size_t n_in, uint32_t in_stride, int L, uint32_t row_len,
-                                                 uint32_t* __restrict__ out, int in_slots /* `in` is the slot array (ec_mem.cuh) */) {
-  ADD_SCRATCH_DECL(QUAD);
+#define ZK_SUM_PARAMS                                                                                       \
+  uint32_t* __restrict__ in, size_t n_in, uint32_t in_stride, int L, uint32_t row_len, uint32_t* __restrict__ out, \
+      int in_slots /* `in` is the slot array (ec_mem.cuh) */
+template <bool QUAD, bool EDW>
+__device__ __forceinline__ void sum_impl(ZK_SUM_PARAMS) {
+  ADD_SCRATCH_DECL(QUAD || EDW);
   size_t n_out = n_in / L;
   size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x, t = QUAD ? gt >> 2 : gt;    // one lane / quad per output
   const uint32_t q = (uint32_t)(gt & 3);
@@ -1006,13 +1021,15 @@ __global__ void __launch_bounds__(256, 2) k_sum(uint32_t* __restrict__ in, size_
   const size_t i0 = (t / row_len) * ((size_t)L * row_len) + (t % row_len);
   XyzzRef acc = make_ref(out, (uint32_t)n_out, (uint32_t)t);
   pt_copy<QUAD>(acc, make_in_ref(in, in_stride, (uint32_t)i0, in_slots), q);
-  for (int u = 1; u < L; u++) pt_add<QUAD>(acc, make_in_ref(in, in_stride, (uint32_t)(i0 + (size_t)u * row_len), in_slots), q, sc);
+  for (int u = 1; u < L; u++) pt_add<QUAD, EDW>(acc, make_in_ref(in, in_stride, (uint32_t)(i0 + (size_t)u * row_len), in_slots), q, sc);
 }
+template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_sum(ZK_SUM_PARAMS) { sum_impl<QUAD, false>(in, n_in, in_stride, L, row_len, out, in_slots); }
+template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_sum_edw(ZK_SUM_PARAMS) { sum_impl<QUAD, true>(in, n_in, in_stride, L, row_len, out, in_slots); }
 
 // k_sum with one lane per output and the running sum held on the CU (add_lds_regy): the throughput-bound plain sums of the bucket
 // reduction.  Same indexing as k_sum.
-__global__ void __launch_bounds__(256, 2) k_sum_lds(uint32_t* __restrict__ in, size_t n_in, uint32_t in_stride, int L, uint32_t row_len,
-                                                     uint32_t* __restrict__ out, int in_slots /* `in` is the slot array (ec_mem.cuh) */) {
+template <bool EDW>
+__device__ __forceinline__ void sum_lds_impl(ZK_SUM_PARAMS) {
   __shared__ uint32_t lds_zz[27 * ZK_LDS_STRIDE], lds_zzz[27 * ZK_LDS_STRIDE], lds_x[24 * ZK_LDS_STRIDE];
   const size_t n_out = n_in / L;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1035,11 +1052,13 @@ __global__ void __launch_bounds__(256, 2) k_sum_lds(uint32_t* __restrict__ in, s
       inf = false;
       continue;
     }
-    if (add_lds_regy(dst, xs, zz, zzz, ty, B)) inf = fp_is_zero_2p(lds_ld(zz));
+    inf = pt_add_lds<EDW>(dst, xs, zz, zzz, ty, B);
   }
   if (inf) { mem_set_inf(dst); return; }
   mem_st(dst, CX, lds_ld_packed(xs)); mem_st(dst, CY, ty); mem_st(dst, CZZ, lds_ld(zz)); mem_st(dst, CZZZ, lds_ld(zzz));
 }
+__global__ void __launch_bounds__(256, 2) k_sum_lds(ZK_SUM_PARAMS) { sum_lds_impl<false>(in, n_in, in_stride, L, row_len, out, in_slots); }
+__global__ void __launch_bounds__(256, 2) k_sum_lds_edw(ZK_SUM_PARAMS) { sum_lds_impl<true>(in, n_in, in_stride, L, row_len, out, in_slots); }
 
 // Two-level split of the bucket index j = hi * R + lo (R = 2^lo_bits, H = 2^hi_bits rows):
 //   sum_j (j+1) B_j = R * sum_hi hi * Row[hi] + sum_lo (lo+1) * Col[lo].
@@ -1065,35 +1084,43 @@ __global__ void __launch_bounds__(256, 2) k_place_hilo(uint32_t* __restrict__ ro
 // R_all: `levels` arrays of W XYZZ points each, limb-major with stride W, consecutive (108*W words apart);
 // `work`: scratch for W accumulators.
 struct LevelShifts { uint8_t log_l[32]; };
-__global__ void __launch_bounds__(64, 2) k_window_combine(uint32_t* __restrict__ R_all, int levels, int G, LevelShifts ls,
-                                                           uint32_t* __restrict__ work /* G accumulators, result left here */) {
+#define ZK_WCOMB_PARAMS uint32_t* __restrict__ R_all, int levels, int G, LevelShifts ls, uint32_t* __restrict__ work /* G accumulators, result left here */
+template <bool EDW>
+__device__ __forceinline__ void window_combine_impl(uint32_t* __restrict__ R_all, int levels, int G, const LevelShifts& ls, uint32_t* __restrict__ work) {
   int gt = blockIdx.x * blockDim.x + threadIdx.x, w = gt >> 2;   // one quad per group
   const uint32_t q = (uint32_t)(gt & 3);
   if (w >= G) return;
   XyzzRef acc = make_ref(work, (uint32_t)G, (uint32_t)w);
   mem_st_lane(acc, q, mem_ld_lane(make_ref(R_all + (size_t)(levels - 1) * 108 * G, (uint32_t)G, (uint32_t)w), q));
   for (int k = levels - 2; k >= 0; k--) {
-    for (int d = 0; d < ls.log_l[k]; d++) dbl_mem_quad(acc, q);
-    add_mem_quad(acc, make_ref(R_all + (size_t)k * 108 * G, (uint32_t)G, (uint32_t)w), q);
+    for (int d = 0; d < ls.log_l[k]; d++) pt_dbl_quad<EDW>(acc, q);
+    pt_add<true, EDW>(acc, make_ref(R_all + (size_t)k * 108 * G, (uint32_t)G, (uint32_t)w), q, AddScratch{nullptr, nullptr});
   }
 }
+__global__ void __launch_bounds__(64, 2) k_window_combine(ZK_WCOMB_PARAMS) { window_combine_impl<false>(R_all, levels, G, ls, work); }
+__global__ void __launch_bounds__(64, 2) k_window_combine_edw(ZK_WCOMB_PARAMS) { window_combine_impl<true>(R_all, levels, G, ls, work); }
 
 // per window: R * (hi part) + (lo part), converted to ABI limbs
 // total (optional): the plain sums of the 2W groups (the last S of the k_seg chain); the lo group's is sum_b S_b of the window and
 // goes out behind the W weighted sums (the NAF finish needs it)
-__global__ void __launch_bounds__(64, 2) k_hilo_combine(uint32_t* __restrict__ work /* 2W */, int W, int lo_bits,
-                                                         uint64_t* __restrict__ out_abi /* W x 4 x 12 u64 (+ W more with total) */,
-                                                         uint32_t* __restrict__ total /* 2W or null */) {
+#define ZK_HCOMB_PARAMS                                                                                                \
+  uint32_t* __restrict__ work /* 2W */, int W, int lo_bits, uint64_t* __restrict__ out_abi /* W x 4 x 12 u64 (+ W more with total) */, \
+      uint32_t* __restrict__ total /* 2W or null */
+template <bool EDW>
+__device__ __forceinline__ void hilo_combine_impl(ZK_HCOMB_PARAMS) {
   int gt = blockIdx.x * blockDim.x + threadIdx.x, w = gt >> 2;
   const uint32_t q = (uint32_t)(gt & 3);
   if (w >= W) return;
   XyzzRef hi = make_ref(work, (uint32_t)(2 * W), (uint32_t)w), lo = make_ref(work, (uint32_t)(2 * W), (uint32_t)(W + w));
-  for (int d = 0; d < lo_bits; d++) dbl_mem_quad(hi, q);
-  add_mem_quad(hi, lo, q);
+  for (int d = 0; d < lo_bits; d++) pt_dbl_quad<EDW>(hi, q);
+  pt_add<true, EDW>(hi, lo, q, AddScratch{nullptr, nullptr});
   uint64_t* o = out_abi + (size_t)w * 48;
   fp_to_abi<FqParams>(mem_ld_lane(hi, q), o + 12 * q);            // lane q converts coordinate q
   if (total) fp_to_abi<FqParams>(mem_ld_lane(make_ref(total, (uint32_t)(2 * W), (uint32_t)(W + w)), q), out_abi + (size_t)(W + w) * 48 + 12 * q);
 }
+// (an Edwards launch leaves (X : Y : Z : T) per window in out_abi: the host applies psi, edw_abi_to_jac)
+__global__ void __launch_bounds__(64, 2) k_hilo_combine(ZK_HCOMB_PARAMS) { hilo_combine_impl<false>(work, W, lo_bits, out_abi, total); }
+__global__ void __launch_bounds__(64, 2) k_hilo_combine_edw(ZK_HCOMB_PARAMS) { hilo_combine_impl<true>(work, W, lo_bits, out_abi, total); }
 
 // ---- batch fixed-base scalar multiplication: out[i] = k_i * G (the inner loop of Groth16 setup:
 // reference libzecale/circuits/aggregator_circuit.tcc:100-109 -> wsnarkT::generate_setup) ----
@@ -1739,13 +1766,14 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   const size_t B = ctx->B, nb = B * W;
   hipStream_t st = ctx->stream;
   ctx->pending_n = n_tot;
+  ctx->win_edw = false;
   if (n_tot == 0) { ctx->pending = true; return ZKHIP_OK; }
   WindowPlan plan;
   memset(&plan, 0, sizeof plan);
   for (int w = 0; w < Wd; w++) { plan.off[w] = ctx->win_off[w]; plan.bits[w] = ctx->win_bits[w]; }
   // the Edwards accumulation (ec_edw.cuh): a single MSM over a one-level-per-window table that has its Edwards form, no batched-affine
-  // levels in front.  The digits are XYZZ's (the table holds chi of the HALVED points); the slots go back to XYZZ right after the
-  // accumulation, everything after that is unchanged.
+  // levels in front.  The digits are XYZZ's (the table holds chi of the HALVED points); the slots, the stitching and the bucket
+  // reduction hold Edwards points (the k_..._edw kernels), and the host maps the window results back (win_edw: edw_abi_to_jac).
   const bool edw = merged == 1 && K == 1 && ctx->K == 1 && ctx->aff_levels == 0 && jobs[0].edw != nullptr;
   const uint32_t wf = edw ? ZK_W_NEXT : ZK_W_FIRST;
   DigitJobs dj;
@@ -1884,11 +1912,6 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
     hipLaunchKernelGGL(k_accumulate<MSM_MAX_JOBS>, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off,
                        cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
   HIP_TRY(hipEventRecord(ctx->ev_acc1, st));
-  // psi: the Edwards slots (buckets, then the F and L pieces of the T_run slices) back to XYZZ
-  if (edw) {
-    const uint32_t n_conv = (uint32_t)nb + 2u * T_run;
-    hipLaunchKernelGGL(k_slots_edw_to_xyzz, dim3(nblk(n_conv, 256)), dim3(256), 0, st, ctx->buckets, ctx->slot_stride, n_conv);
-  }
   ctx->last_S = S_run; ctx->last_T = T_run; ctx->last_tight = tight;
   // fold the F pieces of the buckets that have several (lists made by k_accumulate), then L + F for every cut bucket
   if (T_run > 2) {
@@ -1898,13 +1921,12 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
     if (sblocks > 1024) sblocks = 1024;                                        // (the list is walked with a grid stride)
     // + 512 workgroups for the long list: a wrapping proof has ~290 buckets of 7-8 pieces (values that occur a couple of hundred
     // times in the assignment, in every window): with 128 workgroups they took three sweeps of three rounds each
-    if (fold_quads) hipLaunchKernelGGL(k_fixup_fold<true>, dim3(sblocks + 512), dim3(256), 0, st, ctx->block_tot, ctx->fix_short, ctx->fix_list, sblocks,
-                                       (uint32_t)nb, ctx->buckets, ctx->slot_stride);
-    else hipLaunchKernelGGL(k_fixup_fold<false>, dim3(sblocks + 512), dim3(256), 0, st, ctx->block_tot, ctx->fix_short, ctx->fix_list, sblocks,
-                            (uint32_t)nb, ctx->buckets, ctx->slot_stride);
+    auto fold = fold_quads ? (edw ? k_fixup_fold_edw<true> : k_fixup_fold<true>) : (edw ? k_fixup_fold_edw<false> : k_fixup_fold<false>);
+    hipLaunchKernelGGL(fold, dim3(sblocks + 512), dim3(256), 0, st, ctx->block_tot, ctx->fix_short, ctx->fix_list, sblocks, (uint32_t)nb, ctx->buckets,
+                       ctx->slot_stride);
   }
-  hipLaunchKernelGGL(k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run,
-                     ctx->buckets, ctx->slot_stride, wf);
+  hipLaunchKernelGGL(edw ? k_fixup_edw : k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight,
+                     T_run, ctx->buckets, ctx->slot_stride, wf);
   HIP_TRY(hipGetLastError());
 
   // ---- bucket reduction -------------------------------------------------------------------------------
@@ -1924,8 +1946,8 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   auto launch_sum = [&](hipStream_t s_, uint32_t* in, size_t n_in, uint32_t in_stride, int L, uint32_t row_len, uint32_t* out) {
     size_t n_out = n_in / L;
     const int in_slots = (in == ctx->buckets) ? 1 : 0;          // the first level reads the slot array (an array of structures: ec_mem.cuh)
-    if (n_out >= QUAD_BELOW) hipLaunchKernelGGL(k_sum_lds, dim3(nblk(n_out, 256)), dim3(256), 0, s_, in, n_in, in_stride, L, row_len, out, in_slots);
-    else hipLaunchKernelGGL(k_sum<true>, dim3(nblk(n_out * 4, 256)), dim3(256), 0, s_, in, n_in, in_stride, L, row_len, out, in_slots);
+    if (n_out >= QUAD_BELOW) hipLaunchKernelGGL(edw ? k_sum_lds_edw : k_sum_lds, dim3(nblk(n_out, 256)), dim3(256), 0, s_, in, n_in, in_stride, L, row_len, out, in_slots);
+    else hipLaunchKernelGGL(edw ? k_sum_edw<true> : k_sum<true>, dim3(nblk(n_out * 4, 256)), dim3(256), 0, s_, in, n_in, in_stride, L, row_len, out, in_slots);
   };
   HIP_TRY(hipEventRecord(ctx->ev, st));
   HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
@@ -1983,9 +2005,9 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
     uint32_t* S = ctx->segS[level & 1];
     uint32_t* Rk = ctx->segR + r_off * 108;
     if (n_out >= QUAD_BELOW)
-      hipLaunchKernelGGL(k_seg<false>, dim3(nblk(n_out, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
+      hipLaunchKernelGGL(edw ? k_seg_edw<false> : k_seg<false>, dim3(nblk(n_out, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
     else
-      hipLaunchKernelGGL(k_seg<true>, dim3(nblk(n_out * 4, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
+      hipLaunchKernelGGL(edw ? k_seg_edw<true> : k_seg<true>, dim3(nblk(n_out * 4, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
     HIP_TRY(hipEventRecord(ctx->ev, st));
     HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
     // reduce R (n_out items, G groups) to G items: Rlevels[level]
@@ -2009,12 +2031,13 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   HIP_TRY(hipEventRecord(ctx->ev2, st2));
   HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
   // the last S (one item per group) has weight 0 at its level (o = 0 for level >= 1) and is dropped.
-  hipLaunchKernelGGL(k_window_combine, dim3(nblk((size_t)G * 4, 64)), dim3(64), 0, st, ctx->Rlevels, level, G, ls, ctx->sumR[0]);
-  hipLaunchKernelGGL(k_hilo_combine, dim3(nblk((size_t)W * 4, 64)), dim3(64), 0, st, ctx->sumR[0], W, lo_bits, ctx->win_abi,
+  hipLaunchKernelGGL(edw ? k_window_combine_edw : k_window_combine, dim3(nblk((size_t)G * 4, 64)), dim3(64), 0, st, ctx->Rlevels, level, G, ls, ctx->sumR[0]);
+  hipLaunchKernelGGL(edw ? k_hilo_combine_edw : k_hilo_combine, dim3(nblk((size_t)W * 4, 64)), dim3(64), 0, st, ctx->sumR[0], W, lo_bits, ctx->win_abi,
                      ctx->merged == 2 ? cur : (uint32_t*)nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(ctx->win_host, ctx->win_abi, (size_t)W * 48 * 8 * (ctx->merged == 2 ? 2 : 1), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(ctx->ev_done, st));
+  ctx->win_edw = edw;         // what win_host will hold for THIS launch (the context may serve an XYZZ set next)
   ctx->pending = true;        // only a completely enqueued sequence is collectable; a failed launch leaves the context reusable
   return ZKHIP_OK;
 }
@@ -2031,6 +2054,24 @@ static void xyzz_abi_to_jac(const uint64_t* p, host::HJac& q) {
   q.Z = ZZ * ZZZ;
 }
 
+// The window result of an Edwards launch, (X : Y : Z : T) in ABI limbs: psi (ec_edw.cuh) takes it to the XYZZ point of G1 -
+//   W = Z^2 - Y^2, lambda = X W, ZZ = lambda^2, ZZZ = lambda^3, X' = (X^2 + c1 Z^2) W^2, Y' = c2 Y Z^2 ZZ
+// (x = 1 + c1 Z^2 / X^2, y = c2 Y Z^2 / (X W): tools/gen_params.py edwards_params).  psi is a homomorphism, so psi of the weighted
+// bucket sum is the weighted sum of the buckets' images: twelve host products per MSM.  X = 0 - the identity, or an empty window
+// (all zeros) - gives ZZ = 0: infinity.
+static void edw_abi_to_jac(const uint64_t* p, host::HJac& q) {
+  using namespace host;
+  const HFq X = HFq::from_limbs(p), Y = HFq::from_limbs(p + 12), Z = HFq::from_limbs(p + 24);
+  const HFq c1 = HFq::from_limbs(FqParams::EDW_C1_64), c2 = HFq::from_limbs(FqParams::EDW_C2_64);
+  const HFq Z2 = Z.sqr(), Wv = Z2 - Y.sqr(), lam = X * Wv, ZZ = lam.sqr();
+  uint64_t xyzz[48];
+  ((X.sqr() + c1 * Z2) * Wv.sqr()).to_limbs(xyzz);
+  (c2 * Y * Z2 * ZZ).to_limbs(xyzz + 12);
+  ZZ.to_limbs(xyzz + 24);
+  (ZZ * lam).to_limbs(xyzz + 36);
+  xyzz_abi_to_jac(xyzz, q);
+}
+
 int msm_finish_multi(MsmCtx* ctx, int K, uint64_t* out_jac) {
   using namespace host;
   if (!ctx->pending || !ctx->merged || K < 1 || K > ctx->K) return ZKHIP_ERR_STATE;
@@ -2041,7 +2082,8 @@ int msm_finish_multi(MsmCtx* ctx, int K, uint64_t* out_jac) {
   }
   for (int k = 0; k < K; k++) {
     HJac q = HJac::infinity();
-    if (ctx->pending_n) xyzz_abi_to_jac(ctx->win_host + (size_t)k * 48, q);    // one bucket window per job: nothing to combine
+    if (ctx->pending_n && ctx->win_edw) edw_abi_to_jac(ctx->win_host + (size_t)k * 48, q);      // (an Edwards launch: K = 1, merged = 1)
+    else if (ctx->pending_n) xyzz_abi_to_jac(ctx->win_host + (size_t)k * 48, q);    // one bucket window per job: nothing to combine
     if (ctx->pending_n && ctx->merged == 2) {                                  // odd digits: sum (2 b + 1) S_b = 2 F - sum S_b
       HJac tot;
       xyzz_abi_to_jac(ctx->win_host + (size_t)(ctx->K + k) * 48, tot);
