@@ -51,6 +51,7 @@ int zkhip_init(int device);
 int zkhip_set_device(int device);
 int zkhip_get_device(void);              /* -1 before the first zkhip_init */
 int zkhip_device_count(void);            /* GPUs visible to the process (0 without a HIP runtime) */
+int zkhip_device_memory(size_t* free_bytes, size_t* total_bytes);  /* of the calling thread's library device, now (either may be null) */
 void zkhip_shutdown(void);
 const char* zkhip_strerror(int code);
 const char* zkhip_last_error(void);
@@ -333,7 +334,9 @@ int zkhip_bls12_377_groth16_verify(const uint64_t vk_alpha_g1[12], const uint64_
                                    const uint64_t proof_a[12], const uint64_t proof_b[24], const uint64_t proof_c[12], int* ok);
 
 /* replaces: libzecale::aggregator_circuit<wppT, wsnarkT, nverifierT, NumProofs>(inputs_per_nested_proof)
- * (libzecale/circuits/aggregator_circuit.hpp:32-114; constructor .tcc:17-98): builds the constraint system. */
+ * (libzecale/circuits/aggregator_circuit.hpp:32-114; constructor .tcc:17-98): builds the constraint system.
+ * num_proofs 1 .. 32 (one result bit per nested proof, packed into one primary input), inputs_per_proof 1 .. 16; anything else:
+ * ZKHIP_ERR_ARG.  32 proofs with one input each are 575,723 constraints (a 2^20 domain), with nine inputs 1,230,075 (2^21). */
 typedef struct zkhip_aggregator zkhip_aggregator;
 int zkhip_aggregator_new(size_t num_proofs, size_t inputs_per_proof, zkhip_aggregator** out);
 void zkhip_aggregator_free(zkhip_aggregator* a);
@@ -358,8 +361,9 @@ int zkhip_aggregator_check_inputs(const zkhip_aggregator* a, const uint64_t* nes
 int zkhip_aggregator_vk_hash(const uint64_t* nested_vk, size_t inputs_per_proof, uint64_t out[6]);
 
 /* Witness generation ON THE GPU: the same assignment as zkhip_aggregator_witness, limb for limb, computed by a device kernel that
- * interprets the straight-line program recorded from the circuit (witness_tape.cpp, witness.hip).  One batch occupies four waves for
- * ~tens of milliseconds: the gain is not latency (the host generator takes 8 ms on three cores) but host cores - a server keeps
+ * interprets the straight-line program recorded from the circuit (witness_tape.cpp, witness.hip).  One batch occupies one wave of
+ * the levelled program and one of the key-hash chain (a workgroup of up to sixteen waves where the program is wide: batches of
+ * many nested proofs, zkhip_gpu_witness_set_waves) for ~tens of milliseconds: the gain is not latency (the host generator takes 8 ms on three cores) but host cores - a server keeps
  * many batches in flight and the GPU generates their witnesses under the provers' kernels.
  *   zkhip_aggregator_witness_gpu   one batch, host in / host out (allocates its work space: a test / convenience entry point)
  *   zkhip_gpu_witness_*            work space for one batch in flight on the calling thread's device; run() leaves the assignment
@@ -379,6 +383,20 @@ int zkhip_gpu_witness_new_batched(zkhip_aggregator* a, size_t max_batches, zkhip
 int zkhip_gpu_witness_run_batched(zkhip_gpu_witness* w, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
                                   const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate);
 void zkhip_gpu_witness_free(zkhip_gpu_witness* w);
+/* Waves per witness of the levelled program, for every later run of this handle: 1 = one wave per witness (k_witness); 2, 4, 8, 16 = a
+ * workgroup of that many waves per witness that share each level of the program and meet at a barrier after it (k_witness_wide:
+ * worth it where a level holds several 64-instruction chunks - 5.4 on average at 32 nested proofs, 1.07 at two); 0 = auto, the
+ * default: one wave below 1.5 chunks per level on average, eight from there on (profiles/batch32_witness.txt).  Anything else: ZKHIP_ERR_ARG.  The assignment is the same at every width. */
+int zkhip_gpu_witness_set_waves(zkhip_gpu_witness* w, int waves);
+/* milliseconds the kernels of w's last run took on the device, all its batches together (HIP events on the run's stream, from before
+ * the first launch to after the kernel that writes the assignments; the copies are outside) */
+int zkhip_gpu_witness_last_ms(zkhip_gpu_witness* w, double* ms);
+/* HOST ONLY: what the recorded program of the circuit asks of the device.  out[0] chunks of 64 instructions in the levelled program,
+ * out[1] its levels, out[2] sum over levels of ceil(chunks of the level / waves) - the chunk-times on the critical path when `waves`
+ * waves share each level -, out[3] bytes of values per witness in flight (zkhip_gpu_witness_new_batched allocates max_batches times
+ * that and fails with ZKHIP_ERR_HIP, naming the bytes, when the device does not have them).  waves = 0: out[2] is THE WIDTH auto
+ * picks for this program instead (ask again with that width for its steps). */
+int zkhip_gpu_witness_plan(zkhip_aggregator* a, int waves, size_t out[4]);
 /* the recorded program: [0] operations recorded, [1] positions after levelling (with padding), [2] dependent levels,
  * [3] multiplications, [4] inversions, [5] distinct constants */
 int zkhip_gpu_witness_stats(zkhip_aggregator* a, size_t out[6]);
@@ -560,6 +578,14 @@ typedef struct zkhip_witness_program {
  * wrong values, never a wrong address. */
 int zkhip_internal_witness_run_program(const zkhip_witness_program* p, const uint64_t* inputs, size_t batches, int witnesses_per_workgroup,
                                        unsigned segment_chunks, uint64_t* z_out, uint32_t* flags_out);
+/* The same with the waves per witness given (zkhip_gpu_witness_set_waves: 0, 1, 2, 4, 8, 16; the hook above passes 1).  The wide
+ * kernels run whole levels per launch: the first level boundary at which a launch holds segment_chunks chunks or more. */
+int zkhip_internal_witness_run_program_wide(const zkhip_witness_program* p, const uint64_t* inputs, size_t batches, int witnesses_per_workgroup,
+                                            unsigned segment_chunks, int waves, uint64_t* z_out, uint32_t* flags_out);
+/* HOST ONLY: how a GPU-witness pipeline sizes itself - out[0] witnesses per launch (at most wit_batch, which is 16 or ZKHIP_WIT_BATCH)
+ * and out[1] batcher threads (at most workers) such that out[0] x out[1] x value_bytes stays under a quarter of mem_total: the batch
+ * is halved first (rounding up, down to one), then batchers are dropped (down to one). */
+int zkhip_internal_pipeline_witness_sizing(size_t value_bytes, size_t mem_total, size_t wit_batch, int workers, size_t out[2]);
 /* HOST ONLY: the recorded program of the circuit, as zkhip_gpu_witness_run uploads it (pointers into the handle, valid until
  * zkhip_aggregator_free). */
 int zkhip_internal_witness_tape(zkhip_aggregator* a, zkhip_witness_program* out);
@@ -568,6 +594,10 @@ int zkhip_internal_witness_tape(zkhip_aggregator* a, zkhip_witness_program* out)
 int zkhip_internal_gpu_witness_run(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk,
                                    const uint64_t* const* nested_proofs, const uint64_t* const* nested_inputs, void* d_z_out,
                                    uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup, unsigned segment_chunks);
+/* The same with the waves per witness given (0 = auto; the hook above passes 1) */
+int zkhip_internal_gpu_witness_run_wide(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk,
+                                        const uint64_t* const* nested_proofs, const uint64_t* const* nested_inputs, void* d_z_out,
+                                        uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup, unsigned segment_chunks, int waves);
 
 /* replaces: libff::Fr<wppT>::random_element() as r1cs_gg_ppzksnark_prover draws the proof's randomisers r, s (reached from
  * aggregator_circuit.tcc:168) and the generator its toxic waste: one field element uniform in Fr, 6 Montgomery limbs, from the

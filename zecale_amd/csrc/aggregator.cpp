@@ -1,5 +1,6 @@
 // Host side of the wrapping circuit: native BLS12-377 Groth16 verification and (below) the aggregator circuit.
 #include <string.h>
+#include <atomic>
 #include <mutex>
 #include <thread>
 #include <exception>
@@ -98,6 +99,30 @@ void write_assignment(uint64_t* z_out, size_t n_vars, const std::vector<HFr>& he
   }
 }
 
+// At most this many section threads per witness: a one-GPU job is given sixteen cores, and a batch of 32 has 34 sections.
+constexpr size_t MAX_SECTION_THREADS = 16;
+
+// sections [first, ns) of one witness, each through run(s): one thread per section up to sixteen of them (every batch of up to
+// sixteen proofs, the limit until now, runs exactly as before: the same threads, the same sections), otherwise MAX_SECTION_THREADS
+// workers, less those of the witness that run already, take the next section off a counter.  The calling thread is one of them.
+// A section's values depend on nothing but its inputs, so the assignment is the same whoever computes it.
+template <class Run>
+void run_sections(size_t first, size_t ns, size_t already_running, const Run& run) {
+  const size_t n = ns > first ? ns - first : 0;
+  if (n == 0) return;
+  std::vector<std::thread> th;
+  if (n <= MAX_SECTION_THREADS) {
+    for (size_t s = first + 1; s < ns; s++) th.emplace_back(run, s);
+    run(first);
+  } else {
+    std::atomic<size_t> next{first};
+    auto worker = [&] { for (size_t s = next.fetch_add(1); s < ns; s = next.fetch_add(1)) run(s); };
+    for (size_t w = 1; w + already_running < MAX_SECTION_THREADS; w++) th.emplace_back(worker);
+    worker();
+  }
+  for (auto& t : th) t.join();
+}
+
 // assignment only, sections on separate threads
 void witness_parallel(uint64_t* z_out, size_t n_vars, size_t num_proofs, size_t k, const NestedData* data) {
   const size_t section_cap = n_vars / (num_proofs ? num_proofs : 1) + 64;
@@ -125,10 +150,8 @@ void witness_parallel(uint64_t* z_out, size_t n_vars, size_t num_proofs, size_t 
   };
   std::thread t_hash(run, 0);
   run(1);                                               // the proof sections read the key's lines
-  std::vector<std::thread> th;
-  if (!errs[1]) for (size_t s = 2; s < ns; s++) th.emplace_back(run, s);
+  if (!errs[1]) run_sections(2, ns, 1, run);            // (the hash thread is still running)
   t_hash.join();
-  for (auto& t : th) t.join();
   for (auto& e : errs) if (e) { for (auto& p : parts) section_pool().put(p); std::rethrow_exception(e); }
   b0.z[1] = results[0];
   HFr packed = HFr::zero(), pow2 = HFr::one();
@@ -162,10 +185,7 @@ void witness_proofs_only(uint64_t* z_out, const zkhip_aggregator* a, const Neste
       parts[p].swap(bs.z);
     } catch (...) { errs[p] = std::current_exception(); current_builder() = nullptr; }
   };
-  std::vector<std::thread> th;
-  for (size_t p = 1; p < num_proofs; p++) th.emplace_back(run, p);
-  run(0);
-  for (auto& t : th) t.join();
+  run_sections(0, num_proofs, 0, run);
   for (auto& e : errs) if (e) { for (auto& p : parts) section_pool().put(p); std::rethrow_exception(e); }
   if (b0.z.size() != a->sec_hash) throw std::runtime_error("assignment layout changed");
   HFr packed = HFr::zero(), pow2 = HFr::one();
@@ -192,7 +212,7 @@ void to_csr(const std::vector<LC>& M, std::vector<uint32_t>& rp, std::vector<uin
 extern "C" {
 
 int zkhip_aggregator_new(size_t num_proofs, size_t inputs_per_proof, zkhip_aggregator** out) {
-  if (!out || num_proofs == 0 || num_proofs > 16 || inputs_per_proof == 0 || inputs_per_proof > 16) return ZKHIP_ERR_ARG;
+  if (!out || num_proofs == 0 || num_proofs > 32 || inputs_per_proof == 0 || inputs_per_proof > 16) return ZKHIP_ERR_ARG;
   zkhip_aggregator* a = new zkhip_aggregator();
   a->num_proofs = num_proofs; a->inputs_per_proof = inputs_per_proof;
   Builder b;

@@ -364,6 +364,19 @@ void gpu_loop(zkhip_pipeline* p, zkhip_prover* pr) {
 
 extern "C" {
 
+// Host only: the witnesses per launch and the batcher threads a GPU-witness pipeline runs with, given `value_bytes` of work space
+// per witness in flight and a device of `mem_total` bytes: workers x batch x value_bytes <= mem_total / 4, by halving the batch
+// (rounding up) down to one, then by dropping workers down to one.
+int zkhip_internal_pipeline_witness_sizing(size_t value_bytes, size_t mem_total, size_t wit_batch, int workers, size_t out[2]) {
+  if (!out || !value_bytes || wit_batch < 1 || workers < 1) return ZKHIP_ERR_ARG;
+  const size_t budget = mem_total / 4;
+  size_t w = (size_t)workers;
+  while (wit_batch > 1 && w * wit_batch * value_bytes > budget) wit_batch = (wit_batch + 1) / 2;
+  while (w > 1 && w * wit_batch * value_bytes > budget) w--;
+  out[0] = wit_batch; out[1] = w;
+  return ZKHIP_OK;
+}
+
 int zkhip_aggregator_pipeline_new(zkhip_aggregator* a, const zkhip_crs* crs, int gpu_slots, int witness_workers, zkhip_pipeline** out) {
   return zkhip_aggregator_pipeline_new_ex(a, crs, gpu_slots, witness_workers, 0, out);
 }
@@ -389,6 +402,18 @@ int zkhip_aggregator_pipeline_new_ex(zkhip_aggregator* a, const zkhip_crs* crs, 
   if (p->gpu_witness) {
     if (witness_workers > 8) witness_workers = 8;     // batcher threads: each keeps one launch of wit_batch witnesses in flight
     if (zkhip_set_device(p->device) != ZKHIP_OK) { delete p; return ZKHIP_ERR_STATE; }
+    // The generators' work space - n_pos x 64 bytes of values per witness in flight, 70 MB at a batch of two, 806 MB at 32 proofs of
+    // nine inputs - stays under a quarter of the device's memory (the rule of the Edwards table): fewer witnesses per launch first,
+    // then fewer launches in flight.  Every shape up to 16 proofs keeps its 16 per launch.
+    // (ZKHIP_WIT_BATCH is therefore the MOST witnesses per launch: the rule may lower it.)
+    size_t plan[4] = {0, 0, 0, 0}, mem_free = 0, mem_total = 0;
+    if (zkhip_gpu_witness_plan(a, 0, plan) == ZKHIP_OK && zkhip_device_memory(&mem_free, &mem_total) == ZKHIP_OK) {
+      size_t sized[2] = {p->wit_batch, (size_t)witness_workers};
+      if (zkhip_internal_pipeline_witness_sizing(plan[3], mem_total, p->wit_batch, witness_workers, sized) == ZKHIP_OK) {
+        p->wit_batch = sized[0];
+        witness_workers = (int)sized[1];
+      }
+    }
     const size_t n_slabs = (size_t)witness_workers + (size_t)gpu_slots / 2 + 2;
     for (size_t i = 0; i < n_slabs; i++) {
       void* b = nullptr;

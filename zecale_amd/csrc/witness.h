@@ -36,10 +36,19 @@ int witness_tape_of(zkhip_aggregator* a, const WitnessTape** tape, char* err, si
 // (64 .. 2^20 chunks, default 2,048), each read once
 uint32_t witness_env_wpg();
 uint32_t witness_env_segment();
-// wpg: witnesses per workgroup, a wave each (1, 2 or 4; anything else = 4); seg: chunks of the levelled program per launch (>= 1);
+// wpg: witnesses per workgroup, a wave each (1, 2 or 4; anything else = 4; the narrow kernel only); seg: chunks of the levelled
+// program per launch (>= 1; the wide kernels run whole levels, about seg chunks of them); waves: 1 = k_witness, a wave per witness,
+// 2 | 4 | 8 | 16 = k_witness_wide, a workgroup of that many waves per witness, 0 = what witness_plan picks for the program;
+// h_level_start: the program's level_start on the HOST (n_levels + 1 entries; without it the launch is narrow);
 // inputs: batches x n_inputs x 6 u64 (ABI form: nested key | proofs | inputs); values: batches x n_pos x 16 u32 (witness_value_bytes);
 // z: batches x n_vars x 6 u64 (ABI form); flags: one word per batch, set when an inversion met zero (cleared by the caller)
 constexpr size_t witness_value_bytes = 64;      // one value slot
-void witness_launch(const WitnessProg& P, const uint64_t* d_inputs, uint32_t* d_values, uint64_t* d_z, uint32_t* d_flags, uint32_t batches,
-                    uint32_t wpg, uint32_t seg, hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join);
+void witness_launch(const WitnessProg& P, const uint32_t* h_level_start, const uint64_t* d_inputs, uint32_t* d_values, uint64_t* d_z, uint32_t* d_flags,
+                    uint32_t batches, uint32_t wpg, uint32_t seg, uint32_t waves, hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join);
+// Host only.  steps: the sum over levels of ceil(chunks of the level / waves), the chunk-times on the critical path; waves: the
+// width asked for, or for 0 the one auto picks - 1 below 1.5 chunks per level on average.
+struct WitnessPlan { size_t chunks, levels, steps, value_bytes; uint32_t waves; };
+WitnessPlan witness_plan(const uint32_t* level_start, size_t n_levels, size_t n_pos, uint32_t waves);
+uint32_t witness_auto_waves(size_t chunks, size_t levels);      // what auto picks: two numbers of the program, no walk over its levels
+bool witness_waves_ok(int waves);               // 0, 1, 2, 4, 8, 16
 }  // namespace zkhip

@@ -234,6 +234,128 @@ __global__ void __launch_bounds__(64 * WPG) k_witness(WitnessProg P, uint32_t c0
   if (bad) atomicOr(&flags[batch], 1u);
 }
 
+// ---- wide programs: ONE WORKGROUP PER WITNESS ---------------------------------------------------------------------------------
+// A batch of 32 nested proofs has the depth of a batch of two (15,901 levels against 15,897) and sixteen times the work: a level is
+// 5.4 chunks wide on average, and one wave walks them one after the other.  k_witness_wide gives a witness WAVES waves: within a
+// level wave w takes chunks first + w, first + w + WAVES, ...; ONE workgroup barrier ends the level.  The launch runs whole levels
+// [l0, l1).  Every wave walks its own list of ITEMS - (level, chunk), one item at least per level, an empty one where the level has
+// no chunk for it - and runs the barrier after its last item of a level, so every wave meets every level's barrier exactly once.
+//
+// What a wave may read, and when (the narrow kernel's "a load issued three fences after this wave's own store" says nothing about
+// another wave's store).  __syncthreads() is a workgroup-scope release, the barrier, and a workgroup-scope acquire: whatever any
+// wave stored - to the LDS ring or to the value array - before the barrier that ends level l is visible to every load any wave of
+// the workgroup issues after that barrier.  For the ring that is a wait: s_waitcnt lgkmcnt(0) stands before s_barrier.  For the
+// value array it is NOT: no vmcnt(0) is emitted, the store may still be on its way when the barrier opens.  It is ordered, not
+// drained: the waves of a workgroup run on one CU (no threadgroup-split mode here), whose write-through vector L1 serves their
+// vector memory operations in the order they were issued, so a store issued before the barrier is served before a load issued
+// after it - this is what the compiler's memory model for this target relies on when it omits the wait.  Both the prefetch and
+// the memory-path load below are vector loads issued after that barrier.  Hence, with ls(l) the first position of level l:
+//   * while a wave is at an item of level l it has passed the barrier of level l - 1: every position below ls(l) is complete and
+//     visible, in memory.  The operands of the wave's NEXT item are prefetched from the value array under exactly that limit
+//     (w_prefetch with t.ls), whether the next item belongs to level l or to level l + 1;
+//   * an operand of an item of level l + 1 that lies in level l (at or above the limit its prefetch ran under, `plim`) is read
+//     AFTER the barrier of level l - program order, the wave's previous item ended with it - from the ring, or from memory where the
+//     ring does not hold it;
+//   * positions written by an earlier launch are below ls(l0), complete before this kernel began; the first prefetch runs under
+//     ls(l0) and the ring, empty at launch, is never asked for anything below it (plim >= ls(l0));
+//   * instruction words and constants are read-only and fetched ahead as in k_witness.
+// The ring (slot = position mod WIDE_RING, shared by the workgroup).  During level l (positions [ls, le)) the waves read slots of
+// positions in [max(plim, le - WIDE_RING), ls) and write slots of positions p in [ls, le) with p + WIDE_RING >= le (an earlier p
+// would be overwritten within its own level by a wave that runs in no particular order to this one - and no later level asks the
+// ring for it: its ring_lo is at least le - WIDE_RING + 64).  A written p and a read q of one slot would have p >= q + WIDE_RING
+// >= le: there is none, so reads and writes of one level never meet, and levels are separated by the barrier.  A read q >=
+// le(l) - WIDE_RING of level l - 1 was written: q + WIDE_RING >= le(l) > le(l - 1).
+// LDS: 1,012 ring entries and the twelve of subk, 64 KiB exactly (a witness workgroup takes no more of a CU
+// than k_witness's does).
+constexpr uint32_t WIDE_RING = 1024 - WT_SUBK_LEVELS;
+struct WItem { uint32_t level, chunk, ls, le; bool has, last; };       // wave-uniform: [ls, le) the level's positions; last: the barrier follows
+template <uint32_t WAVES>
+__global__ void __launch_bounds__(64 * WAVES) k_witness_wide(WitnessProg P, uint32_t l0, uint32_t l1, const uint64_t* __restrict__ inputs /* batches x n_inputs x 6, ABI */,
+                                                              uint32_t* __restrict__ values /* batches x n_pos x 16 */, uint32_t* __restrict__ flags) {
+  static_assert(WAVES == 2 || WAVES == 4 || WAVES == 8 || WAVES == 16, "k_witness_wide: 2, 4, 8 or 16 waves");
+  static_assert((WIDE_RING + WT_SUBK_LEVELS) * 64 <= 65536, "k_witness_wide: 64 KiB of LDS");
+  __shared__ uint4 ring[WIDE_RING * 4];
+  __shared__ uint4 subk[WT_SUBK_LEVELS * 4];
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+  const uint32_t batch = blockIdx.x;                                  // (the grid is the batches: no workgroup without a witness)
+  if (threadIdx.x < WT_SUBK_LEVELS * 4) subk[threadIdx.x] = reinterpret_cast<const uint4*>(P.subk)[threadIdx.x];
+  __syncthreads();
+  if (WIT_PRIO) __builtin_amdgcn_s_setprio(3);                        // (see k_witness, where it was timed beside the provers; here it is carried over, not timed)
+  const uint64_t* in = inputs + (size_t)batch * P.n_inputs * 6;
+  uint32_t* vals = values + (size_t)batch * P.n_pos * WSLOT;
+  uint32_t bad = 0;
+  const uint32_t ls0 = P.level_start[l0];
+  // the wave's first item of level it.level (it.ls set), and the item after `it`; from level l1 on: empty items, never run
+  auto enter = [&](WItem& it) {
+    it.le = it.level < l1 ? P.level_start[it.level + 1] : it.ls;
+    it.chunk = it.ls / 64 + wave;
+    it.has = it.chunk < it.le / 64;
+    it.last = !(it.has && it.chunk + WAVES < it.le / 64);
+  };
+  auto advance = [&](const WItem& t) {
+    WItem it = t;
+    if (it.level >= l1) return it;
+    if (!it.last) { it.chunk += WAVES; it.last = !(it.chunk + WAVES < it.le / 64); }
+    else { it.level++; it.ls = it.le; enter(it); }
+    return it;
+  };
+  // (no branch around the loads, as in w_fetch: an empty item fetches the launch's first chunk and turns it into no-ops)
+  auto fetch = [&](const WItem& it) {
+    const uint32_t p = (it.has ? it.chunk * 64 : ls0) + lane;
+    WIns r{P.code[p], P.a[p], P.b[p]};
+    if (!it.has) r.code = WT_NOP;
+    return r;
+  };
+  // one item: `cur` with the operands (cx, cy) prefetched under the limit plim; `nxt` is the wave's next item, whose operands are requested here
+  auto step = [&](const WItem& t, const WIns& cur, WVal& cx, WVal& cy, uint32_t plim, const WIns& nxt, WVal& nx, WVal& ny) {
+    w_prefetch(P, vals, nxt, t.ls, nx, ny);                           // the barrier of level t.level - 1 is behind this wave
+    const uint32_t ring_lo = t.le > WIDE_RING ? t.le - WIDE_RING : 0u;
+    const uint32_t c = cur.code;
+    if (c != WT_NOP) {
+      FrD x = fp_zero<FrParams>(), y = x, r = x;
+      if (c != WT_INPUT) {
+        // at or above plim: the previous level, complete since the barrier this wave's previous item ended with
+        WVal xv = (cur.a < 0 || (uint32_t)cur.a < plim) ? cx : w_ld(&ring[((uint32_t)cur.a % WIDE_RING) * 4]);
+        WVal yv = cy;
+        if (w_binary(c)) yv = (cur.b < 0 || (uint32_t)cur.b < plim) ? cy : w_ld(&ring[((uint32_t)cur.b % WIDE_RING) * 4]);
+        if (ring_lo > plim) {                                         // (wave-uniform, rare: this level and the one before are wider than the ring)
+          if (cur.a >= 0 && (uint32_t)cur.a >= plim && (uint32_t)cur.a < ring_lo) xv = w_ld(reinterpret_cast<const uint4*>(vals + (size_t)cur.a * WSLOT));
+          if (w_binary(c) && cur.b >= 0 && (uint32_t)cur.b >= plim && (uint32_t)cur.b < ring_lo) yv = w_ld(reinterpret_cast<const uint4*>(vals + (size_t)cur.b * WSLOT));
+        }
+        x = w_from(xv);
+        if (w_binary(c)) y = w_from(yv);
+      }
+      if (w_exec(c, cur.b, x, y, in, cur.a, r, subk, P.mu)) bad = 1;
+      const WVal v = w_to(r);
+      const uint32_t p = t.chunk * 64 + lane;
+      w_st(reinterpret_cast<uint4*>(vals + (size_t)p * WSLOT), v);
+      if (p + WIDE_RING >= t.le) w_st(&ring[(p % WIDE_RING) * 4], v);
+    }
+    // ends the level.  LDS stores are waited for (lgkmcnt(0)); global stores are not drained (no vmcnt(0)) but ordered: one CU, one
+    // vector L1 that serves its waves' memory operations in issue order, so any load issued after the barrier sees them
+    if (t.last) __syncthreads();
+  };
+  WItem t0{l0, 0, ls0, 0, false, true};
+  enter(t0);
+  WItem t1 = advance(t0), t2 = advance(t1), t3 = advance(t2);
+  WIns i0 = fetch(t0), i1 = fetch(t1), i2 = fetch(t2), i3 = fetch(t3);
+  WVal ax, ay, bx, by;
+  for (int k = 0; k < 4; k++) ax.q[k] = ay.q[k] = bx.q[k] = by.q[k] = make_uint4(0, 0, 0, 0);
+  w_prefetch(P, vals, i0, ls0, ax, ay);                               // everything before this launch is in memory
+  uint32_t plim = ls0;
+#pragma unroll 1
+  while (t0.level < l1) {
+    const WItem t4 = advance(t3), t5 = advance(t4);
+    const WIns n4 = fetch(t4), n5 = fetch(t5);
+    step(t0, i0, ax, ay, plim, i1, bx, by);
+    if (t1.level < l1) step(t1, i1, bx, by, t0.ls, i2, ax, ay);
+    plim = t1.ls;
+    t0 = t2; t1 = t3; t2 = t4; t3 = t5;
+    i0 = i2; i1 = i3; i2 = n4; i3 = n5;
+  }
+  if (bad) atomicOr(&flags[batch], 1u);
+}
+
 // The key-hash chain ([chain_start, n_pos) of the program, in execution order) by ONE wave per batch: every lane computes the
 // same instruction (a chain has nothing to spread), lane 0 stores.  The last 64 results wait in an LDS ring; the instruction
 // words are fetched 64 at a time, a lane each, and broadcast.
@@ -427,21 +549,59 @@ uint32_t witness_env_wpg() {
   return (uint32_t)wpg;
 }
 
-void witness_launch(const WitnessProg& P, const uint64_t* d_inputs, uint32_t* d_values, uint64_t* d_z, uint32_t* d_flags, uint32_t batches,
-                    uint32_t wpg, uint32_t seg, hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join) {
+// The width auto picks for programs of 1.5 chunks per level and more.  Eight waves, by tools/batch32_witness_ab.py (the narrow kernel
+// and every width interleaved in one run, profiles/batch32_witness.txt): one witness of (32, 1) in 52.5 ms against 130.5 narrow, of
+// (32, 9) in 164.0 against 308.7, the repeats within 0.5 ms; four waves 57.6 / 165.7, sixteen - which spill - 97.3 / 330.3.
+constexpr uint32_t WIT_WIDE_DEFAULT = 8;
+
+// fewer than 1.5 chunks per level: a second wave would have nothing to do in most levels and every level would pay a barrier
+uint32_t witness_auto_waves(size_t chunks, size_t levels) { return 2 * chunks < 3 * levels ? 1 : WIT_WIDE_DEFAULT; }
+
+WitnessPlan witness_plan(const uint32_t* level_start, size_t n_levels, size_t n_pos, uint32_t waves) {
+  WitnessPlan pl{};
+  pl.levels = n_levels;
+  pl.chunks = n_levels ? level_start[n_levels] / 64 : 0;
+  pl.value_bytes = n_pos * witness_value_bytes;
+  if (waves == 0) waves = witness_auto_waves(pl.chunks, pl.levels);
+  pl.waves = waves;
+  for (size_t l = 0; l < n_levels; l++) pl.steps += ((level_start[l + 1] - level_start[l]) / 64 + waves - 1) / waves;
+  return pl;
+}
+
+bool witness_waves_ok(int waves) { return waves == 0 || waves == 1 || waves == 2 || waves == 4 || waves == 8 || waves == 16; }
+
+void witness_launch(const WitnessProg& P, const uint32_t* h_level_start, const uint64_t* d_inputs, uint32_t* d_values, uint64_t* d_z, uint32_t* d_flags,
+                    uint32_t batches, uint32_t wpg, uint32_t seg, uint32_t waves, hipStream_t st, hipStream_t st_chain, hipEvent_t ev_fork, hipEvent_t ev_join) {
   if (wpg != 1 && wpg != 2) wpg = 4;
   if (seg < 1) seg = 1;
+  if (!h_level_start) waves = 1;
+  else if (waves == 0 || !witness_waves_ok((int)waves)) waves = witness_auto_waves(P.n_levels ? h_level_start[P.n_levels] / 64 : 0, P.n_levels);
   // the key-hash chain on a second stream, next to the levelled program; the assignment is gathered when both are done
   (void)hipEventRecord(ev_fork, st);
   (void)hipStreamWaitEvent(st_chain, ev_fork, 0);
   if (P.chain_start < P.n_pos) hipLaunchKernelGGL(k_witness_chain, dim3(batches), dim3(64), 0, st_chain, P, P.chain_start, d_inputs, d_values, d_flags);
   (void)hipEventRecord(ev_join, st_chain);
   const uint32_t n_chunks = P.chain_start / 64;
-  for (uint32_t c0 = 0; c0 < n_chunks; c0 += seg) {
-    const uint32_t c1 = n_chunks - c0 > seg ? c0 + seg : n_chunks;
-    if (wpg == 4) hipLaunchKernelGGL((k_witness<4, 256>), dim3((batches + 3) / 4), dim3(256), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
-    else if (wpg == 2) hipLaunchKernelGGL((k_witness<2, 512>), dim3((batches + 1) / 2), dim3(128), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
-    else hipLaunchKernelGGL((k_witness<1, 1024>), dim3(batches), dim3(64), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
+  if (waves == 1) {
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += seg) {
+      const uint32_t c1 = n_chunks - c0 > seg ? c0 + seg : n_chunks;
+      if (wpg == 4) hipLaunchKernelGGL((k_witness<4, 256>), dim3((batches + 3) / 4), dim3(256), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
+      else if (wpg == 2) hipLaunchKernelGGL((k_witness<2, 512>), dim3((batches + 1) / 2), dim3(128), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
+      else hipLaunchKernelGGL((k_witness<1, 1024>), dim3(batches), dim3(64), 0, st, P, c0, c1, d_inputs, d_values, d_flags, batches);
+    }
+  } else {
+    // whole levels per launch: the first level boundary at which the launch holds `seg` chunks or more (a launch without a chunk is skipped)
+    for (uint32_t l0 = 0; l0 < P.n_levels;) {
+      uint32_t l1 = l0 + 1;
+      while (l1 < P.n_levels && (h_level_start[l1] - h_level_start[l0]) / 64 < seg) l1++;
+      if (h_level_start[l1] > h_level_start[l0]) {
+        if (waves == 2) hipLaunchKernelGGL((k_witness_wide<2>), dim3(batches), dim3(128), 0, st, P, l0, l1, d_inputs, d_values, d_flags);
+        else if (waves == 4) hipLaunchKernelGGL((k_witness_wide<4>), dim3(batches), dim3(256), 0, st, P, l0, l1, d_inputs, d_values, d_flags);
+        else if (waves == 8) hipLaunchKernelGGL((k_witness_wide<8>), dim3(batches), dim3(512), 0, st, P, l0, l1, d_inputs, d_values, d_flags);
+        else hipLaunchKernelGGL((k_witness_wide<16>), dim3(batches), dim3(1024), 0, st, P, l0, l1, d_inputs, d_values, d_flags);
+      }
+      l0 = l1;
+    }
   }
   (void)hipStreamWaitEvent(st, ev_join, 0);
   hipLaunchKernelGGL(k_witness_out, dim3((P.n_vars + 255) / 256, batches), dim3(256), 0, st, P, d_values, d_z);

@@ -1869,6 +1869,8 @@ struct zkhip_gpu_witness {
   int device;
   zkhip_aggregator* agg;
   WitnessProg prog;
+  const WitnessTape* tape = nullptr;     // the circuit's recorded program (lives as long as agg): level boundaries for the wide kernels
+  int waves = 0;                         // zkhip_gpu_witness_set_waves: 0 = auto
   size_t in_words;
   size_t max_batches = 1;
   uint64_t* d_in = nullptr;
@@ -1877,6 +1879,8 @@ struct zkhip_gpu_witness {
   uint64_t* h_in = nullptr;       // pinned staging: inputs, then the flag and the primary inputs on the way back
   hipStream_t st = nullptr, st2 = nullptr;
   hipEvent_t ev = nullptr, ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;       // around the kernels of the last run (zkhip_gpu_witness_last_ms)
+  bool timed = false;
 };
 
 int zkhip_gpu_witness_new(zkhip_aggregator* a, zkhip_gpu_witness** out) { return zkhip_gpu_witness_new_batched(a, 1, out); }
@@ -1889,7 +1893,18 @@ int zkhip_gpu_witness_new_batched(zkhip_aggregator* a, size_t max_batches, zkhip
   const WitnessTape* tape = nullptr;
   int rc = witness_prog(a, &w->prog, &tape, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) { delete w; return rc; }
+  w->tape = tape;
   w->in_words = (size_t)w->prog.n_inputs * 6;
+  {
+    // n_pos x 64 bytes of values per witness (352 MB at 32 proofs with one input each): say so when they do not fit
+    const size_t need = max_batches * (size_t)w->prog.n_pos * witness_value_bytes;
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && need > mem_free) {
+      snprintf(t_err, sizeof t_err, "zkhip_gpu_witness_new: the work space of %zu witnesses takes %zu bytes, %zu are free on the device", max_batches, need, mem_free);
+      delete w;
+      return ZKHIP_ERR_HIP;
+    }
+  }
   hipError_t e = hipMalloc(&w->d_in, max_batches * w->in_words * 8);
   if (e == hipSuccess) e = hipMalloc(&w->d_vals, max_batches * (size_t)w->prog.n_pos * witness_value_bytes);
   if (e == hipSuccess) e = hipMalloc(&w->d_flag, max_batches * 4 + 64);
@@ -1903,12 +1918,44 @@ int zkhip_gpu_witness_new_batched(zkhip_aggregator* a, size_t max_batches, zkhip
   if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev, hipEventBlockingSync | hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&w->ev_join, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreate(&w->ev_t0);
+  if (e == hipSuccess) e = hipEventCreate(&w->ev_t1);
   if (e != hipSuccess) {
-    snprintf(t_err, sizeof t_err, "zkhip_gpu_witness_new: %s", hipGetErrorString(e));
+    snprintf(t_err, sizeof t_err, "zkhip_gpu_witness_new: %s (work space of %zu witnesses: %zu bytes of values)", hipGetErrorString(e), max_batches,
+             max_batches * (size_t)w->prog.n_pos * witness_value_bytes);
     zkhip_gpu_witness_free(w);
     return ZKHIP_ERR_HIP;
   }
   *out = w;
+  return ZKHIP_OK;
+}
+
+int zkhip_gpu_witness_set_waves(zkhip_gpu_witness* w, int waves) {
+  if (!w || !witness_waves_ok(waves)) return fail(ZKHIP_ERR_ARG, "waves per witness: 0 (auto), 1, 2, 4, 8 or 16");
+  w->waves = waves;
+  return ZKHIP_OK;
+}
+
+int zkhip_gpu_witness_last_ms(zkhip_gpu_witness* w, double* ms) {
+  if (!w || !ms) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (!w->timed) return fail(ZKHIP_ERR_STATE, "no run yet");
+  BIND(w);
+  float t = 0.f;
+  API_HIP(hipEventElapsedTime(&t, w->ev_t0, w->ev_t1));
+  *ms = (double)t;
+  return ZKHIP_OK;
+}
+
+// Host only: no device is touched
+int zkhip_gpu_witness_plan(zkhip_aggregator* a, int waves, size_t out[4]) {
+  if (!a || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (!witness_waves_ok(waves)) return fail(ZKHIP_ERR_ARG, "waves per witness: 0 (auto), 1, 2, 4, 8 or 16");
+  const WitnessTape* T = nullptr;
+  int rc = witness_tape_of(a, &T, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  const WitnessPlan pl = witness_plan(T->level_start.data(), T->level_start.size() - 1, T->code.size(), (uint32_t)waves);
+  out[0] = pl.chunks; out[1] = pl.levels; out[2] = pl.steps; out[3] = pl.value_bytes;
+  if (waves == 0) out[2] = pl.waves;      // (see zkhip.h: for auto the width, not its steps)
   return ZKHIP_OK;
 }
 
@@ -1924,6 +1971,8 @@ void zkhip_gpu_witness_free(zkhip_gpu_witness* w) {
   if (w->ev) (void)hipEventDestroy(w->ev);
   if (w->ev_fork) (void)hipEventDestroy(w->ev_fork);
   if (w->ev_join) (void)hipEventDestroy(w->ev_join);
+  if (w->ev_t0) (void)hipEventDestroy(w->ev_t0);
+  if (w->ev_t1) (void)hipEventDestroy(w->ev_t1);
   delete w;
 }
 
@@ -1932,7 +1981,8 @@ void zkhip_gpu_witness_free(zkhip_gpu_witness* w) {
 // (that batch's assignment is unusable: use the host generator).
 static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
                                 const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate,
-                                uint32_t wpg, uint32_t seg /* witness_launch's knobs: the product passes witness_env_wpg() / _segment() */) {
+                                uint32_t wpg, uint32_t seg /* witness_launch's knobs: the product passes witness_env_wpg() / _segment() */,
+                                int waves /* -1: the handle's (zkhip_gpu_witness_set_waves) */) {
   if (!w || (!app && !nested_vk) || !nested_proofs || !nested_inputs || !d_z_out || !degenerate) return fail(ZKHIP_ERR_ARG, "null pointer");
   if (n < 1 || n > w->max_batches) return fail(ZKHIP_ERR_ARG, "more batches than the work space holds");
   BIND(w);
@@ -1940,6 +1990,8 @@ static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app,
   const size_t vk_w = 60 + 12 * (a->inputs_per_proof + 1), pr_w = 48 * a->num_proofs, in_w = 6 * a->inputs_per_proof * a->num_proofs;
   if (vk_w + pr_w + in_w != w->in_words) return fail(ZKHIP_ERR_STATE, "witness program does not match the circuit");
   WitnessProg prog = w->prog;
+  const WitnessTape* tape = w->tape;
+  if (waves < 0) waves = w->waves;
   if (app) {
     // the application's own program (its key folded in: no key-hash chain, a tenth fewer multiplications, zeros at the constant
     // positions of the assignment), uploaded on first use
@@ -1953,6 +2005,7 @@ static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app,
     if (app->prog.prog.n_pos > w->prog.n_pos || app->prog.prog.n_inputs != w->prog.n_inputs)
       return fail(ZKHIP_ERR_STATE, "the application's program does not fit the generator's work space");
     prog = app->prog.prog;
+    tape = &app->tape;                      // (auto decides on the program that runs)
   }
   for (size_t i = 0; i < n; i++) {
     uint64_t* h = w->h_in + i * w->in_words;
@@ -1962,7 +2015,11 @@ static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app,
   uint64_t* h_prim = h_flags + w->max_batches;
   API_HIP(hipMemcpyAsync(w->d_in, w->h_in, n * w->in_words * 8, hipMemcpyHostToDevice, w->st));
   API_HIP(hipMemsetAsync(w->d_flag, 0, n * 4, w->st));
-  witness_launch(prog, w->d_in, w->d_vals, (uint64_t*)d_z_out, w->d_flag, (uint32_t)n, wpg, seg, w->st, w->st2, w->ev_fork, w->ev_join);
+  API_HIP(hipEventRecord(w->ev_t0, w->st));
+  witness_launch(prog, tape->level_start.data(), w->d_in, w->d_vals, (uint64_t*)d_z_out, w->d_flag, (uint32_t)n, wpg, seg, (uint32_t)waves, w->st, w->st2, w->ev_fork,
+                 w->ev_join);
+  API_HIP(hipEventRecord(w->ev_t1, w->st));
+  w->timed = true;
   API_HIP(hipGetLastError());
   API_HIP(hipMemcpyAsync(h_flags, w->d_flag, n * 4, hipMemcpyDeviceToHost, w->st));
   for (size_t i = 0; i < n; i++)
@@ -1976,24 +2033,30 @@ static int gpu_witness_run_impl(zkhip_gpu_witness* w, zkhip_aggregator_app* app,
 
 int zkhip_gpu_witness_run_batched(zkhip_gpu_witness* w, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
                                   const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate) {
-  return gpu_witness_run_impl(w, nullptr, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witness_env_wpg(), witness_env_segment());
+  return gpu_witness_run_impl(w, nullptr, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witness_env_wpg(), witness_env_segment(), -1);
 }
 // the same for batches of ONE registered application: MASKED assignments (zeros at the application's constant positions), ready for
 // zkhip_prover_prove_app_dev
 int zkhip_gpu_witness_run_batched_app(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_proofs,
                                       const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate) {
   if (!app) return fail(ZKHIP_ERR_ARG, "null pointer");
-  return gpu_witness_run_impl(w, app, n, nullptr, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witness_env_wpg(), witness_env_segment());
+  return gpu_witness_run_impl(w, app, n, nullptr, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witness_env_wpg(), witness_env_segment(), -1);
 }
-// Test hook: either of the two above with witness_launch's knobs given by the caller (0 = the process-wide default)
-int zkhip_internal_gpu_witness_run(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
-                                   const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup,
-                                   unsigned segment_chunks) {
+// Test hook: either of the two above with witness_launch's knobs given by the caller (0 = the process-wide default; waves: 0 = auto)
+int zkhip_internal_gpu_witness_run_wide(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
+                                        const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup,
+                                        unsigned segment_chunks, int waves) {
+  if (!witness_waves_ok(waves)) return fail(ZKHIP_ERR_ARG, "waves per witness: 0 (auto), 1, 2, 4, 8 or 16");
   if (witnesses_per_workgroup != 0 && witnesses_per_workgroup != 1 && witnesses_per_workgroup != 2 && witnesses_per_workgroup != 4)
     return fail(ZKHIP_ERR_ARG, "witnesses per workgroup: 0 (default), 1, 2 or 4");
   if (segment_chunks > (1u << 20)) return fail(ZKHIP_ERR_ARG, "segment: at most 2^20 chunks");
   return gpu_witness_run_impl(w, app, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate,
-                              witnesses_per_workgroup ? (uint32_t)witnesses_per_workgroup : witness_env_wpg(), segment_chunks ? segment_chunks : witness_env_segment());
+                              witnesses_per_workgroup ? (uint32_t)witnesses_per_workgroup : witness_env_wpg(), segment_chunks ? segment_chunks : witness_env_segment(), waves);
+}
+int zkhip_internal_gpu_witness_run(zkhip_gpu_witness* w, zkhip_aggregator_app* app, size_t n, const uint64_t* const* nested_vk, const uint64_t* const* nested_proofs,
+                                   const uint64_t* const* nested_inputs, void* d_z_out, uint64_t* primary_inputs, int* degenerate, int witnesses_per_workgroup,
+                                   unsigned segment_chunks) {
+  return zkhip_internal_gpu_witness_run_wide(w, app, n, nested_vk, nested_proofs, nested_inputs, d_z_out, primary_inputs, degenerate, witnesses_per_workgroup, segment_chunks, 1);
 }
 
 int zkhip_gpu_witness_run(zkhip_gpu_witness* w, const uint64_t* nested_vk, const uint64_t* nested_proofs, const uint64_t* nested_inputs,
@@ -2082,7 +2145,13 @@ static const char* witness_program_check(const zkhip_witness_program* p) {
 
 int zkhip_internal_witness_run_program(const zkhip_witness_program* p, const uint64_t* inputs, size_t batches, int witnesses_per_workgroup, unsigned segment_chunks,
                                        uint64_t* z_out, uint32_t* flags_out) {
+  return zkhip_internal_witness_run_program_wide(p, inputs, batches, witnesses_per_workgroup, segment_chunks, 1, z_out, flags_out);
+}
+
+int zkhip_internal_witness_run_program_wide(const zkhip_witness_program* p, const uint64_t* inputs, size_t batches, int witnesses_per_workgroup, unsigned segment_chunks,
+                                            int waves, uint64_t* z_out, uint32_t* flags_out) {
   if (const char* why = witness_program_check(p)) return fail(ZKHIP_ERR_ARG, why);
+  if (!witness_waves_ok(waves)) return fail(ZKHIP_ERR_ARG, "waves per witness: 0 (auto), 1, 2, 4, 8 or 16");
   if (witnesses_per_workgroup != 1 && witnesses_per_workgroup != 2 && witnesses_per_workgroup != 4) return fail(ZKHIP_ERR_ARG, "witnesses per workgroup: 1, 2 or 4");
   if (segment_chunks < 1 || segment_chunks > (1u << 20)) return fail(ZKHIP_ERR_ARG, "segment: 1 .. 2^20 chunks");
   if (batches > 256) return fail(ZKHIP_ERR_ARG, "at most 256 batches");
@@ -2123,8 +2192,8 @@ int zkhip_internal_witness_run_program(const zkhip_witness_program* p, const uin
   API_HIP(hipEventCreateWithFlags(&d.ev_join, hipEventDisableTiming));
   if (in_bytes) API_HIP(hipMemcpyAsync(d.in, inputs, in_bytes, hipMemcpyHostToDevice, d.st));
   API_HIP(hipMemsetAsync(d.flags, 0, batches * 4, d.st));
-  witness_launch(d.pd.prog, (const uint64_t*)d.in, (uint32_t*)d.vals, (uint64_t*)d.z, (uint32_t*)d.flags, (uint32_t)batches, (uint32_t)witnesses_per_workgroup,
-                 segment_chunks, d.st, d.st2, d.ev_fork, d.ev_join);
+  witness_launch(d.pd.prog, T.level_start.data(), (const uint64_t*)d.in, (uint32_t*)d.vals, (uint64_t*)d.z, (uint32_t*)d.flags, (uint32_t)batches,
+                 (uint32_t)witnesses_per_workgroup, segment_chunks, (uint32_t)waves, d.st, d.st2, d.ev_fork, d.ev_join);
   API_HIP(hipGetLastError());
   if (z_bytes) API_HIP(hipMemcpyAsync(z_out, d.z, z_bytes, hipMemcpyDeviceToHost, d.st));
   API_HIP(hipMemcpyAsync(flags_out, d.flags, batches * 4, hipMemcpyDeviceToHost, d.st));
@@ -2145,6 +2214,15 @@ int zkhip_internal_witness_tape(zkhip_aggregator* a, zkhip_witness_program* out)
   out->out_ref = T->out_ref.data(); out->n_vars = T->n_vars;
   out->consts = T->consts.data(); out->n_consts = T->consts.size() / 6;
   out->n_inputs = T->n_inputs;
+  return ZKHIP_OK;
+}
+
+int zkhip_device_memory(size_t* free_bytes, size_t* total_bytes) {
+  BIND_CUR();
+  size_t f = 0, t = 0;
+  API_HIP(hipMemGetInfo(&f, &t));
+  if (free_bytes) *free_bytes = f;
+  if (total_bytes) *total_bytes = t;
   return ZKHIP_OK;
 }
 

@@ -31,7 +31,7 @@ EXPORTS = [
     "zkhip_groth16_setup", "zkhip_groth16_setup_slice", "zkhip_keypair_crs_desc", "zkhip_keypair_vk", "zkhip_keypair_free", "zkhip_keypair_write", "zkhip_keypair_read",
     "zkhip_jac_to_affine", "zkhip_jac_add", "zkhip_to_canonical",
     "zkhip_last_accumulate_interval", "zkhip_crs_upload_ex", "zkhip_crs_upload_slice_ex", "zkhip_bases_precompute_ex", "zkhip_crs_table_kind", "zkhip_crs_finite_terms",
-    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_witness_run_program", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
+    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_pipeline_witness_sizing", "zkhip_internal_witness_run_program", "zkhip_internal_witness_run_program_wide", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_internal_gpu_witness_run_wide", "zkhip_gpu_witness_set_waves", "zkhip_gpu_witness_plan", "zkhip_gpu_witness_last_ms", "zkhip_device_memory", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
     "zkhip_msm_stream_new", "zkhip_msm_stream_submit", "zkhip_msm_stream_submit_host", "zkhip_msm_stream_collect", "zkhip_msm_stream_last_accumulate_ms",
     "zkhip_msm_stream_last_accumulate_interval", "zkhip_msm_stream_free", "zkhip_prover_new_slice", "zkhip_prover_prove_partial",
     "zkhip_dispatcher_new", "zkhip_dispatcher_size", "zkhip_dispatcher_submit", "zkhip_dispatcher_wait", "zkhip_dispatcher_stats", "zkhip_dispatcher_free",
@@ -729,12 +729,14 @@ class AggregatorCircuit:
         _check(load().zkhip_aggregator_witness_gpu(self.handle, _p(vk), _p(pr), _p(inp), _p(z)))
         return z
 
-    def witness_gpu_batched(self, batches, wpg=None, segment=None, app=None):
+    def witness_gpu_batched(self, batches, wpg=None, segment=None, app=None, waves=None):
         """batches: list of (nested_vk, nested_proofs, nested_inputs) -> (assignments u64 [n, n_vars, 6], degenerate bool [n], primary
         inputs) from ONE launch sequence of the circuit's generic program (what zkhip_gpu_witness_run_batched runs), or of `app`'s own
         program (zkhip_gpu_witness_run_batched_app: nested_vk is ignored and the assignments are masked), through the test hook
         zkhip_internal_gpu_witness_run.  wpg (witnesses per workgroup: 1, 2, 4) and segment (chunks per
-        launch) reach witness_launch as given; None = the process-wide default.  A degenerate batch's assignment is unusable."""
+        launch) reach witness_launch as given; None = the process-wide default.  waves: waves per witness (1: k_witness; 2, 4, 8, 16:
+        k_witness_wide; 0: auto); None = 1, the narrow kernel, through the hook without the argument.  A degenerate batch's
+        assignment is unusable."""
         lib = load()
         n, m, l = len(batches), self.num_variables, self.num_primary_inputs()
         c = lambda a: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
@@ -750,10 +752,15 @@ class AggregatorCircuit:
             arr = lambda xs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in xs])
             prim = np.zeros((n, l, 6), dtype=np.uint64)
             deg = (ctypes.c_int * n)()
-            lib.zkhip_internal_gpu_witness_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                           c_u64p_t, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint]
-            _check(lib.zkhip_internal_gpu_witness_run(gw, app.handle if app is not None else None, n, None if app is not None else arr(vks), arr(prs), arr(ins), dz,
-                                                      _p(prim), deg, int(wpg or 0), int(segment or 0)))
+            args = [gw, app.handle if app is not None else None, n, None if app is not None else arr(vks), arr(prs), arr(ins), dz, _p(prim), deg, int(wpg or 0), int(segment or 0)]
+            types = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                     c_u64p_t, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_uint]
+            if waves is None:
+                lib.zkhip_internal_gpu_witness_run.argtypes = types
+                _check(lib.zkhip_internal_gpu_witness_run(*args))
+            else:
+                lib.zkhip_internal_gpu_witness_run_wide.argtypes = types + [ctypes.c_int]
+                _check(lib.zkhip_internal_gpu_witness_run_wide(*args, int(waves)))
             z = np.zeros((n, m, 6), dtype=np.uint64)
             lib.zkhip_device_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
             _check(lib.zkhip_device_copy_out(z.ctypes.data, dz, n * m * 48))
@@ -773,6 +780,18 @@ class AggregatorCircuit:
                     level_start=cp(wp.level_start, wp.n_levels + 1, np.uint32), chain_start=int(wp.chain_start), out_ref=cp(wp.out_ref, wp.n_vars, np.int32),
                     consts=cp(wp.consts, wp.n_consts * 6, np.uint64).reshape(-1, 6), n_inputs=int(wp.n_inputs))
 
+    def gpu_witness_plan(self, waves=0):
+        """Host only (zkhip_gpu_witness_plan): what the circuit's recorded program asks of the device with `waves` waves per witness
+        (0 = the width auto picks): dict of chunks, levels, waves, steps (sum over levels of ceil(chunks / waves)), value_bytes."""
+        lib = load()
+        lib.zkhip_gpu_witness_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+        out = (ctypes.c_size_t * 4)()
+        _check(lib.zkhip_gpu_witness_plan(self.handle, int(waves), out))
+        if int(waves) == 0:
+            waves = int(out[2])
+            _check(lib.zkhip_gpu_witness_plan(self.handle, waves, out))
+        return dict(chunks=int(out[0]), levels=int(out[1]), waves=int(waves), steps=int(out[2]), value_bytes=int(out[3]))
+
     def gpu_witness_stats(self):
         out = (ctypes.c_size_t * 6)()
         _check(load().zkhip_gpu_witness_stats(self.handle, out))
@@ -788,6 +807,72 @@ class AggregatorCircuit:
     def free(self):
         if self.handle:
             load().zkhip_aggregator_free(self.handle)
+            self.handle = None
+
+
+class GpuWitness:
+    """zkhip_gpu_witness: work space for up to max_batches witnesses in flight and the device buffer their assignments are left in.
+    waves: waves per witness of the levelled program (zkhip_gpu_witness_set_waves: 1, 2, 4, 8, 16; 0 or None = auto)."""
+
+    def __init__(self, agg, max_batches=1, waves=None):
+        lib = load()
+        self._agg, self.max_batches, self.handle, self.d_z = agg, int(max_batches), None, None
+        gw = ctypes.c_void_p()
+        lib.zkhip_gpu_witness_new_batched.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        _check(lib.zkhip_gpu_witness_new_batched(agg.handle, self.max_batches, ctypes.byref(gw)))
+        self.handle = gw
+        try:
+            self.set_waves(waves or 0)
+            dz = ctypes.c_void_p()
+            _check(lib.zkhip_device_alloc(self.max_batches * agg.num_variables * 48, ctypes.byref(dz)))
+            self.d_z = dz
+        except Exception:
+            self.free()
+            raise
+
+    def set_waves(self, waves):
+        lib = load()
+        lib.zkhip_gpu_witness_set_waves.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _check(lib.zkhip_gpu_witness_set_waves(self.handle, int(waves)))
+
+    def run(self, batches):
+        """batches: list of (nested_vk, nested_proofs, nested_inputs) -> (device pointers of the assignments (integers, valid until the
+        next run), degenerate bool [n], primary inputs u64 [n, n_primary, 6]): zkhip_gpu_witness_run_batched"""
+        lib = load()
+        n, m, l = len(batches), self._agg.num_variables, self._agg.num_primary_inputs()
+        c = lambda a: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        vks, prs, ins = [c(b[0]) for b in batches], [c(b[1]) for b in batches], [c(b[2]) for b in batches]
+        arr = lambda xs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in xs])
+        prim = np.zeros((n, l, 6), dtype=np.uint64)
+        deg = (ctypes.c_int * n)()
+        lib.zkhip_gpu_witness_run_batched.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_u64p_t,
+                                                      ctypes.POINTER(ctypes.c_int)]
+        _check(lib.zkhip_gpu_witness_run_batched(self.handle, n, arr(vks), arr(prs), arr(ins), self.d_z, _p(prim), deg))
+        return [int(self.d_z.value) + i * m * 48 for i in range(n)], np.array([bool(deg[i]) for i in range(n)]), prim
+
+    def last_ms(self):
+        """milliseconds the kernels of the last run took on the device (zkhip_gpu_witness_last_ms)"""
+        lib = load()
+        lib.zkhip_gpu_witness_last_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        ms = ctypes.c_double(0)
+        _check(lib.zkhip_gpu_witness_last_ms(self.handle, ctypes.byref(ms)))
+        return float(ms.value)
+
+    def copy_out(self, i):
+        m = self._agg.num_variables
+        z = np.zeros((m, 6), dtype=np.uint64)
+        lib = load()
+        lib.zkhip_device_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+        _check(lib.zkhip_device_copy_out(z.ctypes.data, ctypes.c_void_p(int(self.d_z.value) + i * m * 48), m * 48))
+        return z
+
+    def free(self):
+        lib = load()
+        if self.d_z:
+            lib.zkhip_device_free(self.d_z)
+            self.d_z = None
+        if self.handle:
+            lib.zkhip_gpu_witness_free(self.handle)
             self.handle = None
 
 
@@ -892,6 +977,17 @@ class Prover:
         z, r, s = c(z), c(r), c(s)
         out = np.zeros(72, dtype=np.uint64)
         _check(load().zkhip_prover_prove(self.handle, _p(z), _p(r), _p(s), _p(out)))
+        return out
+
+    def prove_dev(self, d_z, r, s):
+        """zkhip_prover_prove_dev: the assignment already in DEVICE memory (an integer pointer: n_vars x 6 limbs, what GpuWitness.run
+        leaves there)."""
+        c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        r, s = c(r), c(s)
+        out = np.zeros(72, dtype=np.uint64)
+        lib = load()
+        lib.zkhip_prover_prove_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, c_u64p_t, c_u64p_t, c_u64p_t]
+        _check(lib.zkhip_prover_prove_dev(self.handle, ctypes.c_void_p(int(d_z)), _p(r), _p(s), _p(out)))
         return out
 
     def prove_app(self, app, z_masked, r, s):
@@ -1268,12 +1364,13 @@ def field_selftest(field, limbs_in):
     return out
 
 
-def witness_run_program(prog, inputs, wpg=4, segment=2048):
+def witness_run_program(prog, inputs, wpg=4, segment=2048, waves=1):
     """Test hook: a caller's program through the GPU witness generator's own upload, launch and kernels
     (zkhip_internal_witness_run_program).  prog: dict with code u8 [n], a / b i32 [n], level_start u32 [levels + 1], chain_start,
     out_ref i32 [n_vars], consts u64 [c, 6] (ABI form), n_inputs; inputs: u64 [batches, n_inputs, 6] (ABI form).  The library
     validates the program first and raises ZkhipError (code -1) for one that breaks a structural rule; zero batches validates only
-    and needs no device.  Returns (assignments u64 [batches, n_vars, 6], flags u32 [batches])."""
+    and needs no device.  waves: waves per witness (1: k_witness, through the hook without the argument; 2, 4, 8, 16: k_witness_wide,
+    whole levels per launch; 0: auto).  Returns (assignments u64 [batches, n_vars, 6], flags u32 [batches])."""
     arrs = dict(code=np.ascontiguousarray(prog["code"], dtype=np.uint8), a=np.ascontiguousarray(prog["a"], dtype=np.int32), b=np.ascontiguousarray(prog["b"], dtype=np.int32),
                 level_start=np.ascontiguousarray(prog["level_start"], dtype=np.uint32), out_ref=np.ascontiguousarray(prog["out_ref"], dtype=np.int32),
                 consts=np.ascontiguousarray(prog["consts"], dtype=np.uint64).reshape(-1, 6))
@@ -1287,9 +1384,15 @@ def witness_run_program(prog, inputs, wpg=4, segment=2048):
     z = np.zeros((batches, arrs["out_ref"].size, 6), dtype=np.uint64)
     flags = np.zeros(max(batches, 1), dtype=np.uint32)
     lib = load()
-    lib.zkhip_internal_witness_run_program.argtypes = [ctypes.POINTER(WitnessProgram), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
-    _check(lib.zkhip_internal_witness_run_program(ctypes.byref(wp), x.ctypes.data if x.size else None, batches, int(wpg), int(segment), z.ctypes.data if z.size else None,
-                                                  flags.ctypes.data))
+    if waves == 1:
+        lib.zkhip_internal_witness_run_program.argtypes = [ctypes.POINTER(WitnessProgram), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+        _check(lib.zkhip_internal_witness_run_program(ctypes.byref(wp), x.ctypes.data if x.size else None, batches, int(wpg), int(segment), z.ctypes.data if z.size else None,
+                                                      flags.ctypes.data))
+    else:
+        lib.zkhip_internal_witness_run_program_wide.argtypes = [ctypes.POINTER(WitnessProgram), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
+                                                                ctypes.c_void_p, ctypes.c_void_p]
+        _check(lib.zkhip_internal_witness_run_program_wide(ctypes.byref(wp), x.ctypes.data if x.size else None, batches, int(wpg), int(segment), int(waves),
+                                                           z.ctypes.data if z.size else None, flags.ctypes.data))
     return z, flags[:batches]
 
 
