@@ -353,3 +353,40 @@ def test_the_library_measures_its_multiplier_peak_and_rebases_its_clock(zk):
     assert 0 <= t0 < t1 < 5000.0                     # milliseconds since the reset, not since the library first planned an MSM
     assert abs((t1 - t0) - stream.last_accumulate_ms()) < 0.05
     stream.free(); dev.free(); b.free()
+
+
+def test_one_context_through_every_plan_outcome(zk, oracle_lib):
+    """A context is planned, reused, re-planned (more terms, another window, plain <-> table) and refused while pending - on the
+    library's slot 0 (Bases.msm) and on the contexts of a handle-owned stream.  The automatic window changes at 1,024 terms."""
+    O = oracle_lib
+    g = aff_limbs(R.G1_GEN)
+    bases = zk.fixed_base_mul(g, random_fr_canonical(901, 1500), montgomery=False)
+    tbases = zk.fixed_base_mul(g, random_fr_canonical(902, 300), montgomery=False)
+    plain = zk.Bases.upload(bases)
+    table = zk.Bases.upload(tbases).precompute()
+    # (set, terms, offset): first plan; same window, larger max_n; window 8 -> 10; plain -> merged; merged -> plain; reuse
+    steps = [(plain, 300, 0), (plain, 700, 0), (plain, 1500, 0), (table, 300, 0), (plain, 200, 100), (plain, 150, 0)]
+    for i, (b, n, off) in enumerate(steps):
+        scal = random_fr_canonical(910 + i, n)
+        pts = (bases if b is plain else tbases)[off:off + n]
+        assert (zk.jac_to_affine(b.msm(scal, offset=off)) == O.jac_to_affine(O.msm(pts, scal))).all(), i
+    # depth 2: slot 0 serves 300 (first plan), 200 (reuse), 700 (larger max_n); slot 1 serves 1,500 (first plan), 150 (window 10 -> 8)
+    sizes = [300, 1500, 200, 700, 150]
+    scal = [random_fr_canonical(920 + i, n) for i, n in enumerate(sizes)]
+    dev = [zk.DeviceBuffer(s) for s in scal]
+    stream = zk.MsmStream(plain, depth=2)
+    got = [None] * 5
+    t0, t1 = stream.submit(dev[0].ptr, sizes[0]), stream.submit(dev[1].ptr, sizes[1])
+    got[0] = stream.collect(t0)
+    t2 = stream.submit(dev[2].ptr, sizes[2])
+    got[1], got[2] = stream.collect(t1), stream.collect(t2)
+    t3, t4 = stream.submit(dev[3].ptr, sizes[3]), stream.submit(dev[4].ptr, sizes[4])
+    with pytest.raises(zk.ZkhipError) as refused:
+        stream.submit(dev[0].ptr, sizes[0])
+    assert refused.value.code == -4
+    got[3], got[4] = stream.collect(t3), stream.collect(t4)
+    for i, n in enumerate(sizes):
+        assert (zk.jac_to_affine(got[i]) == O.jac_to_affine(O.msm(bases[:n], scal[i]))).all(), i
+    stream.free(); plain.free(); table.free()
+    for d in dev:
+        d.free()

@@ -25,9 +25,12 @@ struct MsmJob {
   const EdwPacked* edw = nullptr;  // the same table in precomputed Edwards form (msm_table_edw), or null: a single MSM over a one-level-
                                    // per-window table then accumulates on G1's 2-isogenous Edwards curve (ec_edw.cuh)
 };
+// the terms of a job that can produce an entry: a base at infinity never does (plans are sized by this, launches counted by it)
+static inline size_t msm_job_terms(const MsmJob& j) { return (j.n_finite && j.n_finite < j.n) ? j.n_finite : j.n; }
 
 #define ZK_PRIO_BOARD_WORDS (8 * 8 * 2 * 16 * 4 * 16)
-struct MsmCtx {
+struct MsmCtx {      // all zeros: no plan
+  bool planned;        // msm_plan_init succeeded and msm_plan_free has not run since: every field below is valid
   int c, W, L, logL;   // W: bucket windows (each owns 2^(c-1) buckets)
   int Wd;              // digits per scalar: W without a table; with a precomputed table all Wd digit positions share ONE bucket window
   int merged;          // 1: bases are a table  table[w * stride + i] = 2^(off_w) P_i  (msm_table_build), one digit per window;
@@ -108,8 +111,6 @@ int msm_last_entries(MsmCtx* ctx, uint64_t* out);
 // one sort, one accumulation launch, one reduction chain with a bucket window per job.  out_jac: K x 36.
 int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs);
 int msm_finish_multi(MsmCtx* ctx, int K, uint64_t* out_jac);
-int msm_run(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
-            int scalars_montgomery, size_t table_stride, uint64_t out_jac[36], const EdwPacked* edw = nullptr);
 // levels of a window table for window size c
 static inline int msm_table_levels(int c, int naf = 0) { return naf ? 378 : (378 + c - 1) / c; }
 // d_table: levels x n points, level 0 (= the n base points) already in place; d_tinf: levels x n flags, level 0 in place.

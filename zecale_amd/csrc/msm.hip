@@ -1704,6 +1704,7 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   HIP_TRY(hipMalloc(&ctx->hilo, ((size_t)2 * ctx->W * ((size_t)1 << ((c - 1 + 1) / 2)) + 8) * 108 * 4));
   HIP_TRY(hipMalloc(&ctx->win_abi, (size_t)ctx->W * 48 * 8 * 2));       // (the second half: the plain totals of a NAF plan)
   HIP_TRY(hipHostMalloc(&ctx->win_host, (size_t)ctx->W * 48 * 8 * 2));
+  ctx->planned = true;
   return ZKHIP_OK;
 }
 
@@ -1736,14 +1737,6 @@ int msm_bases_convert(const uint64_t* d_bases_abi, size_t n, AffPacked* d_out, u
   return ZKHIP_OK;
 }
 
-// d_bases: packed device-form points; d_scalars: n x 6 u64 (device memory).  Result: Jacobian, ABI form (host).
-int msm_run(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
-            int scalars_montgomery, size_t table_stride, uint64_t out_jac[36], const EdwPacked* edw) {
-  int rc = msm_launch(ctx, d_bases, d_inf_flags, d_scalars, n, scalars_montgomery, table_stride, edw);
-  if (rc != ZKHIP_OK) return rc;
-  return msm_finish(ctx, out_jac);
-}
-
 // Enqueue one MSM on the context's streams and return without waiting (the prover keeps two contexts
 // in flight so that the latency-bound reduction of one MSM overlaps the accumulation of the next).
 int msm_launch(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags, const uint64_t* d_scalars, size_t n,
@@ -1758,7 +1751,7 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   size_t n_tot = 0, n_eff = 0;
   for (int k = 0; k < K; k++) {
     if (jobs[k].n > ctx->max_n) return ZKHIP_ERR_ARG;
-    n_eff += (jobs[k].n_finite && jobs[k].n_finite < jobs[k].n) ? jobs[k].n_finite : jobs[k].n;
+    n_eff += msm_job_terms(jobs[k]);
     if (n_eff > ctx->total_terms) return ZKHIP_ERR_ARG;          // (the entry list and the slices are sized for total_terms)
     if (merged && jobs[k].n && (jobs[k].table_stride < jobs[k].n || (size_t)(merged == 2 ? 378 : Wd) * jobs[k].table_stride >= ((size_t)1 << 31))) return ZKHIP_ERR_ARG;
     n_tot += jobs[k].n;

@@ -71,8 +71,7 @@ struct ProveState {
   // MSM contexts: [0, ZK_MSM_SLOTS) the slots of zkhip_msm_submit / collect (the first five also serve a proof whose five MSMs run as
   // separate launch sequences), [ZK_MSM_SLOTS] the context of a proof's five MSMs in ONE launch sequence, [ZK_CTX_Z] / [ZK_CTX_H] the
   // two sequences of a proof ALONE (round 6): the four MSMs over the assignment, and the H MSM behind the QAP map
-  MsmCtx ctx[ZK_CTX_TOTAL];
-  bool ready[ZK_CTX_TOTAL] = {};
+  MsmCtx ctx[ZK_CTX_TOTAL] = {};   // (all zeros: no plan yet - msm.h)
   hipStream_t st = nullptr;
   hipEvent_t ev_st = nullptr;      // blocking-sync event for waits on st (the waiting host thread sleeps)
   hipEvent_t ev_up = nullptr, ev_qap = nullptr;   // split proofs: the assignment is on the device / the QAP map has finished (stream-to-stream)
@@ -90,7 +89,7 @@ struct ProveState {
   hipStream_t pre[2] = {nullptr, nullptr};   // streams made ahead of the first proof (zkhip_prover_create_streams): the launch sequence's plan adopts them
   void release() {
     for (int k = 0; k < 2; k++) if (pre[k]) { (void)hipStreamDestroy(pre[k]); pre[k] = nullptr; }
-    for (int k = 0; k < ZK_CTX_TOTAL; k++) if (ready[k]) { msm_plan_free(&ctx[k]); ready[k] = false; }
+    for (int k = 0; k < ZK_CTX_TOTAL; k++) if (ctx[k].planned) msm_plan_free(&ctx[k]);
     if (st) { (void)hipStreamDestroy(st); st = nullptr; }
     if (ev_st) { (void)hipEventDestroy(ev_st); ev_st = nullptr; }
     if (ev_up) { (void)hipEventDestroy(ev_up); ev_up = nullptr; }
@@ -129,6 +128,8 @@ int fail(int code, const char* msg) {
   snprintf(t_err, sizeof t_err, "%s", msg);
   return code;
 }
+// a failed call of the MSM engine: the context holds its message
+int ctx_fail(int code, const MsmCtx* cx) { return fail(code, cx->errbuf); }
 int cur_dev() { return t_dev >= 0 ? t_dev : g.default_device; }
 // bind the calling thread to device d (it must have been initialised)
 int bind_dev(int d) {
@@ -174,29 +175,31 @@ int auto_table_window(size_t n) {
   return 21;
 }
 
-// table_c = 0: plain plan with the automatic window;  > 0: merged plan (bases are a window table built for table_c)
-// total: bound on the terms of all K jobs of a launch together (0: K * n)
-// would ensure_ctx keep this context as it is (same plan, nothing pending)?
-static bool ctx_reusable(const MsmCtx* cx, bool ready, size_t n, int table_c, int K, int naf, size_t total, int plain_c = 0) {
-  const int c = table_c ? table_c : (plain_c ? plain_c : auto_window(n)), merged = table_c ? (naf ? 2 : 1) : 0;
+// The plan of an MSM.  table_c = 0: plain plan with the automatic window;  > 0: merged plan (bases are a window table built for table_c)
+static int plan_window(size_t n, int table_c, int plain_c) { return table_c ? table_c : (plain_c ? plain_c : auto_window(n)); }
+static int plan_merged(int table_c, int naf) { return table_c ? (naf ? 2 : 1) : 0; }
+// would ensure_ctx keep this context as it is (same plan, nothing pending)?  total: bound on the terms of all K jobs together (0: K * n)
+static bool ctx_reusable(const MsmCtx* cx, size_t n, int table_c, int K, int naf, size_t total, int plain_c = 0) {
   if (total == 0 || total > (size_t)K * n) total = (size_t)K * n;
-  return ready && !cx->pending && cx->max_n >= n && cx->total_terms >= total && cx->c == c && cx->merged == merged && cx->K == K &&
-         cx->aff_forced == msm_forced_aff_levels();
+  return cx->planned && !cx->pending && cx->max_n >= n && cx->total_terms >= total && cx->c == plan_window(n, table_c, plain_c) &&
+         cx->merged == plan_merged(table_c, naf) && cx->K == K && cx->aff_forced == msm_forced_aff_levels();
 }
-int ensure_ctx(MsmCtx* cx, bool* ready, size_t n, int table_c, int K = 1, int naf = 0, size_t total = 0, int plain_c = 0, hipStream_t* adopt = nullptr) {
-  const int c = table_c ? table_c : (plain_c ? plain_c : auto_window(n)), merged = table_c ? (naf ? 2 : 1) : 0;
-  if (total == 0 || total > (size_t)K * n) total = (size_t)K * n;
-  if (*ready && cx->pending) return fail(ZKHIP_ERR_STATE, "an MSM submitted on this context has not been collected (zkhip_msm_collect)");
-  if (*ready && cx->max_n >= n && cx->total_terms >= total && cx->c == c && cx->merged == merged && cx->K == K && cx->aff_forced == msm_forced_aff_levels()) return ZKHIP_OK;
-  if (*ready) { msm_plan_free(cx); *ready = false; }
-  int rc = msm_plan_init(cx, n, c, merged, K, total, adopt);
-  if (rc != ZKHIP_OK) {
-    snprintf(t_err, sizeof t_err, "msm_plan_init: %s", cx->errbuf);
-    msm_plan_free(cx);          // whatever was allocated before the failure
-    return rc;
-  }
-  *ready = true;
-  return ZKHIP_OK;
+int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K = 1, int naf = 0, size_t total = 0, int plain_c = 0, hipStream_t* adopt = nullptr) {
+  if (cx->pending) return fail(ZKHIP_ERR_STATE, "an MSM submitted on this context has not been collected (zkhip_msm_collect)");
+  if (ctx_reusable(cx, n, table_c, K, naf, total, plain_c)) return ZKHIP_OK;
+  if (cx->planned) msm_plan_free(cx);
+  const int rc = msm_plan_init(cx, n, plan_window(n, table_c, plain_c), plan_merged(table_c, naf), K, total, adopt);
+  if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "msm_plan_init: %s", cx->errbuf); msm_plan_free(cx); }   // (frees what the failed plan had allocated: "no plan" again)
+  return rc;
+}
+// one MSM over `len` bases of b from `offset` on: slices sized by len (no finite-bases bound), the Edwards table from the same point
+MsmJob single_job(const zkhip_bases* b, size_t offset, const void* d_scalars, size_t len, int scalars_mode) {
+  return MsmJob{b->d_pts + offset, b->d_inf ? b->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len, scalars_mode, b->len, 0, msm_edw_at(b->d_edw, offset)};
+}
+// the last accumulation launch of ps ran on cx (zkhip_last_accumulate_ms / _interval / _entries read it back)
+void note_last_acc(ProveState& ps, MsmCtx* cx) {
+  ps.last_acc_ctx = cx; ps.last_accumulate_ms = cx->last_accumulate_ms;
+  ps.last_acc_interval[0] = cx->last_acc_begin_ms; ps.last_acc_interval[1] = cx->last_acc_end_ms;
 }
 }  // namespace
 
@@ -440,13 +443,14 @@ int zkhip_msm_dev(const zkhip_bases* bases, size_t offset, const void* d_scalars
   ProveState& ps = g.dev[bases->device].ps;
   std::lock_guard<std::mutex> lk(g.dev[bases->device].mu);
   if (offset > bases->len || len > bases->len - offset) return fail(ZKHIP_ERR_ARG, "offset + len exceeds the base set");
-  int rc = ensure_ctx(&ps.ctx[0], &ps.ready[0], len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
+  MsmCtx* cx = &ps.ctx[0];
+  int rc = ensure_ctx(cx, len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
   if (rc != ZKHIP_OK) return rc;
-  rc = msm_run(&ps.ctx[0], bases->d_pts + offset, bases->d_inf ? bases->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len,
-               scalars_montgomery, bases->len, out_jac, msm_edw_at(bases->d_edw, offset));
-  if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", ps.ctx[0].errbuf);
-  else { ps.last_acc_ctx = &ps.ctx[0]; ps.last_accumulate_ms = ps.ctx[0].last_accumulate_ms; ps.last_acc_interval[0] = ps.ctx[0].last_acc_begin_ms; ps.last_acc_interval[1] = ps.ctx[0].last_acc_end_ms; t_prove_dev = bases->device; }
-  return rc;
+  const MsmJob job = single_job(bases, offset, d_scalars, len, scalars_montgomery);
+  if ((rc = msm_launch_multi(cx, 1, &job)) == ZKHIP_OK) rc = msm_finish(cx, out_jac);
+  if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+  note_last_acc(ps, cx); t_prove_dev = bases->device;
+  return ZKHIP_OK;
 }
 
 // Asynchronous form: enqueue on one of the library's MSM contexts and return; collect later.  Two MSMs in flight overlap
@@ -459,8 +463,8 @@ int zkhip_msm_submit(const zkhip_bases* bases, size_t offset, const void* d_scal
   std::lock_guard<std::mutex> lk(g.dev[bases->device].mu);
   if (offset > bases->len || len > bases->len - offset) return fail(ZKHIP_ERR_ARG, "offset + len exceeds the base set");
   MsmCtx* cx = &ps.ctx[slot];
-  if (ps.ready[slot] && cx->pending) return fail(ZKHIP_ERR_STATE, "slot busy: collect its result first");
-  int rc = ensure_ctx(cx, &ps.ready[slot], len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
+  if (cx->pending) return fail(ZKHIP_ERR_STATE, "slot busy: collect its result first");
+  int rc = ensure_ctx(cx, len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
   if (rc != ZKHIP_OK) return rc;
   // a stream of MSMs, optionally GATED (ZKHIP_MSM_GATE=1): the accumulation of this one waits for the end of the accumulation
   // submitted before it on another slot, so that two accumulations never share the chip.  Measured (tools/gate_ab.sh, 2^20 terms,
@@ -468,14 +472,14 @@ int zkhip_msm_submit(const zkhip_bases* bases, size_t offset, const void* d_scal
   // head of the next - so the default is off; the gate gives event-timed kernel durations that are per-launch costs.
   static const bool gate = getenv("ZKHIP_MSM_GATE") ? atoi(getenv("ZKHIP_MSM_GATE")) != 0 : false;
   const int prev = ps.last_submit_slot;
-  cx->acc_gate = (gate && prev >= 0 && prev != slot && ps.ready[prev]) ? ps.ctx[prev].ev_acc1 : nullptr;
-  rc = msm_launch(cx, bases->d_pts + offset, bases->d_inf ? bases->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len,
-                  scalars_montgomery, bases->len, msm_edw_at(bases->d_edw, offset));
+  cx->acc_gate = (gate && prev >= 0 && prev != slot && ps.ctx[prev].planned) ? ps.ctx[prev].ev_acc1 : nullptr;
+  const MsmJob job = single_job(bases, offset, d_scalars, len, scalars_montgomery);
+  rc = msm_launch_multi(cx, 1, &job);
   cx->acc_gate = nullptr;                   // (the event belongs to another context: never kept beyond this launch)
-  if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", cx->errbuf);
-  else if (len) ps.last_submit_slot = slot;
-  if (rc == ZKHIP_OK) t_slot_dev[slot] = bases->device;      // zkhip_msm_collect(slot) has no handle: it collects where this thread submitted
-  return rc;
+  if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+  if (len) ps.last_submit_slot = slot;
+  t_slot_dev[slot] = bases->device;         // zkhip_msm_collect(slot) has no handle: it collects where this thread submitted
+  return ZKHIP_OK;
 }
 
 int zkhip_msm_collect(int slot, uint64_t out_jac[36]) {
@@ -485,11 +489,11 @@ int zkhip_msm_collect(int slot, uint64_t out_jac[36]) {
   ProveState& ps = g.dev[dev].ps;
   std::lock_guard<std::mutex> lk(g.dev[dev].mu);
   MsmCtx* cx = &ps.ctx[slot];
-  if (!ps.ready[slot] || !cx->pending) return fail(ZKHIP_ERR_STATE, "nothing submitted on this slot");
-  int rc = msm_finish(cx, out_jac);
-  if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", cx->errbuf);
-  else { ps.last_acc_ctx = cx; ps.last_accumulate_ms = cx->last_accumulate_ms; ps.last_acc_interval[0] = cx->last_acc_begin_ms; ps.last_acc_interval[1] = cx->last_acc_end_ms; t_prove_dev = dev; }
-  return rc;
+  if (!cx->pending) return fail(ZKHIP_ERR_STATE, "nothing submitted on this slot");
+  const int rc = msm_finish(cx, out_jac);
+  if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+  note_last_acc(ps, cx); t_prove_dev = dev;
+  return ZKHIP_OK;
 }
 
 int zkhip_msm(const zkhip_bases* bases, size_t offset, const uint64_t* scalars, size_t len, int scalars_montgomery,
@@ -818,17 +822,176 @@ static int prove_check(const zkhip_crs* crs, const R1csDev* rd, size_t a_lo, siz
   return ZKHIP_OK;
 }
 
+using clk = std::chrono::steady_clock;
+static double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
+
+// One MSM of a proof over the first len bases of a query vector.  The finite-bases bound counts only for a WHOLE vector.
+static MsmJob query_job(const zkhip_bases* b, const uint64_t* scalars, size_t len, int scalars_mode) {
+  return MsmJob{b->d_pts, b->d_inf, scalars, len, scalars_mode, b->len, len == b->len ? b->n_finite : 0};
+}
+// what a proof's strategies share: its state, its inputs, and the five MSMs in the order of `sums` - A, B-G2, B-G1, H, L
+struct ProofRun {
+  ProveState& ps;
+  R1csDev* rd;
+  const uint64_t *z_host, *dz, *d_z_app;   // z_host: null when the assignment is already on the device (dz)
+  int tc, naf;                             // the key's table window (0: plain) and kind
+  clk::time_point t0;                      // start of the phase being timed
+  uint64_t* sums;
+  MsmJob jobs[5];
+};
+static void proof_jobs(const zkhip_crs* crs, const R1csDev* rd, const uint64_t* dz, size_t a_lo, size_t h_lo, size_t l_lo, MsmJob jobs[5]) {
+  const uint64_t *za = dz + a_lo * 6, *zl = dz + (rd->n_primary + 1 + l_lo) * 6, *h = (const uint64_t*)rd->bufA + h_lo * 6;
+  jobs[0] = query_job(crs->A, za, crs->A->len, 1); jobs[1] = query_job(crs->B2, za, crs->A->len, 1); jobs[2] = query_job(crs->B1, za, crs->A->len, 1);
+  jobs[3] = query_job(crs->H, h, crs->H->len, 2); jobs[4] = query_job(crs->L, zl, crs->L->len, 1);    // (h: the QAP map's output, packed device form)
+}
+static size_t jobs_terms(const MsmJob* jobs, int K) {
+  size_t t = 0;
+  for (int k = 0; k < K; k++) t += msm_job_terms(jobs[k]);
+  return t ? t : 1;
+}
+// a strategy's answer when its plan does not fit the engine's 32-bit entry positions (ensure_ctx: ZKHIP_ERR_ARG) and nothing has been
+// enqueued: the next strategy decides.  Never leaves prove_partial.
+constexpr int ZK_PLAN_UNFIT = 1;
+
+// OPTION, off by default (ZKHIP_PROVE_SPLIT=1; =2: without the gate between the two accumulations) - a proof that is alone on the
+// chip as TWO launch sequences (round 6): four of the five MSMs - A, B-G2, B-G1, L - need only the assignment, so
+// their sort and accumulation start as soon as z is on the device, on their own plan, while the QAP map runs beside them on the
+// prover's stream; the H MSM follows on a second plan behind an event on h, and the bucket reduction of the first sequence runs
+// under its accumulation.  Same group elements, bit-identical proofs (the partitioned and serial tests pass with it on).
+// MEASURED AND NOT ADOPTED (profiles/r06_split_proof_ab.txt, one box, tools/partition_model.py): one 2^20 proof alone 50.0 ms as one
+// sequence, 52.0 split (49.8-50.5 without the gate); one rank of an eight-way 2^22 key 38.6 -> 39.8 ms; an eighth of a 2^20 key
+// 12.4 -> 13.5-14.8 ms.  The map is not idle time to hide: at 2^22 its seven FFTs and three SpMVs fill the chip (9.4 ms of
+// multiplier and HBM work) and share the accumulation's issue slots when run beside it - the two accumulation launches together
+// take 44 ms where the single one takes 37 - and every launch sequence brings its own one-fill tail, stitching and reduction chain.
+static int prove_split(ProofRun& p, bool gated) {
+  ProveState& ps = p.ps;
+  const MsmJob jz[4] = {p.jobs[0], p.jobs[1], p.jobs[2], p.jobs[4]}, &jh = p.jobs[3];
+  MsmCtx *cz = &ps.ctx[ZK_CTX_Z], *ch = &ps.ctx[ZK_CTX_H];
+  const size_t max_z = jz[0].n > jz[3].n ? jz[0].n : jz[3].n;
+  int rc = ensure_ctx(cz, max_z ? max_z : 1, p.tc, 4, p.naf, jobs_terms(jz, 4), 0, ps.pre);
+  if (rc == ZKHIP_OK) rc = ensure_ctx(ch, jh.n, p.tc, 1, p.naf, jobs_terms(&jh, 1));
+  if (rc != ZKHIP_OK) return rc == ZKHIP_ERR_ARG ? ZK_PLAN_UNFIT : rc;
+  if (!ps.ev_up) API_HIP(hipEventCreateWithFlags(&ps.ev_up, hipEventDisableTiming));
+  if (!ps.ev_qap) API_HIP(hipEventCreateWithFlags(&ps.ev_qap, hipEventDisableTiming));
+  if (p.z_host) API_HIP(hipMemcpyAsync(ps.dz, p.z_host, p.rd->n_vars * 48, hipMemcpyHostToDevice, ps.st));
+  API_HIP(hipEventRecord(ps.ev_up, ps.st));
+  API_HIP(hipStreamWaitEvent(cz->stream, ps.ev_up, 0));
+  ps.ms[0] = ms_since(p.t0);
+  const auto tl0 = p.t0 = clk::now();
+  if ((rc = msm_launch_multi(cz, 4, jz)) != ZKHIP_OK) return ctx_fail(rc, cz);
+  rc = qap_h_dev(p.rd, p.dz, ps.st, t_err, sizeof t_err, p.d_z_app);
+  if (rc == ZKHIP_OK) {
+    hipError_t e = hipEventRecord(ps.ev_qap, ps.st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ch->stream, ps.ev_qap, 0);
+    if (e != hipSuccess) { snprintf(t_err, sizeof t_err, "split proof: %s", hipGetErrorString(e)); rc = ZKHIP_ERR_HIP; }
+  }
+  if (rc == ZKHIP_OK) {
+    ch->acc_gate = gated ? cz->ev_acc1 : nullptr;        // H's accumulation starts when the first one has ended
+    if ((rc = msm_launch_multi(ch, 1, &jh)) != ZKHIP_OK) (void)ctx_fail(rc, ch);
+    ch->acc_gate = nullptr;
+  }
+  ps.ms[1] = ms_since(p.t0);                      // (enqueueing the QAP map and both sequences: the phases overlap on the device)
+  // whatever was enqueued is collected on every exit (a pending plan would refuse the next proof); the first error is reported
+  uint64_t sz[4 * 36];
+  const int rc_z = msm_finish_multi(cz, 4, sz);
+  const int rc_h = rc == ZKHIP_OK ? msm_finish_multi(ch, 1, p.sums + 108) : ZKHIP_OK;
+  if (rc == ZKHIP_OK && rc_z != ZKHIP_OK) rc = ctx_fail(rc_z, cz);
+  if (rc == ZKHIP_OK && rc_h != ZKHIP_OK) rc = ctx_fail(rc_h, ch);
+  if (rc != ZKHIP_OK) { (void)hipStreamSynchronize(ps.st); return rc; }
+  memcpy(p.sums, sz, 3 * 36 * 8); memcpy(p.sums + 144, sz + 108, 36 * 8);
+  for (int j = 0; j < 5; j++) ps.ms[2 + j] = ms_since(tl0);
+  note_last_acc(ps, cz);                          // (two accumulation launches: the sum of their times)
+  ps.last_accumulate_ms += ch->last_accumulate_ms; ps.last_acc_ctx2 = ch;
+  ps.split_last = true;
+  return ZKHIP_OK;
+}
+// the assignment to the device and the QAP map on stream qst; a chained proof does not wait for either
+static int prove_upload_and_map(ProofRun& p, hipStream_t qst, bool chain) {
+  ProveState& ps = p.ps;
+  auto host_waits = [&]() -> int {      // (the MSM contexts run on their own streams; a chained proof's MSMs follow on qst)
+    if (!chain) { API_HIP(hipEventRecord(ps.ev_st, qst)); API_HIP(zk_event_wait(ps.ev_st)); }
+    return ZKHIP_OK;
+  };
+  int rc = ZKHIP_OK;
+  if (p.z_host) {
+    API_HIP(hipMemcpyAsync(ps.dz, p.z_host, p.rd->n_vars * 48, hipMemcpyHostToDevice, qst));
+    if ((rc = host_waits()) != ZKHIP_OK) return rc;
+  }
+  ps.ms[0] = ms_since(p.t0);
+  p.t0 = clk::now();
+  // (an application's constants - d_z_app - are part of the assignment the QAP map sees; the MSMs over z run on the masked
+  //  vector: a zero scalar produces no bucket entry, the constants' share of A, B and L is the application's four cached points)
+  if ((rc = qap_h_dev(p.rd, p.dz, qst, t_err, sizeof t_err, p.d_z_app)) == ZKHIP_OK) rc = host_waits();
+  ps.ms[1] = ms_since(p.t0);
+  return rc;
+}
+// Table-backed key: the five MSMs share ONE launch sequence (one sort, one accumulation launch over all five entry lists, one
+// reduction chain with a bucket window per MSM) - a fifth of the launches, five times the lanes in each.
+static int prove_batched(ProofRun& p, size_t maxlen, bool chain) {
+  ProveState& ps = p.ps;
+  MsmCtx* cx = &ps.ctx[ZK_MSM_SLOTS];
+  const size_t total = jobs_terms(p.jobs, 5);
+  int rc = ensure_ctx(cx, maxlen, p.tc, 5, p.naf, total, 0, ps.pre);
+  if (rc == ZKHIP_ERR_ARG) {
+    // (a silent performance cliff) the plan's 32-bit entry positions / slice weights do not hold this key's terms at
+    // this window: said once per process, then one launch sequence per MSM
+    static std::atomic<bool> told{false};
+    if (!told.exchange(true))
+      fprintf(stderr, "zkhip: the five MSMs of this key do not fit ONE launch sequence (window %d, %zu terms: 32-bit slice weights); "
+                      "using one sequence per MSM - a larger table window (zkhip_key_opts.window) avoids this\n", p.tc, total);
+    return ZK_PLAN_UNFIT;
+  }
+  if (rc != ZKHIP_OK) return rc;
+  if (ps.quad_below) { cx->quad_below = ps.quad_below; cx->one_stream = 1; }
+  const auto tl0 = clk::now();
+  if ((rc = msm_launch_multi(cx, 5, p.jobs)) == ZKHIP_OK) rc = msm_finish_multi(cx, 5, p.sums);
+  if (rc != ZKHIP_OK) {
+    // (a chained proof's stream also carried the upload and the QAP map: their failure surfaces here)
+    snprintf(t_err, sizeof t_err, "%s%s", cx->errbuf, chain ? " [chained proof: this stream also carried the upload of the assignment and the QAP map]" : "");
+    return rc;
+  }
+  for (int j = 0; j < 5; j++) ps.ms[2 + j] = ms_since(tl0);
+  note_last_acc(ps, cx);
+  return ZKHIP_OK;
+}
+// One launch sequence per MSM, several in flight: while MSM j reduces its buckets (latency-bound, few lanes), MSM j+1 accumulates.
+// Large circuits keep two contexts (each holds ~1.3 GB of work space at 2^20); small ones (every phase is latency-bound and the
+// chip is mostly idle) run all five MSMs side by side.  These launches take only the geometry of a job: plans of K = 1 without a
+// bound on the terms, no finite-bases bound and no Edwards table (msm_launch's defaults).
+static int prove_separate(ProofRun& p, size_t maxlen) {
+  ProveState& ps = p.ps;
+  const int nctx = (maxlen <= ((size_t)1 << 18)) ? 5 : 2;
+  for (int k = 0, rc; k < nctx; k++) {
+    if ((rc = ensure_ctx(&ps.ctx[k], maxlen, p.tc, 1, p.naf)) != ZKHIP_OK) return rc;
+    if (ps.quad_below) { ps.ctx[k].quad_below = ps.quad_below; ps.ctx[k].one_stream = 1; }
+  }
+  clk::time_point tl[5];
+  for (int j = 0; j < 5 + nctx; j++) {          // launch j, after collecting launch j - nctx from the same context
+    MsmCtx* cx = &ps.ctx[j % nctx];
+    int rc;
+    if (j >= nctx) {
+      rc = msm_finish(cx, p.sums + 36 * (j - nctx));
+      ps.ms[2 + j - nctx] = ms_since(tl[j - nctx]);
+      if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+    }
+    if (j >= 5) continue;
+    const MsmJob& job = p.jobs[j];
+    tl[j] = clk::now();
+    rc = msm_launch(cx, job.bases, job.inf_flags, job.scalars, job.n, job.scalars_mode, job.table_stride);
+    if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+  }
+  note_last_acc(ps, &ps.ctx[4 % nctx]);
+  return ZKHIP_OK;
+}
+
 static int prove_partial(ProveState& ps, const zkhip_crs* crs, R1csDev* rd, const uint64_t* z, size_t a_lo, size_t h_lo, size_t l_lo,
                          uint64_t sums[5 * 36], const uint64_t* d_z_ready = nullptr, const uint64_t* d_z_app = nullptr) {
-  using clk = std::chrono::steady_clock;
-  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-  const size_t m = rd->n_vars, l = rd->n_primary;
-  const size_t a_len = crs->A->len, h_len = crs->H->len, l_len = crs->L->len;
+  const size_t m = rd->n_vars;
   { int rc_ = prove_check(crs, rd, a_lo, h_lo, l_lo); if (rc_ != ZKHIP_OK) return rc_; }
-  const int tc = crs->A->table_c;
-  auto t0 = clk::now();
+  const int tc = crs->A->table_c, naf = crs->A->table_naf;
+  const auto t0 = clk::now();
   if (!ps.st) {
-    // (ZKHIP_QAP_STREAM_PRIO=1: the QAP map's stream at the highest priority - an experiment of the split proof, see below)
+    // (ZKHIP_QAP_STREAM_PRIO=1: the QAP map's stream at the highest priority - an experiment of the split proof)
     static const int qprio = getenv("ZKHIP_QAP_STREAM_PRIO") ? atoi(getenv("ZKHIP_QAP_STREAM_PRIO")) : 0;
     int lo = 0, hi = 0;
     if (qprio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) API_HIP(hipStreamCreateWithPriority(&ps.st, hipStreamNonBlocking, hi));
@@ -840,183 +1003,30 @@ static int prove_partial(ProveState& ps, const zkhip_crs* crs, R1csDev* rd, cons
     API_HIP(hipMalloc(&ps.dz, m * 48));
     ps.dz_cap = m;
   }
-  const uint64_t* dz = d_z_ready ? d_z_ready : ps.dz;
+  ProofRun p{ps, rd, d_z_ready ? nullptr : z, d_z_ready ? d_z_ready : ps.dz, d_z_app, tc, naf, t0, sums, {}};
+  proof_jobs(crs, rd, p.dz, a_lo, h_lo, l_lo, p.jobs);
+  const size_t a_len = p.jobs[0].n, h_len = p.jobs[3].n;
+  const size_t maxlen = a_len > h_len ? a_len : (h_len ? h_len : 1);
   // a streaming prover whose five MSMs go through one launch sequence on ONE stream puts the upload and the QAP map on that stream
   // too: the host thread enqueues a whole proof without waiting between the phases (device side 376.8 -> 387.5 proofs/s in three
   // A/B pairs; ZKHIP_STREAM_CHAIN=0 restores the two waits, =2 chains every prover instance: +0.8 % for four 2^20 provers, not
   // adopted - the plain entry point's phase timings are the bench's one-proof-alone figures).  A chained proof's phase timings measure
   // enqueueing, not execution.
-  static const int chain_env = getenv("ZKHIP_STREAM_CHAIN") ? atoi(getenv("ZKHIP_STREAM_CHAIN")) : 1;
-  size_t maxlen = a_len > h_len ? a_len : h_len;
-  if (maxlen < 1) maxlen = 1;
-  size_t total_finite = 0;                          // (the rule of msm_launch_multi: a base at infinity never produces an entry)
-  {
-    const zkhip_bases* qs[5] = {crs->A, crs->B2, crs->B1, crs->H, crs->L};
-    const size_t lens[5] = {a_len, a_len, a_len, h_len, l_len};
-    for (int j = 0; j < 5; j++) {
-      const size_t nf = lens[j] == qs[j]->len ? qs[j]->n_finite : 0;
-      total_finite += (nf && nf < lens[j]) ? nf : lens[j];
-    }
-  }
   // (only when the launch sequence's context will be used as it stands: a context that ensure_ctx is about to rebuild gets a new stream)
-  const bool chain = chain_env && (ps.quad_below || chain_env == 2) && crs->A->table_c > 0 && crs->batch_msms && ps.ctx[ZK_MSM_SLOTS].stream &&
-                     ctx_reusable(&ps.ctx[ZK_MSM_SLOTS], ps.ready[ZK_MSM_SLOTS], maxlen, tc, 5, crs->A->table_naf, total_finite ? total_finite : 1);
-  hipStream_t qst = chain ? ps.ctx[ZK_MSM_SLOTS].stream : ps.st;
+  static const int chain_env = getenv("ZKHIP_STREAM_CHAIN") ? atoi(getenv("ZKHIP_STREAM_CHAIN")) : 1;
+  const bool chain = chain_env && (ps.quad_below || chain_env == 2) && tc > 0 && crs->batch_msms && ps.ctx[ZK_MSM_SLOTS].stream &&
+                     ctx_reusable(&ps.ctx[ZK_MSM_SLOTS], maxlen, tc, 5, naf, jobs_terms(p.jobs, 5));
   ps.chained_last = chain;
   ps.split_last = false;
   ps.last_acc_ctx2 = nullptr;
-  // OPTION, off by default (ZKHIP_PROVE_SPLIT=1; =2: without the gate between the two accumulations) - a proof that is alone on the
-  // chip as TWO launch sequences (round 6): four of the five MSMs - A, B-G2, B-G1, L - need only the assignment, so
-  // their sort and accumulation start as soon as z is on the device, on their own plan, while the QAP map runs beside them on the
-  // prover's stream; the H MSM follows on a second plan behind an event on h, and the bucket reduction of the first sequence runs
-  // under its accumulation.  Same group elements, bit-identical proofs (the partitioned and serial tests pass with it on).
-  // MEASURED AND NOT ADOPTED (profiles/r06_split_proof_ab.txt, one box, tools/partition_model.py): one 2^20 proof alone 50.0 ms as one
-  // sequence, 52.0 split (49.8-50.5 without the gate); one rank of an eight-way 2^22 key 38.6 -> 39.8 ms; an eighth of a 2^20 key
-  // 12.4 -> 13.5-14.8 ms.  The map is not idle time to hide: at 2^22 its seven FFTs and three SpMVs fill the chip (9.4 ms of
-  // multiplier and HBM work) and share the accumulation's issue slots when run beside it - the two accumulation launches together
-  // take 44 ms where the single one takes 37 - and every launch sequence brings its own one-fill tail, stitching and reduction chain.
+  int rc;
   const int split_env = g_prove_split.load();
-  if (split_env && !chain && !ps.quad_below && tc > 0 && crs->batch_msms && h_len > 0 && a_len > 0) {
-    const zkhip_bases* qz[4] = {crs->A, crs->B2, crs->B1, crs->L};
-    const size_t lz[4] = {a_len, a_len, a_len, l_len};
-    size_t tot_z = 0, max_z = a_len > l_len ? a_len : l_len;
-    for (int j = 0; j < 4; j++) { const size_t nf = lz[j] == qz[j]->len ? qz[j]->n_finite : 0; tot_z += (nf && nf < lz[j]) ? nf : lz[j]; }
-    const size_t nf_h = h_len == crs->H->len ? crs->H->n_finite : 0, tot_h = (nf_h && nf_h < h_len) ? nf_h : h_len;
-    MsmCtx *cz = &ps.ctx[ZK_CTX_Z], *ch = &ps.ctx[ZK_CTX_H];
-    int rc = ensure_ctx(cz, &ps.ready[ZK_CTX_Z], max_z ? max_z : 1, tc, 4, crs->A->table_naf, tot_z ? tot_z : 1, 0, ps.pre);
-    if (rc == ZKHIP_OK) rc = ensure_ctx(ch, &ps.ready[ZK_CTX_H], h_len, tc, 1, crs->A->table_naf, tot_h ? tot_h : 1);
-    if (rc == ZKHIP_OK) {
-      if (!ps.ev_up) API_HIP(hipEventCreateWithFlags(&ps.ev_up, hipEventDisableTiming));
-      if (!ps.ev_qap) API_HIP(hipEventCreateWithFlags(&ps.ev_qap, hipEventDisableTiming));
-      if (!d_z_ready) API_HIP(hipMemcpyAsync(ps.dz, z, m * 48, hipMemcpyHostToDevice, ps.st));
-      API_HIP(hipEventRecord(ps.ev_up, ps.st));
-      API_HIP(hipStreamWaitEvent(cz->stream, ps.ev_up, 0));
-      ps.ms[0] = ms_since(t0);
-      t0 = clk::now();
-      MsmJob mz[4];
-      const uint64_t* scz[4] = {dz + a_lo * 6, dz + a_lo * 6, dz + a_lo * 6, dz + (l + 1 + l_lo) * 6};
-      for (int j = 0; j < 4; j++)
-        mz[j] = MsmJob{qz[j]->d_pts, qz[j]->d_inf, scz[j], lz[j], 1, qz[j]->len, lz[j] == qz[j]->len ? qz[j]->n_finite : 0};
-      const MsmJob mh{crs->H->d_pts, crs->H->d_inf, (const uint64_t*)rd->bufA + h_lo * 6, h_len, 2, crs->H->len, nf_h};
-      auto tl0 = clk::now();
-      rc = msm_launch_multi(cz, 4, mz);
-      if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cz->errbuf); return rc; }
-      rc = qap_h_dev(rd, dz, ps.st, t_err, sizeof t_err, d_z_app);
-      if (rc == ZKHIP_OK) {
-        hipError_t e = hipEventRecord(ps.ev_qap, ps.st);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ch->stream, ps.ev_qap, 0);
-        if (e != hipSuccess) { snprintf(t_err, sizeof t_err, "split proof: %s", hipGetErrorString(e)); rc = ZKHIP_ERR_HIP; }
-      }
-      if (rc == ZKHIP_OK) {
-        ch->acc_gate = split_env == 2 ? nullptr : cz->ev_acc1;       // H's accumulation starts when the first one has ended (2: no gate)
-        rc = msm_launch_multi(ch, 1, &mh);
-        ch->acc_gate = nullptr;
-        if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", ch->errbuf);
-      }
-      ps.ms[1] = ms_since(t0);                      // (enqueueing the QAP map and both sequences: the phases overlap on the device)
-      uint64_t sz[4 * 36];
-      const int rc_z = msm_finish_multi(cz, 4, sz);           // (always collected: a pending plan would refuse the next proof)
-      if (rc_z != ZKHIP_OK && rc == ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cz->errbuf); rc = rc_z; }
-      if (rc != ZKHIP_OK) { (void)hipStreamSynchronize(ps.st); return rc; }
-      if ((rc = msm_finish_multi(ch, 1, sums + 108)) != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", ch->errbuf); return rc; }
-      memcpy(sums, sz, 3 * 36 * 8);
-      memcpy(sums + 144, sz + 108, 36 * 8);
-      for (int j = 0; j < 5; j++) ps.ms[2 + j] = ms_since(tl0);
-      ps.last_accumulate_ms = cz->last_accumulate_ms + ch->last_accumulate_ms;
-      ps.last_acc_ctx = cz; ps.last_acc_ctx2 = ch;
-      ps.split_last = true;
-      return ZKHIP_OK;
-    }
-    if (rc != ZKHIP_ERR_ARG) return rc;             // (a plan that does not fit 32-bit entry positions: the single-sequence path below decides)
-  }
-  if (!d_z_ready) {
-    API_HIP(hipMemcpyAsync(ps.dz, z, m * 48, hipMemcpyHostToDevice, qst));
-    if (!chain) {
-      API_HIP(hipEventRecord(ps.ev_st, qst));
-      API_HIP(zk_event_wait(ps.ev_st));
-    }
-  }
-  ps.ms[0] = ms_since(t0);
-  t0 = clk::now();
-  // (an application's constants - d_z_app - are part of the assignment the QAP map sees; the MSMs over z below run on the masked
-  //  vector: a zero scalar produces no bucket entry, the constants' share of A, B and L is the application's four cached points)
-  int rc = qap_h_dev(rd, dz, qst, t_err, sizeof t_err, d_z_app);
-  if (rc != ZKHIP_OK) return rc;
-  if (!chain) {
-    API_HIP(hipEventRecord(ps.ev_st, qst));
-    API_HIP(zk_event_wait(ps.ev_st));   // the MSM contexts run on their own streams
-  }
-  ps.ms[1] = ms_since(t0);
-  struct { const zkhip_bases* b; const uint64_t* sc; size_t len; int mode; uint64_t* out; } jobs[5] = {
-      {crs->A, dz + a_lo * 6, a_len, 1, sums}, {crs->B2, dz + a_lo * 6, a_len, 1, sums + 36}, {crs->B1, dz + a_lo * 6, a_len, 1, sums + 72},
-      {crs->H, (const uint64_t*)rd->bufA + h_lo * 6, h_len, 2, sums + 108}, {crs->L, dz + (l + 1 + l_lo) * 6, l_len, 1, sums + 144}};
-  bool batched = tc > 0 && crs->batch_msms;
-  if (batched) {
-    // table-backed key: the five MSMs share ONE launch sequence (one sort, one accumulation launch over all five entry
-    // lists, one reduction chain with a bucket window per MSM) - a fifth of the launches, five times the lanes in each.
-    // (A plan that does not fit the engine's 32-bit entry positions is refused with ZKHIP_ERR_ARG: one sequence per MSM then.)
-    const size_t total = total_finite;
-    rc = ensure_ctx(&ps.ctx[ZK_MSM_SLOTS], &ps.ready[ZK_MSM_SLOTS], maxlen, tc, 5, crs->A->table_naf, total ? total : 1, 0, ps.pre);
-    if (rc == ZKHIP_OK && ps.quad_below) { ps.ctx[ZK_MSM_SLOTS].quad_below = ps.quad_below; ps.ctx[ZK_MSM_SLOTS].one_stream = 1; }
-    if (rc == ZKHIP_ERR_ARG) {
-      // (a silent performance cliff) the plan's 32-bit entry positions / slice weights do not hold this key's terms at
-      // this window: said once per process, then one launch sequence per MSM
-      static std::atomic<bool> told{false};
-      if (!told.exchange(true))
-        fprintf(stderr, "zkhip: the five MSMs of this key do not fit ONE launch sequence (window %d, %zu terms: 32-bit slice weights); "
-                        "using one sequence per MSM - a larger table window (zkhip_key_opts.window) avoids this\n", tc, total);
-      batched = false;
-    }
-    else if (rc != ZKHIP_OK) return rc;
-  }
-  if (batched) {
-    MsmCtx* cx = &ps.ctx[ZK_MSM_SLOTS];
-    MsmJob mj[5];
-    for (int j = 0; j < 5; j++)
-      mj[j] = MsmJob{jobs[j].b->d_pts, jobs[j].b->d_inf, jobs[j].sc, jobs[j].len, jobs[j].mode, jobs[j].b->len,
-                     jobs[j].len == jobs[j].b->len ? jobs[j].b->n_finite : 0};
-    auto tl0 = clk::now();
-    if ((rc = msm_launch_multi(cx, 5, mj)) == ZKHIP_OK) rc = msm_finish_multi(cx, 5, sums);
-    if (rc != ZKHIP_OK) {
-      // (a chained proof's stream also carried the upload and the QAP map: their failure surfaces here)
-      snprintf(t_err, sizeof t_err, "%s%s", cx->errbuf, chain ? " [chained proof: this stream also carried the upload of the assignment and the QAP map]" : "");
-      return rc;
-    }
-    for (int j = 0; j < 5; j++) ps.ms[2 + j] = ms_since(tl0);
-    ps.last_accumulate_ms = cx->last_accumulate_ms;
-    ps.last_acc_ctx = cx;
-    return ZKHIP_OK;
-  }
-  // MSMs in flight: while MSM j reduces its buckets (latency-bound, few lanes), MSM j+1 accumulates.  Large
-  // circuits keep two contexts (each holds ~1.3 GB of work space at 2^20); small ones (every phase is
-  // latency-bound and the chip is mostly idle) run all five MSMs side by side.
-  const int nctx = (maxlen <= ((size_t)1 << 18)) ? 5 : 2;
-  MsmCtx* ctxs[5];
-  for (int k = 0; k < nctx; k++) {
-    if ((rc = ensure_ctx(&ps.ctx[k], &ps.ready[k], maxlen, tc, 1, crs->A->table_naf)) != ZKHIP_OK) return rc;
-    if (ps.quad_below) { ps.ctx[k].quad_below = ps.quad_below; ps.ctx[k].one_stream = 1; }
-    ctxs[k] = &ps.ctx[k];
-  }
-  clk::time_point tl[5];
-  for (int j = 0; j < 5; j++) {
-    MsmCtx* cx = ctxs[j % nctx];
-    if (j >= nctx) {
-      rc = msm_finish(cx, jobs[j - nctx].out);
-      ps.ms[2 + j - nctx] = ms_since(tl[j - nctx]);
-      if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cx->errbuf); return rc; }
-    }
-    tl[j] = clk::now();
-    rc = msm_launch(cx, jobs[j].b->d_pts, jobs[j].b->d_inf, jobs[j].sc, jobs[j].len, jobs[j].mode, jobs[j].b->len);
-    if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cx->errbuf); return rc; }
-  }
-  for (int j = 5 - nctx; j < 5; j++) {
-    rc = msm_finish(ctxs[j % nctx], jobs[j].out);
-    ps.ms[2 + j] = ms_since(tl[j]);
-    if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", ctxs[j % nctx]->errbuf); return rc; }
-  }
-  ps.last_accumulate_ms = ctxs[4 % nctx]->last_accumulate_ms;
-  ps.last_acc_ctx = ctxs[4 % nctx];
-  return ZKHIP_OK;
+  if (split_env && !chain && !ps.quad_below && tc > 0 && crs->batch_msms && h_len > 0 && a_len > 0)
+    if ((rc = prove_split(p, split_env != 2)) != ZK_PLAN_UNFIT) return rc;
+  if ((rc = prove_upload_and_map(p, chain ? ps.ctx[ZK_MSM_SLOTS].stream : ps.st, chain)) != ZKHIP_OK) return rc;
+  if (tc > 0 && crs->batch_msms)
+    if ((rc = prove_batched(p, maxlen, chain)) != ZK_PLAN_UNFIT) return rc;
+  return prove_separate(p, maxlen);
 }
 
 int zkhip_groth16_prove_partial(const zkhip_crs* crs_slice, zkhip_r1cs* r1cs, const uint64_t* z, size_t a_lo, size_t h_lo, size_t l_lo,
@@ -1133,7 +1143,6 @@ static int finish_impl(const uint64_t alpha_g1[24], const uint64_t beta_g1[24], 
                        const uint64_t delta_g2[24], const uint64_t sums_jac[180], const uint64_t r_m[6], const uint64_t s_m[6],
                        uint64_t proof_affine[72], double* tail_ms, TailPre* pre = nullptr) {
   using namespace host;
-  using clk = std::chrono::steady_clock;
   if (!alpha_g1 || !beta_g1 || !beta_g2 || !delta_g1 || !delta_g2 || !sums_jac || !r_m || !s_m || !proof_affine) return fail(ZKHIP_ERR_ARG, "null pointer");
   auto t0 = clk::now();
   const uint64_t *evA = sums_jac, *evB2 = sums_jac + 36, *evB1 = sums_jac + 72, *evH = sums_jac + 108, *evL = sums_jac + 144;
@@ -1152,7 +1161,7 @@ static int finish_impl(const uint64_t alpha_g1[24], const uint64_t beta_g1[24], 
   gA.to_affine(x, y); x.to_limbs(proof_affine); y.to_limbs(proof_affine + 12);
   gB2.to_affine(x, y); x.to_limbs(proof_affine + 24); y.to_limbs(proof_affine + 36);
   gC.to_affine(x, y); x.to_limbs(proof_affine + 48); y.to_limbs(proof_affine + 60);
-  if (tail_ms) *tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+  if (tail_ms) *tail_ms = ms_since(t0);
   return ZKHIP_OK;
 }
 
@@ -1455,9 +1464,9 @@ int zkhip_prover_create_streams(zkhip_prover* p, int which) {
   std::lock_guard<std::mutex> lk(p->mu);
   ProveState& ps = p->ps;
   if (which == 0) {
-    if (!ps.pre[0] && !ps.ready[ZK_MSM_SLOTS]) API_HIP(hipStreamCreateWithFlags(&ps.pre[0], hipStreamNonBlocking));
+    if (!ps.pre[0] && !ps.ctx[ZK_MSM_SLOTS].planned) API_HIP(hipStreamCreateWithFlags(&ps.pre[0], hipStreamNonBlocking));
   } else {
-    if (!ps.pre[1] && !ps.ready[ZK_MSM_SLOTS]) API_HIP(hipStreamCreateWithFlags(&ps.pre[1], hipStreamNonBlocking));
+    if (!ps.pre[1] && !ps.ctx[ZK_MSM_SLOTS].planned) API_HIP(hipStreamCreateWithFlags(&ps.pre[1], hipStreamNonBlocking));
     if (!ps.st) API_HIP(hipStreamCreateWithFlags(&ps.st, hipStreamNonBlocking));
   }
   return ZKHIP_OK;
@@ -1469,7 +1478,7 @@ int zkhip_prover_set_streaming(zkhip_prover* p, int on) {
   // measured on the wrapping circuit: 212 -> 228 proofs/s with six provers in flight, 107 -> 98 one at a time
   p->ps.quad_below = on ? 1024u : 0u;
   p->rd->spmv_log_lanes = on ? (p->rd->spmv_log_lanes_alone < 2 ? p->rd->spmv_log_lanes_alone : 2) : p->rd->spmv_log_lanes_alone;
-  for (int k = 0; k < ZK_CTX_TOTAL; k++) if (p->ps.ready[k]) { p->ps.ctx[k].quad_below = on ? 1024u : 65536u; p->ps.ctx[k].one_stream = on ? 1 : 0; }
+  for (int k = 0; k < ZK_CTX_TOTAL; k++) if (p->ps.ctx[k].planned) { p->ps.ctx[k].quad_below = on ? 1024u : 65536u; p->ps.ctx[k].one_stream = on ? 1 : 0; }
   return ZKHIP_OK;
 }
 
@@ -1477,14 +1486,13 @@ static int last_entries_of(ProveState& ps, uint64_t* out) {
   *out = 0;
   if (!ps.last_acc_ctx) return ZKHIP_OK;
   int rc = msm_last_entries(ps.last_acc_ctx, out);
-  if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", ps.last_acc_ctx->errbuf);
-  if (rc == ZKHIP_OK && ps.last_acc_ctx2) {          // a split proof: two accumulation launches
+  if (rc != ZKHIP_OK) return ctx_fail(rc, ps.last_acc_ctx);
+  if (ps.last_acc_ctx2) {          // a split proof: two accumulation launches
     uint64_t more = 0;
-    rc = msm_last_entries(ps.last_acc_ctx2, &more);
-    if (rc != ZKHIP_OK) snprintf(t_err, sizeof t_err, "%s", ps.last_acc_ctx2->errbuf);
+    if ((rc = msm_last_entries(ps.last_acc_ctx2, &more)) != ZKHIP_OK) return ctx_fail(rc, ps.last_acc_ctx2);
     *out += more;
   }
-  return rc;
+  return ZKHIP_OK;
 }
 int zkhip_prover_last_accumulate_entries(zkhip_prover* p, uint64_t* out) {
   if (!p || !out) return fail(ZKHIP_ERR_ARG, "null argument");
@@ -2288,8 +2296,7 @@ struct zkhip_msm_stream {
   int device = 0;
   const zkhip_bases* bases = nullptr;
   int depth = 0;
-  std::vector<MsmCtx> ctx;
-  std::vector<char> ready;
+  std::vector<MsmCtx> ctx;               // (value-initialised: all zeros, no plan - msm.h)
   std::vector<uint64_t> ticket_of;       // per slot: the ticket in flight there, 0 = free
   std::vector<void*> d_stage;            // per slot: device copy of host scalars (zkhip_msm_stream_submit_host)
   std::vector<size_t> stage_cap;
@@ -2304,9 +2311,8 @@ int zkhip_msm_stream_new(const zkhip_bases* bases, int depth, zkhip_msm_stream**
   BIND(bases);
   zkhip_msm_stream* st = new zkhip_msm_stream();
   st->device = bases->device; st->bases = bases; st->depth = depth;
-  st->ctx.resize(depth); st->ready.assign(depth, 0); st->ticket_of.assign(depth, 0);
+  st->ctx.resize(depth); st->ticket_of.assign(depth, 0);
   st->d_stage.assign(depth, nullptr); st->stage_cap.assign(depth, 0);
-  for (auto& c : st->ctx) memset(&c, 0, sizeof c);
   *out = st;
   return ZKHIP_OK;
 }
@@ -2315,7 +2321,7 @@ void zkhip_msm_stream_free(zkhip_msm_stream* st) {
   if (!st) return;
   (void)bind_dev(st->device);
   for (int k = 0; k < st->depth; k++) {
-    if (st->ready[k]) {
+    if (st->ctx[k].planned) {
       if (st->ctx[k].pending) { uint64_t drop[36]; (void)msm_finish(&st->ctx[k], drop); }      // never free work space under a running launch
       msm_plan_free(&st->ctx[k]);
     }
@@ -2335,9 +2341,7 @@ static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const voi
   for (int k = 0; k < st->depth; k++) if (!st->ticket_of[k]) { slot = k; break; }
   if (slot < 0) return fail(ZKHIP_ERR_STATE, "every slot of this stream is in flight: collect a result first");
   MsmCtx* cx = &st->ctx[slot];
-  bool rdy = st->ready[slot] != 0;
-  int rc = ensure_ctx(cx, &rdy, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c);
-  st->ready[slot] = rdy ? 1 : 0;
+  int rc = ensure_ctx(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c);
   if (rc != ZKHIP_OK) return rc;
   if (h_scalars && len) {
     // host scalars: one asynchronous copy in front of the MSM's kernels, on the context's own stream (truly asynchronous from pinned
@@ -2350,9 +2354,8 @@ static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const voi
     API_HIP(hipMemcpyAsync(st->d_stage[slot], h_scalars, len * 48, hipMemcpyHostToDevice, cx->stream));
     d_scalars = st->d_stage[slot];
   }
-  rc = msm_launch(cx, b->d_pts + offset, b->d_inf ? b->d_inf + offset : nullptr, (const uint64_t*)d_scalars, len, scalars_montgomery, b->len,
-                  msm_edw_at(b->d_edw, offset));
-  if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cx->errbuf); return rc; }
+  const MsmJob job = single_job(b, offset, d_scalars, len, scalars_montgomery);
+  if ((rc = msm_launch_multi(cx, 1, &job)) != ZKHIP_OK) return ctx_fail(rc, cx);
   st->ticket_of[slot] = st->next_ticket;
   *ticket = st->next_ticket++;
   return ZKHIP_OK;
@@ -2376,8 +2379,8 @@ int zkhip_msm_stream_collect(zkhip_msm_stream* st, uint64_t ticket, uint64_t out
   if (slot < 0) return fail(ZKHIP_ERR_STATE, ticket ? "no such ticket in flight on this stream" : "nothing in flight on this stream");
   MsmCtx* cx = &st->ctx[slot];
   st->ticket_of[slot] = 0;                  // (msm_finish clears `pending` whatever it returns: the slot is free again)
-  int rc = msm_finish(cx, out_jac);
-  if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "%s", cx->errbuf); return rc; }
+  const int rc = msm_finish(cx, out_jac);
+  if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
   st->last_accumulate_ms = cx->last_accumulate_ms; st->last_interval[0] = cx->last_acc_begin_ms; st->last_interval[1] = cx->last_acc_end_ms;
   return ZKHIP_OK;
 }
