@@ -100,6 +100,36 @@ class hip_proving_key {
   size_t n_vars_ = 0;
 };
 
+// A verification key resident on the GPU (zkhip_verifier): Groth16 verification of MANY proofs at once by the pairing kernels, the
+// same equation as wsnarkT::verify (aggregator_dummy_test.cpp:61-62).  Non-copyable; one batch in flight per instance, several
+// instances - one host thread each - run side by side.  Points are not checked: on their curves and of order r, or infinity.
+class hip_verifier {
+ public:
+  // alpha (G1), beta, delta (G2): 24 limbs each; abc: (n_inputs + 1) x 24 limbs
+  hip_verifier(const uint64_t* alpha_g1, const uint64_t* beta_g2, const uint64_t* delta_g2, const uint64_t* abc, size_t n_inputs) {
+    zk_check(zkhip_verifier_new(alpha_g1, beta_g2, delta_g2, abc, n_inputs, &v_), "zkhip_verifier_new");
+  }
+  hip_verifier(const hip_verifier&) = delete;
+  hip_verifier& operator=(const hip_verifier&) = delete;
+  ~hip_verifier() { zkhip_verifier_free(v_); }
+  size_t num_inputs() const { return zkhip_verifier_num_inputs(v_); }
+  // inputs: proofs.size() x num_inputs() x 6 limbs.  One verdict per proof (1 = accepted).
+  std::vector<uint8_t> verify_batch(const uint64_t* inputs, const std::vector<groth16_proof>& proofs) {
+    std::vector<uint64_t> flat(proofs.size() * 72);
+    for (size_t i = 0; i < proofs.size(); i++) {
+      std::memcpy(&flat[i * 72], proofs[i].a.data(), 192);
+      std::memcpy(&flat[i * 72 + 24], proofs[i].b.data(), 192);
+      std::memcpy(&flat[i * 72 + 48], proofs[i].c.data(), 192);
+    }
+    std::vector<uint8_t> ok(proofs.size());
+    zk_check(zkhip_verifier_verify_batch(v_, inputs, flat.data(), proofs.size(), ok.data()), "zkhip_verifier_verify_batch");
+    return ok;
+  }
+
+ private:
+  zkhip_verifier* v_ = nullptr;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Policy-class adapter.  `baseT` is the reference's CPU policy class (libzeth::groth16_snark<ppT>);
 // `bridgeT` converts its types to limb arrays (three small functions, shown in INTEGRATION.md):
@@ -121,6 +151,11 @@ class groth16_snark_hip : public baseT {
     uint64_t r[6], s[6];
     bridgeT::random_scalars(r, s);
     return bridgeT::proof_from_limbs(dev->generate_proof(z.data(), r, s));
+  }
+  // Next to the inherited verify(inputs, proof, vk) (one proof, CPU): many proofs under one key on the GPU.  The key is a
+  // hip_verifier the caller made once from the verification key's limbs; inputs: proofs.size() x vk.num_inputs() x 6 limbs.
+  static std::vector<uint8_t> verify_batch(hip_verifier& vk, const uint64_t* inputs, const std::vector<groth16_proof>& proofs) {
+    return vk.verify_batch(inputs, proofs);
   }
 };
 

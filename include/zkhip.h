@@ -321,6 +321,26 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
                          const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_affine[72],
                          int* ok);
 
+/* ---- Groth16 verification in batches on the device ------------------------------------------------------------------------------
+ * replaces: wsnarkT::verify(primary_inputs, proof, vk) (libzecale/tests/aggregator/aggregator_dummy_test.cpp:61-62), the same seam
+ * and the same equation as zkhip_groth16_verify above, for MANY proofs under one key at once: the reduced Tate pairing of
+ * zkhip_groth16_verify as gfx950 kernels (pairing.cuh / pairing.hip), eight lanes per verification, and
+ * acc = ABC_0 + sum x_i ABC_i per proof on the device.  Verdicts equal zkhip_groth16_verify's on every input that meets the
+ * PRECONDITIONS, which - as in the host route's pairing - are NOT checked here: every point of the key and of the proofs is on its
+ * curve and of order r, or the point at infinity (all zero).  Encodings, the fixed G2 generator paired with acc, and "a pair with a
+ * member at infinity contributes 1" are the host route's.
+ * A handle owns its stream and work space and lives on the calling thread's library device (zkhip_set_device); ONE batch is in
+ * flight per handle, several handles - one host thread each - run beside each other and beside provers.  There is no CPU fallback:
+ * ZKHIP_ERR_NO_DEVICE / ZKHIP_ERR_STATE without an initialised device.  count == 0 returns ZKHIP_OK; n_inputs == 0 is valid.
+ * vk_abc: (n_inputs + 1) x 24 limbs; inputs: count x n_inputs x 6 limbs; proofs_affine: count x [A (G1) | B (G2) | C (G1)];
+ * ok: count bytes, 1 = accepted. */
+typedef struct zkhip_verifier zkhip_verifier;
+int zkhip_verifier_new(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                       const uint64_t* vk_abc, size_t n_inputs, zkhip_verifier** out);
+size_t zkhip_verifier_num_inputs(const zkhip_verifier* v);
+int zkhip_verifier_verify_batch(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* ok);
+void zkhip_verifier_free(zkhip_verifier* v);
+
 /* ---- the wrapping (aggregator) circuit: host code, no device needed ------------------------------- */
 /* Nested objects are over BLS12-377, whose base field is Fr of BW6-761: coordinates are 6-limb Montgomery
  * elements.  G1 affine = x | y (12 limbs); G2 affine = x.c0 | x.c1 | y.c0 | y.c1 (24 limbs), Fq2 = Fq[u]/(u^2+5).
@@ -544,6 +564,15 @@ int zkhip_measure_ntt(unsigned log_d, int dir, int coset, int batch, int reps, d
  * receives n x { a b / R, a^2 / R, (a b + c d) / R } in the device's own form (R = 2^783 / 2^406).  Operands must respect the
  * bodies' contract (limbs below 2^29 except the top one, products below 2^10 R p). */
 int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out);
+/* Test hooks of the pairing kernels (no counterpart).
+ * fq6_selftest: n independent operand sets through the per-lane bodies of pairing.cuh inside a real kernel, eight lanes per set:
+ * op 0 = a b, 1 = a^2, 2 = a (b_0 + b_3 w^3 + b_4 w^4) (the sparse line product; b's other coefficients are ignored) in
+ * Fq6 = Fq[w]/(w^6 + 4).  a, b, out: n x 6 coefficients x 12 ABI limbs.
+ * pairing_product: out[i] = prod_{p < pairs_per_product} t(g1[i][p], g2[i][p]), the REDUCED value (6 x 12 ABI limbs, canonical), of
+ * `count` products; g1, g2: count x pairs_per_product x 24 limbs; pairs_per_product in 1 .. 4.  route 0: the host code of
+ * zkhip_groth16_verify (needs no device); route 1: the kernels of zkhip_verifier_verify_batch. */
+int zkhip_internal_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out);
 /* Test hook (no counterpart), HOST ONLY - works without a device: the prover's tail (row a9) on the paths a healthy proof never
  * takes: `rounds` proofs abandoned between the start of the tail's key-only scalar multiplications and their collection, the key's
  * tables freed at once (run under the CPU AddressSanitizer build); a delta of small order (`small_order_g1`, e.g. (1, 0)) whose

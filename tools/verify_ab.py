@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Groth16 verification of the batch-2 wrapping key's proofs: the GPU pairing kernels (zkhip.Verifier) against the host route
+(zkhip.groth16_verify) on 16 threads, measured in the same run, and the wrapping stream's rate with and without a Verifier checking
+every proof beside it.  Writes profiles/verify_gpu.txt (or --out).  Each block runs once; the first GPU call (work space) is not timed.
+Usage: python tools/verify_ab.py [--out FILE] [--stream N] [--gpu-slots K]"""
+import argparse
+import os
+import sys
+import threading
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HOST_THREADS = 16
+COUNTS = (1, 64, 1024, 16384)
+EXTRA = (16, 32, 128, 256)          # more points for the count at which the GPU overtakes the host
+BATCH = 256
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "verify_gpu.txt"))
+    ap.add_argument("--stream", type=int, default=2048, help="proofs per block of the stream measurement (0: skip)")
+    ap.add_argument("--gpu-slots", type=int, default=24)
+    ap.add_argument("--pool", type=int, default=16, help="distinct proofs (the batches repeat them; the last one gets a bumped input)")
+    args = ap.parse_args()
+    import bench
+    from zecale_amd import zkhip
+    zkhip.init(0)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    nvk_l, npr, nin, trapdoor = bench.aggregator_inputs(1)
+    agg = zkhip.AggregatorCircuit(2, 1)
+    desc = zkhip.r1cs_desc_from_aggregator(agg)
+    kp = zkhip.Keypair(desc, *trapdoor)
+    vk, crs = kp.vk(), kp.upload_crs()
+    z = agg.witness(nvk_l, npr, nin)
+    n_in = agg.num_primary_inputs()
+    prim = np.ascontiguousarray(z[1:1 + n_in])
+    rs = bench.random_fr_uniform(9, 2 * args.pool)
+    prover = zkhip.Prover(crs, desc)
+    pool = np.array([prover.prove(z, rs[2 * i], rs[2 * i + 1]) for i in range(args.pool)])
+    prover.free()
+    pool_in = np.tile(prim, (args.pool, 1, 1))
+    pool_in[-1, 0, 0] ^= np.uint64(1)                       # one invalid statement in the pool
+    say("# Groth16 verification, batch-2 wrapping key (%d primary inputs): GPU pairing kernels vs the host route on %d threads" % (n_in, HOST_THREADS))
+
+    # ---- host route, 16 threads (ctypes releases the GIL)
+    n_host = 256
+    idx = [i % args.pool for i in range(n_host)]
+    with ThreadPoolExecutor(HOST_THREADS) as ex:
+        list(ex.map(lambda i: zkhip.groth16_verify(vk, pool_in[i], pool[i]), idx[:HOST_THREADS]))      # threads up
+        t = time.perf_counter()
+        host_ok = list(ex.map(lambda i: zkhip.groth16_verify(vk, pool_in[i], pool[i]), idx))
+        host_dt = time.perf_counter() - t
+    host_rate = n_host / host_dt
+    assert host_ok == [i != args.pool - 1 for i in idx], "host verdicts"
+    t = time.perf_counter()
+    zkhip.groth16_verify(vk, pool_in[0], pool[0])
+    say("host: %d proofs on %d threads in %.2f s = %.1f verifications/s (one proof on one thread: %.1f ms)" % (n_host, HOST_THREADS, host_dt, host_rate, (time.perf_counter() - t) * 1e3))
+
+    # ---- GPU route
+    ver = zkhip.Verifier(vk)
+    ver.verify_batch(pool_in[:1], pool[:1])
+    say("%8s %12s %16s %14s %s" % ("count", "ms/batch", "verifications/s", "host ms (16 t)", "GPU faster"))
+    gpu_ms = {}
+    for count in sorted(COUNTS + EXTRA):
+        idx = np.arange(count) % args.pool
+        inp, prf = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
+        t = time.perf_counter()
+        ok = ver.verify_batch(inp, prf)
+        dt = time.perf_counter() - t
+        assert list(ok) == [i != args.pool - 1 for i in idx], "GPU verdicts at count %d" % count
+        gpu_ms[count] = dt * 1e3
+        host_ms = count / host_rate * 1e3 if count >= HOST_THREADS else 1e3 / (host_rate / HOST_THREADS)
+        say("%8d %12.1f %16.1f %14.1f %s%s" % (count, dt * 1e3, count / dt, host_ms, "yes" if dt * 1e3 < host_ms else "no", "" if count in COUNTS else "   (crossover probe)"))
+    over = [c for c in sorted(gpu_ms) if gpu_ms[c] < (c / host_rate * 1e3 if c >= HOST_THREADS else 1e3 / (host_rate / HOST_THREADS))]
+    say("the GPU overtakes the %d host threads at count %s (smallest measured count at which its batch is faster)" % (HOST_THREADS, over[0] if over else "none measured"))
+    gate = gpu_ms[1024] < 1024 / host_rate * 1e3
+    say("GATE (GPU faster than %d host threads at 1,024 proofs): %s  (%.1fx)" % (HOST_THREADS, "met" if gate else "MISSED", (1024 / host_rate * 1e3) / gpu_ms[1024]))
+
+    # ---- the wrapping stream with and without a Verifier beside it (interleaved: without, with, without, with)
+    if args.stream:
+        provers = [zkhip.Prover(crs, desc) for _ in range(args.gpu_slots)]
+        for p_ in provers:
+            p_.set_streaming(True)
+            p_.prove(z, rs[0], rs[1])
+
+        def block(with_verifier):
+            counter, lock, done = [args.stream], threading.Lock(), []
+            cv = threading.Condition()
+            verdicts = []
+
+            def worker(p_):
+                while True:
+                    with lock:
+                        if counter[0] <= 0:
+                            return
+                        counter[0] -= 1
+                    pr = p_.prove(z, rs[0], rs[1])
+                    with cv:
+                        done.append(pr)
+                        cv.notify()
+
+            def checker():
+                seen = 0
+                while seen < args.stream:
+                    with cv:
+                        cv.wait_for(lambda: len(done) - seen >= min(BATCH, args.stream - seen))
+                        take = done[seen:seen + BATCH]
+                    verdicts.extend(ver.verify_batch(np.tile(prim, (len(take), 1, 1)), np.array(take)))
+                    seen += len(take)
+            ths = [threading.Thread(target=worker, args=(p_,)) for p_ in provers] + ([threading.Thread(target=checker)] if with_verifier else [])
+            t = time.perf_counter()
+            [x.start() for x in ths]; [x.join() for x in ths]
+            dt = time.perf_counter() - t
+            assert all(verdicts) and len(verdicts) == (args.stream if with_verifier else 0)
+            return args.stream / dt
+        rates = [(w, block(w)) for w in (False, True, False, True)]
+        say("wrapping stream, %d proofs per block on %d prover instances, proofs/s (every proof verified in batches of %d where a Verifier runs beside it):" % (args.stream, args.gpu_slots, BATCH))
+        for w, r in rates:
+            say("  %-18s %8.1f" % ("with Verifier" if w else "without Verifier", r))
+        for p_ in provers:
+            p_.free()
+    ver.free(); crs.free(); kp.free(); agg.free()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0 if gate else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

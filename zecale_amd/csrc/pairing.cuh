@@ -1,0 +1,132 @@
+// The BW6-761 reduced Tate pairing of pairing_host.hpp, cut into per-lane bodies for the device (pairing.hip) and for g++
+// (tests/pairing_host_shim.cpp): t(P, Q) = f_{r,P}(psi(Q))^((q^6-1)/r), Fq6 = Fq[w]/(w^6 + 4), lines l0 + l3 w^3 + l4 w^4,
+// vertical lines dropped (wsnarkT::verify of the snark policy class, reference libzecale/tests/aggregator/aggregator_dummy_test.cpp:61-62).
+//
+// THE CUT: one lane per Fq6 coefficient, six lanes of a group of eight, operands exchanged through LDS.
+//   * An Fq6 product is 36 Fq products; coefficient k needs exactly six of them (c_k = sum_i a_i b'_{k-i}, b'_j = b_j for j >= 0 and
+//     -4 b_{j+6} below), i.e. three fp_mul2 - the same work on every lane, no reduction tree, no partial sums to exchange: a lane
+//     reads its twelve operands from LDS and writes one coefficient back.  The house DPP quad would spread ONE Fq product over four
+//     lanes; here the six coefficients are the independent units the algebra already offers, and the multiplier's chain stays whole.
+//   * The point steps of the (up to four) pairs are independent of each other and of the accumulator's squaring: pair p runs on lane p
+//     of the group while all six coefficient lanes square; the group then folds the four lines into the accumulator one after the other
+//     (a sparse line costs one fp_mul2 and one fp_mul per lane).
+//   * Eight lanes per verification: G = 8 verifications per wave, and a 128-thread workgroup holds WG = 16.
+// Every body below is a function of (lane index, operand arrays) with a fixed amount of work; none of them waits, spins or branches on data
+// (the choice between b_j and -4 b_j, and "this pair has reached infinity", are selects).
+//
+// LAZY BOUNDS ([k]: value < k p, limbs normalised; fp29.cuh: a b + c d < 2^10 R p, R / p > 2^22, fp_sub<K>(a, b) needs b <= K p):
+//   Fq6 coefficients in memory are [4]; -4 x of a [4] value is [16]; line coefficients l3, l4 are [2], l0 is [6]; Jacobian X [18], Y [4], Z [4].
+#pragma once
+#include "fp29.cuh"
+
+namespace zkhip {
+
+constexpr int PAIRING_GROUP = 8;        // lanes per verification (six coefficient lanes + two idle)
+constexpr int PAIRING_MAX_PAIRS = 4;    // pairs per product (one point step per lane, lanes 0 .. 3)
+constexpr int PAIRING_MILLER_STEPS = 376;   // bit length of r minus one
+
+ZK_HD ZK_INL Fq fq_select(bool c, const Fq& a, const Fq& b) {
+  Fq r;
+#pragma unroll
+  for (int i = 0; i < FqParams::NL; i++) r.l[i] = c ? a.l[i] : b.l[i];
+  return r;
+}
+// -4 x for x [4]: 4 x is [16], 16 p - 4 x is [16]
+ZK_HD ZK_INL Fq fq_times_m4(const Fq& x) { return fp_sub<FqParams, 16>(fp_zero<FqParams>(), fp_dbl(fp_dbl(x))); }
+// b'_j of the reduction by w^6 = -4: b_j for j >= 0, -4 b_{j+6} for j < 0.   b [4] -> [16]
+ZK_HD ZK_INL Fq fq6_wrapped(const Fq* b, int j) {
+  const Fq x = b[j < 0 ? j + 6 : j];
+  return fq_select(j < 0, fq_times_m4(x), x);
+}
+
+// coefficient k (0 .. 5) of a b.  a, b: six coefficients [4].  Result [4]:
+//   each fp_mul2 sums two products of [4] x [16]: < 128 p^2 < 2^10 R p, its result < 128 p^2 / R + p < p (1 + 2^-15); three of them < 4 p.
+ZK_HD ZK_INL Fq fq6_mul_coeff(int k, const Fq* a, const Fq* b) {
+  Fq s = fp_zero<FqParams>();
+#pragma unroll 1
+  for (int t = 0; t < 3; t++) {
+    const Fq r = fp_mul2(a[2 * t], fq6_wrapped(b, k - 2 * t), a[2 * t + 1], fq6_wrapped(b, k - 2 * t - 1));
+    s = fp_add(s, r);                                   // [1 + 2^-15] each: the sum stays below [4]
+  }
+  return s;
+}
+
+// coefficient k of f (l0 + l3 w^3 + l4 w^4).  f: six coefficients [4]; l = {l0 [6], l3 [2], l4 [2]}.  Result [4]:
+//   fp_mul2: [4] x [6] + [4] x [16] < 88 p^2; fp_mul: [4] x [16]; each result < p (1 + 2^-15), their sum < [4].
+ZK_HD ZK_INL Fq fq6_mul_line_coeff(int k, const Fq* f, const Fq* l) {
+  const Fq l3 = fq_select(k < 3, fq_times_m4(l[1]), l[1]);
+  const Fq l4 = fq_select(k < 4, fq_times_m4(l[2]), l[2]);
+  const Fq t = fp_mul2(f[k], l[0], f[k < 3 ? k + 3 : k - 3], l3);
+  const Fq u = fp_mul(f[k < 4 ? k + 2 : k - 4], l4);
+  return fp_add(t, u);
+}
+
+struct MillerConst {     // one pair, device form, all [2]
+  Fq px, py;             // P in G1, affine
+  Fq xq4, yq4n;          // xQ / 4 and -yQ / 4: psi(Q) = (-xQ/4) w^4, (-yQ/4) w^3; the lines only ever use -(-xQ/4)
+};
+struct MillerPoint {     // running T = [k] P, Jacobian: X [18], Y [4], Z [4]
+  Fq X, Y, Z;
+};
+
+ZK_HD ZK_INL void miller_identity_line(Fq* line) {
+  line[0] = fp_one<FqParams>();
+  line[1] = fp_zero<FqParams>();
+  line[2] = fp_zero<FqParams>();
+}
+
+// line(T, T)(psi(Q)) scaled by 2 Y Z^3 (pairing_host.hpp miller_double), then T <- 2 T (dbl-2009-l with D = 4 X Y^2).
+// `done` (T has reached infinity, or the pair has a member at infinity) turns the line into 1; T is then never used again.
+ZK_HD ZK_INL void miller_double_step(MillerPoint& T, const MillerConst& c, bool done, Fq* line) {
+  const Fq XX = fp_sqr(T.X), YY = fp_sqr(T.Y), ZZ = fp_sqr(T.Z);          // [2]   (X [18]: 324 p^2, far below the limit)
+  const Fq t3 = fp_add(fp_dbl(XX), XX);                                   // [6]   3 X^2
+  const Fq YZ = fp_mul(T.Y, T.Z);                                         // [2]
+  const Fq A = fp_mul(YZ, ZZ);                                            // [2]   Y Z^3
+  const Fq tZ = fp_mul(t3, ZZ);                                           // [2]   3 X^2 Z^2
+  const Fq m = fp_mul(t3, T.X);                                           // [2]   3 X^3
+  line[0] = fp_sub<FqParams, 4>(m, fp_dbl(YY));                           // [6]   3 X^3 - 2 Y^2          (2 Y^2 is [4])
+  line[1] = fp_mul(fp_dbl(A), c.yq4n);                                    // [2]   (2 Y Z^3)(-yQ/4)
+  line[2] = fp_mul(tZ, c.xq4);                                            // [2]   (-3 X^2 Z^2)(-xQ/4)
+  if (done) miller_identity_line(line);
+  const Fq S = fp_mul(T.X, YY);                                           // [2]   X Y^2
+  const Fq F = fp_sqr(t3);                                                // [2]
+  const Fq D = fp_dbl(fp_dbl(S));                                         // [8]   4 X Y^2
+  const Fq X3 = fp_sub<FqParams, 16>(F, fp_dbl(D));                       // [18]  F - 2 D                (2 D is [16])
+  const Fq DX = fp_sub_k<FqParams, 32>(D, X3);                            // [40]  D - X3                 (X3 is [18] <= 32)
+  const Fq nY8 = fp_sub<FqParams, 16>(fp_zero<FqParams>(), fp_dbl(fp_dbl(fp_dbl(YY))));   // [16]  -8 Y^2  (8 Y^2 is [16])
+  T.Y = fp_mul2(t3, DX, nY8, YY);                                         // [2]   3 X^2 (D - X3) - 8 Y^4:  6 x 40 + 16 x 2 = 272 p^2
+  T.X = X3;
+  T.Z = fp_dbl(YZ);                                                       // [4]
+}
+
+// line(T, P)(psi(Q)) scaled by D = Z (x2 Z^2 - X) (pairing_host.hpp miller_add), then T <- T + P (madd).
+// Returns true when T = +-P (H = 0): the line is vertical, the step contributes 1 and the pair is done - for points of order r
+// that is the last addition of the loop and nothing else.
+ZK_HD ZK_INL bool miller_add_step(MillerPoint& T, const MillerConst& c, bool done, Fq* line) {
+  const Fq ZZ = fp_sqr(T.Z);                                              // [2]
+  const Fq U = fp_mul(c.px, ZZ);                                          // [2]
+  const Fq ZZZ = fp_mul(ZZ, T.Z);                                         // [2]
+  const Fq W = fp_mul(c.py, ZZZ);                                         // [2]
+  const Fq H = fp_mul(fp_sub_k<FqParams, 32>(U, T.X), fp_one<FqParams>());  // [2]  x2 Z^2 - X ([34], X is [18] <= 32) brought back below 2 p
+  const Fq N = fp_sub<FqParams, 4>(W, T.Y);                               // [6]   y2 Z^3 - Y              (Y is [4])
+  done = done || fp_is_zero_2p(H);
+  const Fq D = fp_mul(T.Z, H);                                            // [2]
+  const Fq npy = fp_sub<FqParams, 2>(fp_zero<FqParams>(), c.py);          // [2]
+  line[0] = fp_mul2(N, c.px, D, npy);                                     // [2]   N x2 - D y2:  6 x 2 + 2 x 2 = 16 p^2
+  line[1] = fp_mul(D, c.yq4n);                                            // [2]   D (-yQ/4)
+  line[2] = fp_mul(N, c.xq4);                                             // [2]   (-N)(-xQ/4)
+  if (done) miller_identity_line(line);
+  const Fq HH = fp_sqr(H);                                                // [2]
+  const Fq HHH = fp_mul(HH, H);                                           // [2]
+  const Fq V = fp_mul(T.X, HH);                                           // [2]
+  const Fq NN = fp_sqr(N);                                                // [2]
+  const Fq X3 = fp_sub_sub2<FqParams, 8>(NN, HHH, V);                     // [10]  N^2 - H^3 - 2 V         (H^3 + 2 V is [6] <= 8)
+  const Fq VX = fp_sub<FqParams, 16>(V, X3);                              // [18]                          (X3 is [10] <= 16)
+  const Fq nY = fp_sub<FqParams, 4>(fp_zero<FqParams>(), T.Y);            // [4]
+  T.Y = fp_mul2(N, VX, nY, HHH);                                          // [2]   N (V - X3) - Y H^3:  6 x 18 + 4 x 2 = 116 p^2
+  T.X = X3;
+  T.Z = D;                                                                // [2]
+  return done;
+}
+
+}  // namespace zkhip

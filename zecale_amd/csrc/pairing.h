@@ -1,0 +1,27 @@
+// Internal interface of the pairing engine (pairing.hip).  The public C ABI is include/zkhip.h.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/zkhip.h"
+
+namespace zkhip {
+
+// A stream and the device work space of one batch in flight, plus (verifier handles) the key: everything a zkhip_verifier owns.
+// Lives on the device that was current when it was made; the caller binds its thread to that device before every call.
+struct PairingCtx;
+
+// vk_* null: a context for pairing_products only.  Otherwise the key of zkhip_verifier_new (ABI limbs, host memory).
+int pairing_ctx_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc,
+                    size_t n_inputs, PairingCtx** out, char* errbuf, size_t errlen);
+void pairing_ctx_free(PairingCtx* c);
+size_t pairing_ctx_num_inputs(const PairingCtx* c);
+
+// out[i] = prod_{p < pairs} t(g1[i][p], g2[i][p]), reduced GT value, 6 x 12 ABI limbs.  pairs in 1 .. 4.
+int pairing_products(PairingCtx* c, const uint64_t* g1, const uint64_t* g2, int pairs, size_t count, uint64_t* out, char* errbuf, size_t errlen);
+// ok[i] = e(A_i, B_i) e(acc_i, -g2) e(alpha, -beta) e(C_i, -delta) == 1
+int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, uint8_t* ok, char* errbuf, size_t errlen);
+// op 0: a b, 1: a^2, 2: a (b0 + b3 w^3 + b4 w^4) through the lane bodies of pairing.cuh; a, b, out: n x 72 ABI limbs
+int pairing_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen);
+
+}  // namespace zkhip

@@ -103,8 +103,8 @@ inline void miller_add(MillerPair& m, Fq6& f) {
   m.X = X3; m.Y = Y3; m.Z = D;
 }
 
-// prod_i t(P_i, Q_i) == 1 ?   points affine (x, y) in ABI limbs; infinity (all zero) contributes 1.
-inline bool pairing_product_is_one(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
+// prod_i t(P_i, Q_i), the reduced value.   points affine (x, y) in ABI limbs; infinity (all zero) contributes 1.
+inline Fq6 pairing_product_value(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
   std::vector<MillerPair> ms;
   HFq quarter_neg = HFq::from_u64(4).inv().neg();    // -1/4
   for (size_t i = 0; i < g1.size(); i++) {
@@ -126,7 +126,12 @@ inline bool pairing_product_is_one(const std::vector<const uint64_t*>& g1, const
     if ((r[i / 64] >> (i % 64)) & 1)
       for (auto& m : ms) if (!m.done) miller_add(m, f);
   }
-  return f.pow_limbs(FqParams::FINAL_EXP, FqParams::FINAL_EXP_LIMBS).is_one();
+  return f.pow_limbs(FqParams::FINAL_EXP, FqParams::FINAL_EXP_LIMBS);
+}
+
+// prod_i t(P_i, Q_i) == 1 ?
+inline bool pairing_product_is_one(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
+  return pairing_product_value(g1, g2).is_one();
 }
 
 }  // namespace host

@@ -15,6 +15,7 @@
 #include "ntt.h"
 #include "qap.h"
 #include "pairing_host.hpp"
+#include "pairing.h"
 #include "witness.h"
 #include <chrono>
 #include <condition_variable>
@@ -42,6 +43,11 @@ struct zkhip_bases {
 
 struct zkhip_r1cs {
   R1csDev* dev;
+  int device;
+};
+
+struct zkhip_verifier {
+  PairingCtx* ctx;
   int device;
 };
 
@@ -1572,6 +1578,63 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
   std::vector<const uint64_t*> p2 = {proof_affine + 24, neg_g2, neg_beta, neg_delta};
   *ok = pairing_product_is_one(p1, p2) ? 1 : 0;
   return ZKHIP_OK;
+}
+
+// ---- Groth16 verification in batches on the device (pairing.hip)
+int zkhip_verifier_new(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                       size_t n_inputs, zkhip_verifier** out) {
+  if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called (the pairing kernels are the only batch verifier)");
+  BIND_CUR();
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  PairingCtx* ctx = nullptr;
+  const int rc = pairing_ctx_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, &ctx, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  *out = new zkhip_verifier{ctx, cur_dev()};
+  return ZKHIP_OK;
+}
+size_t zkhip_verifier_num_inputs(const zkhip_verifier* v) { return v ? pairing_ctx_num_inputs(v->ctx) : 0; }
+int zkhip_verifier_verify_batch(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* ok) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (count == 0) return ZKHIP_OK;
+  if (!proofs_affine || !ok || (pairing_ctx_num_inputs(v->ctx) && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  BIND(v);
+  return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, ok, t_err, sizeof t_err);
+}
+void zkhip_verifier_free(zkhip_verifier* v) {
+  if (!v) return;
+  if (bind_dev(v->device) == ZKHIP_OK) pairing_ctx_free(v->ctx);
+  delete v;
+}
+
+int zkhip_internal_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  BIND_CUR();
+  if (op < 0 || op > 2 || (n && (!a || !b || !out)) || n > (1u << 20)) return fail(ZKHIP_ERR_ARG, "op 0 (mul), 1 (sqr) or 2 (mul_line), at most 2^20 sets");
+  if (n == 0) return ZKHIP_OK;
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return pairing_fq6_selftest(op, a, b, n, out, t_err, sizeof t_err);
+}
+
+int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out) {
+  if ((route != 0 && route != 1) || pairs_per_product < 1 || pairs_per_product > 4) return fail(ZKHIP_ERR_ARG, "route 0 (host) or 1 (GPU), 1 .. 4 pairs per product");
+  if (count && (!g1 || !g2 || !out)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (count == 0) return ZKHIP_OK;
+  if (route == 0) {
+    for (size_t i = 0; i < count; i++) {
+      std::vector<const uint64_t*> p1, p2;
+      for (size_t p = 0; p < pairs_per_product; p++) { p1.push_back(g1 + (i * pairs_per_product + p) * 24); p2.push_back(g2 + (i * pairs_per_product + p) * 24); }
+      const host::Fq6 v = host::pairing_product_value(p1, p2);
+      for (int k = 0; k < 6; k++) v.c[k].to_limbs(out + i * 72 + k * 12);
+    }
+    return ZKHIP_OK;
+  }
+  if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called");
+  BIND_CUR();
+  PairingCtx* ctx = nullptr;
+  int rc = pairing_ctx_new(nullptr, nullptr, nullptr, nullptr, 0, &ctx, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  rc = pairing_products(ctx, g1, g2, (int)pairs_per_product, count, out, t_err, sizeof t_err);
+  pairing_ctx_free(ctx);
+  return rc;
 }
 
 int zkhip_groth16_setup(const zkhip_r1cs_desc* cs, const uint64_t tau_m[6], const uint64_t alpha_m[6], const uint64_t beta_m[6],

@@ -39,6 +39,7 @@ EXPORTS = [
     "zkhip_aggregator_app_new", "zkhip_aggregator_app_free", "zkhip_aggregator_app_num_constants", "zkhip_aggregator_app_constants", "zkhip_aggregator_app_mask",
     "zkhip_aggregator_witness_app", "zkhip_groth16_prove_app", "zkhip_prover_prove_app", "zkhip_prover_prove_app_dev", "zkhip_gpu_witness_run_batched_app",
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
+    "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product",
 ]
 
 
@@ -196,6 +197,13 @@ def load():
     lib.zkhip_aggregator_pipeline_submit.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, ctypes.POINTER(ctypes.c_uint64)]
     lib.zkhip_aggregator_pipeline_wait.argtypes = [ctypes.c_void_p, ctypes.c_uint64, c_u64p, c_u64p]
     lib.zkhip_aggregator_pipeline_free.argtypes = [ctypes.c_void_p]
+    lib.zkhip_verifier_new.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, vpp]
+    lib.zkhip_verifier_num_inputs.argtypes = [ctypes.c_void_p]
+    lib.zkhip_verifier_num_inputs.restype = ctypes.c_size_t
+    lib.zkhip_verifier_verify_batch.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.zkhip_verifier_free.argtypes = [ctypes.c_void_p]
+    lib.zkhip_internal_fq6_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
+    lib.zkhip_internal_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
     _lib = lib
     return lib
 
@@ -666,6 +674,61 @@ def groth16_verify(vk, inputs, proof):
     _check(load().zkhip_groth16_verify(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), _p(inp), inp.shape[0],
                                        _p(c(proof)), ctypes.byref(ok)))
     return bool(ok.value)
+
+
+# the batch verifier's kernels (zecale_amd/csrc/pairing.cuh / pairing.hip): a verification owns eight lanes, so one wave holds
+# VERIFIER_GROUP of them and one 128-thread workgroup VERIFIER_WORKGROUP (tests size their batches around both)
+VERIFIER_GROUP = 8
+VERIFIER_WORKGROUP = 16
+
+
+class Verifier:
+    """Groth16 verification in batches on the GPU (zkhip_verifier): the pairing of groth16_verify as gfx950 kernels.  vk as for
+    groth16_verify.  The handle owns its stream and work space on the calling thread's device; one batch in flight per handle,
+    several handles - one host thread each - run side by side.  Points must be on their curves and of order r (or infinity):
+    unlike groth16_verify this route checks nothing."""
+
+    def __init__(self, vk):
+        c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+        abc = c(vk["ABC"]).reshape(-1, 24)
+        self.handle = ctypes.c_void_p()
+        _check(load().zkhip_verifier_new(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), abc.shape[0] - 1, ctypes.byref(self.handle)))
+        self.n_inputs = int(load().zkhip_verifier_num_inputs(self.handle))
+
+    def verify_batch(self, inputs, proofs):
+        """inputs: count x n_inputs x 6 limbs; proofs: count x 72 limbs.  Returns a bool array, one verdict per proof."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        ok = np.zeros(pr.shape[0], dtype=np.uint8)
+        _check(load().zkhip_verifier_verify_batch(self.handle, _p(inp), _p(pr), pr.shape[0], ok.ctypes.data))
+        return ok.astype(bool)
+
+    def free(self):
+        if self.handle:
+            load().zkhip_verifier_free(self.handle)
+            self.handle = None
+
+
+def fq6_selftest(op, a, b):
+    """Test hook: the pairing kernels' per-lane Fq6 bodies.  op "mul" / "sqr" / "mul_line" (b_0 + b_3 w^3 + b_4 w^4);
+    a, b: n x 6 x 12 ABI limbs; returns n x 6 x 12 limbs."""
+    x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 6, 12)
+    y = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 6, 12)
+    assert x.shape == y.shape
+    out = np.zeros_like(x)
+    _check(load().zkhip_internal_fq6_selftest({"mul": 0, "sqr": 1, "mul_line": 2}[op], _p(x), _p(y), x.shape[0], _p(out)))
+    return out
+
+
+def pairing_product(route, g1, g2):
+    """Test hook: reduced GT values of products of pairings.  g1, g2: count x pairs x 24 limbs (pairs <= 4); route "host" or "gpu".
+    Returns count x 6 x 12 ABI limbs."""
+    x = np.ascontiguousarray(g1, dtype=np.uint64)
+    y = np.ascontiguousarray(g2, dtype=np.uint64)
+    assert x.ndim == 3 and x.shape == y.shape and x.shape[2] == 24
+    out = np.zeros((x.shape[0], 6, 12), dtype=np.uint64)
+    _check(load().zkhip_internal_pairing_product({"host": 0, "gpu": 1}[route], _p(x), _p(y), x.shape[1], x.shape[0], _p(out)))
+    return out
 
 
 def bls12_377_groth16_verify(nested_vk, inputs, proof):
