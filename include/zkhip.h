@@ -564,6 +564,15 @@ int zkhip_measure_ntt(unsigned log_d, int dir, int coset, int batch, int reps, d
  * receives n x { a b / R, a^2 / R, (a b + c d) / R } in the device's own form (R = 2^783 / 2^406).  Operands must respect the
  * bodies' contract (limbs below 2^29 except the top one, products below 2^10 R p). */
 int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out);
+/* Test hooks of the Edwards accumulation's lockstep route (no counterpart).  A single MSM over a table in the Edwards model always
+ * enqueues two accumulations, one bucket per lane (k_accumulate_edw_lock) and sliced (k_accumulate_edw); a word the device writes
+ * per launch decides which of them runs.
+ * set_lockstep: mode 0 = every launch sliced, 1 = the device decides, -1 = the environment (ZKHIP_LOCKSTEP); min_buckets = the
+ * non-empty buckets a launch needs for the lockstep route (-1: two waves for every SIMD of the chip; tests on small sets lower it).
+ * last_acc_path: the word of the launch zkhip_last_accumulate_ms was read from, copied back when this is called and never
+ * otherwise: 1 lockstep, 0 sliced, -1 not an Edwards launch. */
+int zkhip_internal_set_lockstep(int mode, int min_buckets);
+int zkhip_internal_last_acc_path(int* out);
 /* Test hooks of the pairing kernels (no counterpart).
  * fq6_selftest: n independent operand sets through the per-lane bodies of pairing.cuh inside a real kernel, eight lanes per set:
  * op 0 = a b, 1 = a^2, 2 = a (b_0 + b_3 w^3 + b_4 w^4) (the sparse line product; b's other coefficients are ignored) in

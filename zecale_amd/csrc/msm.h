@@ -56,6 +56,9 @@ struct MsmCtx {      // all zeros: no plan
   size_t hist_len;
   uint32_t *counts, *offsets, *block_tot, *entries;
   uint32_t* goff;       // slice weights in front of every bucket (nb + 1 values): see k_accumulate
+  uint32_t *order, *ord_hist;   // Edwards launches (k_bucket_order): the bucket indices by count, descending (nb values), and the
+                                // counting sort's histogram [ZK_LOCK_KEYS][blocks]; null in plans that never serve one
+  uint32_t lock_min_live;       // non-empty buckets a launch needs for the lockstep route: two waves for every SIMD of the chip
   uint2* fix_list;      // (first, last) F slot of the buckets cut into more than four F pieces (k_accumulate -> k_fixup_fold)
   uint2* fix_short;     // (first F slot, number of F pieces) of the buckets with two to four (k_accumulate -> k_fixup_fold)
   uint32_t *buckets, *segS[2], *segR, *sumR[2], *Rlevels, *colS[2], *hilo;
@@ -90,6 +93,11 @@ struct MsmCtx {      // all zeros: no plan
 // tuning / test knob: number of batched-affine levels of the plans made from now on (-1: automatic)
 void msm_force_aff_levels(int levels);
 int msm_forced_aff_levels();
+// A/B and test knob of the lockstep route of the Edwards accumulation: mode 0 off, 1 on, -1 the environment (ZKHIP_LOCKSTEP);
+// min_buckets: the non-empty buckets a launch needs to take it (-1: the chip's own figure)
+void msm_force_lockstep(int mode, int min_buckets);
+// the route the plan's last launch took, read back from the device: 1 lockstep, 0 sliced, -1 not an Edwards launch
+int msm_last_acc_path(MsmCtx* ctx, int* out);
 // total_terms: upper bound on the terms (finite bases) of all K jobs of one launch together; 0 = K * max_n
 // adopt: two streams created by the caller beforehand (or null): the plan's main and side stream - the plan owns them from here on
 int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms = 0, hipStream_t* adopt = nullptr);

@@ -649,9 +649,90 @@ __global__ void __launch_bounds__(256, 2) k_accumulate(ZK_ACC_PARAMS) {
   accumulate_impl<NJ, false>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
                              dbg_times, prio_mode, prio_board, prio_tag);
 }
+// (fix_cnt[2] is the launch's lock_ok word, k_bucket_order below: 1 = k_accumulate_edw_lock has this launch, nothing to do here)
 __global__ void __launch_bounds__(256, 2) k_accumulate_edw(ZK_ACC_PARAMS) {
+  if (fix_cnt[2] == 1u) return;
   accumulate_impl<1, true>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
                            dbg_times, prio_mode, prio_board, prio_tag);
+}
+
+// ---- the lockstep route of the Edwards accumulation: one bucket per lane -----------------------------------------------------
+// With uniform scalars every bucket of a 2^20 launch holds 38 +- 6 entries.  Lanes that own whole BUCKETS of (nearly) equal
+// population open and close their runs in the same iteration: no bucket is cut (nothing to stitch), the boundary block of the
+// sliced kernel - paid by the whole wave whenever one lane is at a boundary - runs once per wave, and the loop carries an entry
+// index and a count, nothing else.  What thread-per-bucket lost to the spread of populations (k_accumulate's comment) is taken out
+// by ORDERING the buckets by population first: k_bucket_order is a counting sort of the bucket indices by count, descending, so
+// the 64 buckets of a wave differ by a count or two and the waves are dispatched longest first.
+// Whether a launch takes this route is decided ON THE DEVICE, per launch (the host never reads the word): lock_ok = 1 when no
+// bucket holds more than ZK_LOCK_CAP entries (a boolean-heavy witness puts a third of its entries in one bucket: never here) and
+// at least min_live buckets are non-empty (two waves for every SIMD).  Both routes are always enqueued; the one that is not
+// taken returns on its first instruction.
+// ZK_LOCK_CAP: at the headline's mean of 38 entries a bucket the largest of 2^19 binomial populations is about 70; 4 x 38 = 152,
+// rounded to a power of two: 128.  A launch whose mean population is past ~90 (narrow windows over many terms) stays sliced.
+#define ZK_LOCK_CAP 128u
+#define ZK_LOCK_KEYS (ZK_LOCK_CAP + 2u)
+// sort key of a bucket: 0 = over the cap (the order is not used then), CAP + 1 - count for counts 1 .. CAP, CAP + 1 = empty
+__device__ __forceinline__ uint32_t lock_key(uint32_t cnt) { return cnt > ZK_LOCK_CAP ? 0u : ZK_LOCK_CAP + 1u - cnt; }
+// PASS 0: ohist[key][block] = buckets of this block (1024 of them) with that key.  The host scans ohist (k_scan_*).
+// PASS 1: order[] = the bucket indices by key (inside a key: any order - the counts are equal); block 0 writes lock_ok.
+template <int PASS>
+__global__ void __launch_bounds__(256) k_bucket_order(const uint32_t* __restrict__ counts, uint32_t nb, uint32_t* __restrict__ ohist,
+                                                       uint32_t* __restrict__ order, uint32_t* __restrict__ lock_ok, uint32_t min_live, int enable) {
+  __shared__ uint32_t s_k[ZK_LOCK_KEYS];
+  const uint32_t tid = threadIdx.x, nblocks = gridDim.x;
+  for (uint32_t j = tid; j < ZK_LOCK_KEYS; j += 256) s_k[j] = PASS == 0 ? 0u : ohist[(size_t)j * nblocks + blockIdx.x];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t b = blockIdx.x * 1024u + (uint32_t)k * 256u + tid;
+    if (b < nb) {
+      const uint32_t pos = atomicAdd(&s_k[lock_key(counts[b])], 1u);
+      if (PASS == 1 && pos < nb) order[pos] = b;
+    }
+  }
+  if (PASS == 0) {
+    __syncthreads();
+    for (uint32_t j = tid; j < ZK_LOCK_KEYS; j += 256) ohist[(size_t)j * nblocks + blockIdx.x] = s_k[j];
+  } else if (blockIdx.x == 0 && tid == 0) {
+    // (scanned ohist: [1][0] = the buckets over the cap, [CAP + 1][0] = the non-empty buckets)
+    const uint32_t over = ohist[nblocks], live = ohist[(size_t)(ZK_LOCK_CAP + 1u) * nblocks];
+    *lock_ok = (enable && over == 0u && live >= min_live) ? 1u : 0u;
+  }
+}
+
+// Lane t owns bucket order[t].  The order is descending, so the wave's trip count is its first lane's count; a lane whose own
+// count is reached sits out the remaining iterations (a count or two, at most).  Waves of empty buckets - the tail of the order -
+// leave without touching a slot: the cleared Z words keep meaning "empty".  No pacing board here: the waves of a launch have
+// different lengths and are dispatched longest first, a SIMD's two waves are never a pair that should end together.
+__global__ void __launch_bounds__(256, 2) k_accumulate_edw_lock(const EdwPacked* __restrict__ etab, const uint32_t* __restrict__ entries,
+                                                                 const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                 const uint32_t* __restrict__ order, uint32_t nb, uint32_t* __restrict__ slots,
+                                                                 uint32_t stride, const uint32_t* __restrict__ lock_ok) {
+  if (*lock_ok == 0u) return;
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  __shared__ uint32_t lds_zz[27 * ZK_LDS_STRIDE], lds_zzz[27 * ZK_LDS_STRIDE], lds_x[24 * ZK_LDS_STRIDE];
+  uint32_t* zz = lds_zz + threadIdx.x;
+  uint32_t* zzz = lds_zzz + threadIdx.x;
+  uint32_t* xs = lds_x + threadIdx.x;
+  const uint32_t b = t < nb ? order[t] : 0u;
+  const uint32_t cnt = t < nb ? counts[b] : 0u;
+  const uint32_t trip = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt);
+  if (trip == 0u) return;
+  const uint32_t off = offsets[b];
+  Fq ty;
+  edw_set_identity(xs, zz, zzz, ty);
+  uint32_t e_next = cnt ? entries[off] : 0u;
+  for (uint32_t j = 0; j < trip; j++) {
+    if (j < cnt) {
+      const uint32_t e = e_next;
+      if (j + 1 < cnt) e_next = entries[off + j + 1];   // fetched a whole addition ahead of its use
+      edw_madd_lds_regy(xs, zz, zzz, ty, etab + (e & 0x7fffffffu), (e >> 31) != 0);
+    }
+  }
+  if (cnt) {
+    XyzzRef acc = make_slot_ref(slots, stride, b);
+    ZK_CLOSE_RUN(acc, xs, zz, zzz, ty);
+  }
 }
 
 // chi for every entry of a window table (levels x n points): the precomputed Edwards table.  Entries at infinity hold zeros; *bad
@@ -938,6 +1019,7 @@ template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_fixup_fold(ZK_F
   fixup_fold_impl<QUAD, false>(cnt, list_short, list_long, short_blocks, nb, slots, stride);
 }
 template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_fixup_fold_edw(ZK_FOLD_PARAMS) {
+  if (cnt[2] == 1u) return;         // (lock_ok: the lockstep route cut no bucket)
   fixup_fold_impl<QUAD, true>(cnt, list_short, list_long, short_blocks, nb, slots, stride);
 }
 
@@ -980,7 +1062,10 @@ __device__ __forceinline__ void fixup_impl(ZK_FIXUP_PARAMS) {
   mem_st(dst, CX, lds_ld_packed(xs)); mem_st(dst, CY, ty); mem_st(dst, CZZ, lds_ld(zz)); mem_st(dst, CZZZ, lds_ld(zzz));
 }
 __global__ void __launch_bounds__(256, 2) k_fixup(ZK_FIXUP_PARAMS) { fixup_impl<false>(offsets, counts, goff, nb, S_host, tight, T, slots, stride, wf); }
-__global__ void __launch_bounds__(256, 2) k_fixup_edw(ZK_FIXUP_PARAMS) { fixup_impl<true>(offsets, counts, goff, nb, S_host, tight, T, slots, stride, wf); }
+__global__ void __launch_bounds__(256, 2) k_fixup_edw(ZK_FIXUP_PARAMS, const uint32_t* __restrict__ lock_ok) {
+  if (*lock_ok == 1u) return;       // (the lockstep route cut no bucket)
+  fixup_impl<true>(offsets, counts, goff, nb, S_host, tight, T, slots, stride, wf);
+}
 
 // Segment pass of the bucket reduction.  in: n_in items (XYZZ limb-major, stride n_in), grouped in
 // runs of L.  For segment t: S_t = sum_u item[tL+u],  R_t = sum_u (u + o) item[tL+u]   (o in {0,1}).
@@ -1493,6 +1578,28 @@ static int choose_aff_levels(size_t m_entries, size_t nb) {
   return forced >= 0 ? forced : 0;
 }
 
+// The lockstep route of the Edwards accumulation (k_accumulate_edw_lock): ZKHIP_LOCKSTEP=0|1, read once; 0 forces every launch's
+// lock_ok word to 0 (the sliced route).  msm_force_lockstep overrides the environment (A/B runs and tests: -1 = the environment
+// again) and, with min_buckets >= 0, the number of non-empty buckets a launch needs (-1 = two waves for every SIMD of the chip).
+#define ZK_LOCKSTEP_DEFAULT 1
+static int g_lock_forced = -1, g_lock_min_live = -1;
+void msm_force_lockstep(int mode, int min_buckets) { g_lock_forced = mode < 0 ? -1 : (mode ? 1 : 0); g_lock_min_live = min_buckets < 0 ? -1 : min_buckets; }
+static int lockstep_mode() {
+  static const int env_mode = env_int("ZKHIP_LOCKSTEP", ZK_LOCKSTEP_DEFAULT, 0, 1);
+  return g_lock_forced >= 0 ? g_lock_forced : env_mode;
+}
+// the lock_ok word of the plan's last launch (1: the lockstep route ran, 0: the sliced one; -1: not an Edwards launch), copied
+// back here and nowhere else: a test hook, synchronises the device
+int msm_last_acc_path(MsmCtx* ctx, int* out) {
+  *out = -1;
+  if (!ctx->planned || !ctx->win_edw || !ctx->order) return ZKHIP_OK;
+  uint32_t v = 0;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(&v, ctx->block_tot + 2, 4, hipMemcpyDeviceToHost));
+  *out = (int)v;
+  return ZKHIP_OK;
+}
+
 // One event per device, recorded the first time a plan is made there - and again whenever the caller asks (msm_time_base_reset):
 // the origin of the absolute launch times of k_accumulate.  hipEventElapsedTime returns FLOAT milliseconds: 1 us of resolution
 // lasts ~8 s from the origin, 0.06 ms an hour - a caller that compares intervals re-bases at the start of its timed region.
@@ -1639,7 +1746,21 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   HIP_TRY(hipMalloc(&ctx->offsets, nb * 4));
   HIP_TRY(hipMalloc(&ctx->goff, (nb + 1) * 4));
   if ((size_t)ctx->Wd * total_terms * ZK_W_NEXT >= ((size_t)1 << 32)) return ZKHIP_ERR_ARG;      // slice weights are 32-bit
-  HIP_TRY(hipMalloc(&ctx->block_tot, ((nb > ctx->hist_len ? nb : ctx->hist_len) / 1024 + 2) * 4));
+  // (block totals of the scans; afterwards [0], [1] = the lengths of the two stitching lists, [2] = lock_ok)
+  const size_t ord_m = (size_t)ZK_LOCK_KEYS * nblk(nb, 1024);
+  {
+    size_t scan_m = nb > ctx->hist_len ? nb : ctx->hist_len;
+    if (ord_m > scan_m) scan_m = ord_m;
+    HIP_TRY(hipMalloc(&ctx->block_tot, (scan_m / 1024 + 4) * 4));
+  }
+  if (merged == 1 && K == 1) {      // a plan that may serve Edwards launches: the lockstep route's bucket order
+    HIP_TRY(hipMalloc(&ctx->order, nb * 4));
+    HIP_TRY(hipMalloc(&ctx->ord_hist, ord_m * 4));
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    ctx->lock_min_live = 64u * 2u * 4u * (uint32_t)(cus > 0 ? cus : 256);     // two waves for each of a CU's four SIMDs
+  }
   HIP_TRY(hipMalloc(&ctx->entries, ((size_t)ctx->Wd * total_terms + 1) * 4));
   // batched-affine levels: bounds on the level sizes, the buffers of their outputs
   {
@@ -1713,7 +1834,7 @@ void msm_plan_free(MsmCtx* ctx) {
                   ctx->segS[0], ctx->segS[1], ctx->segR, ctx->sumR[0], ctx->sumR[1], ctx->Rlevels, ctx->win_abi,
                   ctx->colS[0], ctx->colS[1], ctx->hilo, ctx->pbuf[0], ctx->pbuf[1], ctx->aff_scratch,
                   ctx->lcnt[0], ctx->lcnt[1], ctx->lcnt[2], ctx->lcnt[3], ctx->loff[0], ctx->loff[1], ctx->loff[2], ctx->loff[3],
-                  ctx->fix_list, ctx->fix_short, ctx->dbg_times, ctx->goff, ctx->prio_board};
+                  ctx->fix_list, ctx->fix_short, ctx->dbg_times, ctx->goff, ctx->prio_board, ctx->order, ctx->ord_hist};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (ctx->win_host) (void)hipHostFree(ctx->win_host);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1853,6 +1974,17 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
     hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)gb);
     hipLaunchKernelGGL(k_scan_add, dim3(gb), dim3(256), 0, st, ctx->goff, ctx->block_tot, nb + 1);
   }
+  // the lockstep route's bucket order and its go / no-go word (block_tot[2], written last: the scans above and below use block_tot)
+  if (edw) {
+    const unsigned ob = nblk(nb, 1024), os = nblk((size_t)ZK_LOCK_KEYS * ob, 1024);
+    const int lock_on = lockstep_mode();
+    const uint32_t min_live = g_lock_min_live >= 0 ? (uint32_t)g_lock_min_live : ctx->lock_min_live;
+    hipLaunchKernelGGL(k_bucket_order<0>, dim3(ob), dim3(256), 0, st, cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
+    hipLaunchKernelGGL(k_scan_local, dim3(os), dim3(256), 0, st, ctx->ord_hist, ctx->ord_hist, ctx->block_tot, (size_t)ZK_LOCK_KEYS * ob);
+    hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)os);
+    hipLaunchKernelGGL(k_scan_add, dim3(os), dim3(256), 0, st, ctx->ord_hist, ctx->block_tot, (size_t)ZK_LOCK_KEYS * ob);
+    hipLaunchKernelGGL(k_bucket_order<1>, dim3(ob), dim3(256), 0, st, cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
+  }
   HIP_TRY(hipMemsetAsync(ctx->block_tot, 0, 8, st));   // block_tot[0], [1] are reused as the lengths of the two stitching lists (scans are done)
   // slice length for THIS n (the plan's slot array is sized for max_n)
   uint32_t S_run, T_run;
@@ -1895,10 +2027,12 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   const uint32_t* acc_entries = dense ? nullptr : ctx->entries;
   static const int acc_prio = env_int("ZKHIP_ACC_PRIO", 1, 0, 2);      // 2: by quarters of the slice only (no board)
   const uint32_t prio_tag = (++ctx->prio_seq & 0x7fffu) + 1u;     // (see k_accumulate: the wave that is behind asks for priority; 0 = the arbiter's own order)
-  if (edw)
+  if (edw) {
+    hipLaunchKernelGGL(k_accumulate_edw_lock, dim3(nblk(nb, 256)), dim3(256), 0, st, jobs[0].edw, ctx->entries, cur_off, cur_cnt, ctx->order, (uint32_t)nb,
+                       ctx->buckets, ctx->slot_stride, ctx->block_tot + 2);
     hipLaunchKernelGGL(k_accumulate_edw, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off, cur_cnt, ctx->goff,
                        (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
-  else if (ctx->K == 1 || dense)
+  } else if (ctx->K == 1 || dense)
     hipLaunchKernelGGL(k_accumulate<1>, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off, cur_cnt, ctx->goff,
                        (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
   else
@@ -1918,8 +2052,12 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
     hipLaunchKernelGGL(fold, dim3(sblocks + 512), dim3(256), 0, st, ctx->block_tot, ctx->fix_short, ctx->fix_list, sblocks, (uint32_t)nb, ctx->buckets,
                        ctx->slot_stride);
   }
-  hipLaunchKernelGGL(edw ? k_fixup_edw : k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight,
-                     T_run, ctx->buckets, ctx->slot_stride, wf);
+  if (edw)
+    hipLaunchKernelGGL(k_fixup_edw, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets,
+                       ctx->slot_stride, wf, ctx->block_tot + 2);
+  else
+    hipLaunchKernelGGL(k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets,
+                       ctx->slot_stride, wf);
   HIP_TRY(hipGetLastError());
 
   // ---- bucket reduction -------------------------------------------------------------------------------

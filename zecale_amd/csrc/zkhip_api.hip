@@ -2472,6 +2472,24 @@ int zkhip_measure_ntt(unsigned log_d, int dir, int coset, int batch, int reps, d
   return ntt_measure((int)log_d, dir, coset, batch, reps, ms_per_transform, t_err, sizeof t_err);
 }
 
+// Test hooks of the lockstep route of the Edwards accumulation (msm.hip k_accumulate_edw_lock)
+int zkhip_internal_set_lockstep(int mode, int min_buckets) {
+  msm_force_lockstep(mode, min_buckets);
+  return ZKHIP_OK;
+}
+int zkhip_internal_last_acc_path(int* out) {
+  if (!out) return fail(ZKHIP_ERR_ARG, "null argument");
+  *out = -1;
+  const int dev = t_prove_dev >= 0 ? t_prove_dev : cur_dev();
+  if (dev < 0) return ZKHIP_OK;
+  { int rc_ = bind_dev(dev); if (rc_ != ZKHIP_OK) return rc_; }
+  std::lock_guard<std::mutex> lk(g.dev[dev].mu);
+  MsmCtx* cx = g.dev[dev].ps.last_acc_ctx;
+  if (!cx) return ZKHIP_OK;
+  const int rc = msm_last_acc_path(cx, out);
+  return rc == ZKHIP_OK ? rc : ctx_fail(rc, cx);
+}
+
 int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out) {
   BIND_CUR();
   if ((field != 0 && field != 1) || (n && (!limbs_in || !limbs_out)) || n > (1u << 20)) return fail(ZKHIP_ERR_ARG, "field 0 (Fq) or 1 (Fr), at most 2^20 cases");

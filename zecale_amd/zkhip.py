@@ -39,7 +39,7 @@ EXPORTS = [
     "zkhip_aggregator_app_new", "zkhip_aggregator_app_free", "zkhip_aggregator_app_num_constants", "zkhip_aggregator_app_constants", "zkhip_aggregator_app_mask",
     "zkhip_aggregator_witness_app", "zkhip_groth16_prove_app", "zkhip_prover_prove_app", "zkhip_prover_prove_app_dev", "zkhip_gpu_witness_run_batched_app",
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
-    "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product",
+    "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path",
 ]
 
 
@@ -1412,6 +1412,19 @@ def last_accumulate_entries():
     """Mixed additions of the k_accumulate launch zkhip_last_accumulate_ms timed (the non-zero digits it sorted)."""
     out = ctypes.c_uint64(0)
     _check(load().zkhip_last_accumulate_entries(ctypes.byref(out)))
+    return int(out.value)
+
+
+def set_lockstep(mode, min_buckets=-1):
+    """Test / A-B knob of the Edwards accumulation's lockstep route (zkhip_internal_set_lockstep): mode 0 sliced, 1 the device decides,
+    -1 the environment (ZKHIP_LOCKSTEP); min_buckets: non-empty buckets a launch needs for it (-1: the chip's own figure)."""
+    _check(load().zkhip_internal_set_lockstep(int(mode), int(min_buckets)))
+
+
+def last_acc_path():
+    """The route the last single MSM's accumulation took, read back from the device: 1 lockstep, 0 sliced, -1 not an Edwards launch."""
+    out = ctypes.c_int(-1)
+    _check(load().zkhip_internal_last_acc_path(ctypes.byref(out)))
     return int(out.value)
 
 
