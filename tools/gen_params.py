@@ -123,6 +123,7 @@ def main():
     extra_q += arr("EDW_C1", mont(ep["c1"]))                        # -3 t^2 / 4
     extra_q += arr("EDW_C2", mont(ep["c2"]))                        # 3 t / 2
     extra_q += arr("EDW_THREE", mont(3))
+    extra_q += arr("EDW_DINV", mont(pow(ep["d"], -1, Q)))           # 1 / d: a bucket opened from a table point, T = (2 d x y) / d
     # psi's constants once more in the host's form: the window result of an Edwards launch is mapped back on the host (msm.hip edw_abi_to_jac)
     extra_q += arr("EDW_C1_64", limbs(ep["c1"] * Rabi_q % Q, 12, 64), "uint64_t", 3, "0x%016xull")
     extra_q += arr("EDW_C2_64", limbs(ep["c2"] * Rabi_q % Q, 12, 64), "uint64_t", 3, "0x%016xull")

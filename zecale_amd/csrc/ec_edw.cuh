@@ -84,6 +84,109 @@ __device__ __forceinline__ void edw_set_identity(uint32_t* xs, uint32_t* zs, uin
   ty = fp_one<FqParams>();
 }
 
+// ---- the lockstep kernel's own forms (msm.hip k_accumulate_edw_lock): the table point gathered a whole multiplication ahead ----
+// The sliced kernel's addition above gathers its point in three groups (ymx at step 0, ypx at step 1, t2d at step 2) and waits
+// for each within the step that issued it.  Here the 72 packed words of the point are in registers BEFORE the addition starts, in
+// the addition's own temporaries: T0 = ymx, T1 = ypx, T2 = t2d (words 0 .. 23 of each).  Each is consumed by the step that then
+// writes it (0: A, 1: E and H, 2: F and G - the roles of edw_madd_lds_regy) and they are refilled - with the NEXT entry's point -
+// before the last product, Z3 = F G, where T0, T1 are dead and T2, T3 have just been copied into the multiplier's operands: no
+// register beyond edw_madd_lds_regy's, no second buffer, and the gather has that whole product to arrive.  A negated entry swaps
+// the two source addresses (ymx <-> ypx) when the loads are issued; its t2d is not negated - F <-> G are selected instead, as above.
+// The addresses are formed where the loads are issued (the entry word passes through an empty asm statement: hoisted out of the
+// rolled loop, three 64-bit pointers would be live across every multiplication of the addition).
+__device__ __forceinline__ void edw_pre_issue(Fq& T0, Fq& T1, Fq& T2, const EdwPacked* etab, uint32_t e) {
+  asm volatile("" : "+v"(e));
+  const char* p = reinterpret_cast<const char*>(etab + (e & 0x7fffffffu));         // (a table point is 18 x 16 bytes, 16-byte aligned)
+  const uint32_t sw = (e >> 31) * 96u;                                              // negated: ypx first
+  const zk_u32x4* a = reinterpret_cast<const zk_u32x4*>(p + sw);
+  const zk_u32x4* b = reinterpret_cast<const zk_u32x4*>(p + (96u - sw));
+  const zk_u32x4* c = reinterpret_cast<const zk_u32x4*>(p + 192);
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const zk_u32x4 u = a[j], v = b[j], w = c[j];
+    T0.l[4 * j] = u.x; T0.l[4 * j + 1] = u.y; T0.l[4 * j + 2] = u.z; T0.l[4 * j + 3] = u.w;
+    T1.l[4 * j] = v.x; T1.l[4 * j + 1] = v.y; T1.l[4 * j + 2] = v.z; T1.l[4 * j + 3] = v.w;
+    T2.l[4 * j] = w.x; T2.l[4 * j + 1] = w.y; T2.l[4 * j + 2] = w.z; T2.l[4 * j + 3] = w.w;
+  }
+}
+static_assert(offsetof(EdwPacked, ypx) == 96 && offsetof(EdwPacked, t2d) == 192, "edw_pre_issue addresses the coordinates by offset");
+
+// acc += the point in T0, T1, T2 (edw_pre_issue: already swapped when negated; neg selects F <-> G), the accumulator as in
+// edw_madd_lds_regy.  Step 0 loads and unpacks X once and forms both Y1 - X1 and Y1 + X1: the sum stays in ty ([4]; ty is dead
+// until step 5 writes Y3).  The last product, Z3 = F G, stands BEHIND the rolled loop of the other six, with a multiplier body of
+// its own: there the compiler sees that T0 .. T3 are dead, and the 72 words of the next point land in registers nobody holds
+// (inside the rolled loop every temporary is live at every step as far as the allocator can tell: the same code as a seventh
+// switch arm compiled to 256 VGPRs with 21 spilled; this form: 245, none - and only with the switches written as they are, six
+// cases and an unreachable default: with step 5 as the default arm the allocator spills 28).  Before that product the gather of
+// the next entry e1's point is issued when the lane has one, and behind it the load of the index after that one (entries[k2]
+// into e2, when has_e2): every load of an addition is in flight under a whole product, and the one wait of the next addition's
+// step 0 finds them all done.  Bounds as above.
+__device__ __forceinline__ void edw_madd_lds_pre(uint32_t* xs, uint32_t* zs, uint32_t* ts, Fq& ty, Fq& T0, Fq& T1, Fq& T2, bool neg,
+                                                 const EdwPacked* etab, uint32_t e1, bool has_e1, uint32_t& e2,
+                                                 const uint32_t* entries, uint32_t k2, bool has_e2) {
+  Fq T3;                  // (not initialised: written by step 2, read from step 3 on)
+#pragma unroll 1
+  for (int step = 0; step < 6; step++) {
+    Fq a, b;
+    switch (step) {
+      case 0: {                                                                                           // A = (Y1 - X1)(y2 - x2)
+        const Fq X = lds_ld_packed(xs);
+        a = fp_sub<FqParams, 2>(ty, X); ty = fp_add(ty, X); b = fp_unpack32<FqParams>(T0.l);
+        break;
+      }
+      case 1: a = ty; b = fp_unpack32<FqParams>(T1.l); break;                                             // B = (Y1 + X1)(y2 + x2)
+      case 2: a = lds_ld(ts); b = fp_unpack32<FqParams>(T2.l); break;                                     // C = T1 2d x2 y2
+      case 3: a = T1; b = fq_sel(neg, T3, T2); break;                                                     // X3 = E F
+      case 4: a = T1; b = T0; break;                                                                      // T3 = E H
+      case 5: a = fq_sel(neg, T2, T3); b = T0; break;                                                     // Y3 = G H
+      default: __builtin_unreachable();
+    }
+    Fq r = fp_mul(a, b);
+    switch (step) {
+      case 0: T0 = r; break;                                                                              // A
+      case 1: T1 = fp_sub<FqParams, 2>(r, T0); T0 = fp_add(r, T0); break;                                 // E = B - A, H = B + A [4]
+      case 2: {
+        const Fq D = fp_dbl(lds_ld(zs));                                                                  // [4]
+        T2 = fp_sub<FqParams, 2>(D, r);                                                                   // D - C [6]: F (-p: G)
+        T3 = fp_add(D, r);                                                                                // D + C [6]: G (-p: F)
+        break;
+      }
+      case 3: lds_st_packed(xs, r); break;
+      case 4: lds_st(ts, r); break;
+      case 5: ty = r; break;
+      default: __builtin_unreachable();
+    }
+  }
+  const Fq F = T2, G = T3;
+  if (has_e1) edw_pre_issue(T0, T1, T2, etab, e1);
+  if (has_e2) {
+    asm volatile("" : "+v"(k2));                                                                          // (as in edw_pre_issue)
+    e2 = entries[k2];
+  }
+  lds_st(zs, fp_mul(F, G));                                                                               // Z3 = F G
+}
+
+// A bucket's first entry is not added to the identity: the accumulator is SET to the point in T0, T1, T2 (already swapped when
+// negated), (X : Y : Z : T) = ((y + x) - (y - x) : (y + x) + (y - x) : 2 : (2 d x y) / d) = (2x : 2y : 2 : 2xy) - one product
+// instead of seven.  The lanes of a lockstep wave open together (iteration 0 is wave-uniform), so no lane waits for another's six
+// idle steps.  A negated entry negates t2d before the product (T = -2xy).  Bounds: the table's words are canonical [1], so
+// X = ypx - ymx + p [2], Y = ypx + ymx [2], Z = 2 in Montgomery form [2], T a product [2]: what step 0 of the addition
+// (fp_sub<2>) and the close of a one-entry bucket expect of stored coordinates.  The gather of e1's point is issued under the
+// product.
+__device__ __forceinline__ void edw_open_lds_pre(uint32_t* xs, uint32_t* zs, uint32_t* ts, Fq& ty, Fq& T0, Fq& T1, Fq& T2, bool neg,
+                                                 const EdwPacked* etab, uint32_t e1, bool has_e1) {
+  {
+    const Fq ymx = fp_unpack32<FqParams>(T0.l), ypx = fp_unpack32<FqParams>(T1.l);
+    lds_st_packed(xs, fp_sub_k<FqParams, 1>(ypx, ymx));
+    ty = fp_add(ypx, ymx);
+  }
+  lds_st(zs, fp_dbl(fp_one<FqParams>()));
+  Fq a = fp_unpack32<FqParams>(T2.l);
+  if (neg) a = fp_sub_k<FqParams, 1>(fp_zero<FqParams>(), a);                                              // [2]
+  if (has_e1) edw_pre_issue(T0, T1, T2, etab, e1);
+  lds_st(ts, fp_mul(a, fp_const<FqParams>(FqParams::EDW_DINV)));
+}
+
 // ---- full additions and doublings: the stitching and the bucket reduction of an Edwards launch (msm.hip, point model EDW) ----
 // Every array the reduction touches holds extended points in the X | Y | ZZ | ZZZ words (X | Y | Z | T).  A slot or item whose Z
 // words are ZERO is EMPTY - nothing was ever accumulated there (k_slots_clear_zz, pt_set_inf) - and counts as the neutral element:

@@ -719,14 +719,22 @@ __global__ void __launch_bounds__(256, 2) k_accumulate_edw_lock(const EdwPacked*
   const uint32_t trip = (uint32_t)__builtin_amdgcn_readfirstlane((int)cnt);
   if (trip == 0u) return;
   const uint32_t off = offsets[b];
-  Fq ty;
-  edw_set_identity(xs, zz, zzz, ty);
-  uint32_t e_next = cnt ? entries[off] : 0u;
-  for (uint32_t j = 0; j < trip; j++) {
+  // Entry j's table point is in T0, T1, T2 before iteration j starts (ec_edw.cuh edw_pre_issue): iteration j issues the gather of
+  // entry j + 1 and the load of entry j + 2's index under its last product, so the loop carries the entry it works on, the two
+  // behind it and the three temporaries that hold the point.  Every index load is guarded by the lane's own count - the last
+  // bucket ends where the entry array ends - and a lane that sits out loads nothing.
+  Fq ty, T0, T1, T2;           // (not initialised: written before they are read)
+  uint32_t e = cnt ? entries[off] : 0u;
+  uint32_t e1 = cnt > 1u ? entries[off + 1u] : 0u, e2 = cnt > 2u ? entries[off + 2u] : 0u;
+  // iteration 0 (wave-uniform): the bucket opens FROM its first table point, one product; a bucket of one entry closes from here
+  if (cnt) {
+    edw_pre_issue(T0, T1, T2, etab, e);                                             // (the one exposed gather of a wave)
+    edw_open_lds_pre(xs, zz, zzz, ty, T0, T1, T2, (e >> 31) != 0, etab, e1, cnt > 1u);
+  }
+  for (uint32_t j = 1; j < trip; j++) {
     if (j < cnt) {
-      const uint32_t e = e_next;
-      if (j + 1 < cnt) e_next = entries[off + j + 1];   // fetched a whole addition ahead of its use
-      edw_madd_lds_regy(xs, zz, zzz, ty, etab + (e & 0x7fffffffu), (e >> 31) != 0);
+      e = e1; e1 = e2;
+      edw_madd_lds_pre(xs, zz, zzz, ty, T0, T1, T2, (e >> 31) != 0, etab, e1, j + 1 < cnt, e2, entries, off + j + 2, j + 2 < cnt);
     }
   }
   if (cnt) {
