@@ -27,6 +27,7 @@
 #include "ec_edw.cuh"
 #include "host_field.hpp"
 #include "msm.h"
+#include "msm_plan.hpp"
 #include "wait.h"
 
 
@@ -1538,54 +1539,21 @@ int msm_field_selftest(int field, const uint32_t* in_host, size_t n, uint32_t* o
   } while (0)
 
 static inline unsigned nblk(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
-// Window layout: W = ceil(378 / c) windows tile exactly 378 bits; the top W*c - 378 of them get c-1 bits.
-static void window_layout(int c, uint16_t* off, uint8_t* bits) {
-  const int W = (378 + c - 1) / c, n_small = W * c - 378;
-  int bit = 0;
-  for (int w = 0; w < W; w++) {
-    int cw = (w >= W - n_small) ? c - 1 : c;
-    off[w] = (uint16_t)bit; bits[w] = (uint8_t)cw;
-    bit += cw;
-  }
-}
-
-// target number of entries per lane and machine fill (tuning knob; ZKHIP_SLICE_TARGET overrides for experiments).  Round 4, with
-// weighted slices and paced waves: 48 / 80 / 160 give 83.3-83.7 / 84.1 / 81.9-83.2 Mscalar/s in the 2^20 stream (slices of 38 / 76 /
-// 152 entries: half the boundary pieces to stitch at 76; one fill per launch at 152 loses the overlap of fills), 20.5-20.6 / 20.8-20.9
-// 2^20-proofs/s, the wrapping stream unchanged (one fill either way).
-static size_t slice_target() {
-  static size_t v = 0;
-  if (!v) {
-    const char* e = getenv("ZKHIP_SLICE_TARGET");
-    v = e ? (size_t)atoi(e) : 80;
-    if (v < 8 || v > 4096) v = 80;
-  }
-  return v;
-}
-
 static int env_int(const char* name, int dflt, int lo, int hi) {
   const char* e = getenv(name);
   if (!e) return dflt;
   int v = atoi(e);
   return (v < lo || v > hi) ? dflt : v;
 }
-// upper bound on the size of level l+1 given a bound on level l: ceil(n/2) summed over at most min(nb, m) non-empty buckets
-static size_t level_bound(size_t m, size_t nb) { return (m + (m < nb ? m : nb)) / 2; }
+// target number of entries per lane and machine fill (tuning knob, read once).  48 / 80 / 160 give 83.3-83.7 / 84.1 / 81.9-83.2 Mscalar/s
+// in the 2^20 stream: half the boundary pieces to stitch at 80; one fill per launch at 160 loses the overlap of fills
+static size_t slice_target() {
+  static const size_t v = (size_t)env_int("ZKHIP_SLICE_TARGET", 80, 8, 4096);
+  return v;
+}
 static int g_aff_forced = -2;      // -2: not set (environment, then automatic); -1: automatic; >= 0: that many levels
 void msm_force_aff_levels(int levels) { g_aff_forced = levels < -1 ? -1 : (levels > MSM_MAX_AFF_LEVELS ? MSM_MAX_AFF_LEVELS : levels); }
 int msm_forced_aff_levels() { return g_aff_forced == -2 ? env_int("ZKHIP_AFF_LEVELS", -1, 0, MSM_MAX_AFF_LEVELS) : g_aff_forced; }
-// How many batched-affine levels run before the XYZZ accumulation.  Automatic = NONE: measured on gfx950 (DESIGN.md section 5,
-// profiles/r02_affine_*), one level over the 10.2 M pairs of a 2^20-term MSM takes 7.3 ms where the XYZZ kernel spends 6.1 ms on
-// the same additions - 25 % fewer VALU instructions per addition, but 3.6 x the memory instructions (every operand is gathered
-// in the forward AND the backward pass) at two waves per SIMD.  The levels stay available (zkhip_set_affine_levels,
-// ZKHIP_AFF_LEVELS) and tested: they compute the same group element.
-static int choose_aff_levels(size_t m_entries, size_t nb) {
-  (void)m_entries; (void)nb;
-  int forced = msm_forced_aff_levels();
-  return forced >= 0 ? forced : 0;
-}
-
 // The lockstep route of the Edwards accumulation (k_accumulate_edw_lock): ZKHIP_LOCKSTEP=0|1, read once; 0 forces every launch's
 // lock_ok word to 0 (the sliced route).  msm_force_lockstep overrides the environment (A/B runs and tests: -1 = the environment
 // again) and, with min_buckets >= 0, the number of non-empty buckets a launch needs (-1 = two waves for every SIMD of the chip).
@@ -1693,12 +1661,7 @@ static void read_accumulate_times(MsmCtx* ctx) {
 
 int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms, hipStream_t* adopt) {
   memset(ctx, 0, sizeof *ctx);
-  // terms of ALL jobs of one launch sequence together: K * max_n unless the caller knows better (a proving key's five query vectors
-  // differ in length and a third of the B query is the point at infinity: the wrapping key has 192,664 finite bases where
-  // 5 * 65,535 = 327,675 would be planned - slices, boundary slots and the slot array's zero fill all scale with this bound)
-  if (total_terms == 0 || total_terms > (size_t)K * max_n) total_terms = (size_t)K * max_n;
-  if (total_terms < max_n && K == 1) total_terms = max_n;
-  ctx->total_terms = total_terms;
+  ctx->total_terms = total_terms = plan::total_terms(K, max_n, total_terms);
   (void)msm_time_base();
   if (K < 1 || K > MSM_MAX_JOBS || (!merged && K != 1)) return ZKHIP_ERR_ARG;
   ctx->K = K;
@@ -1708,12 +1671,11 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   if (c < 4 || c > (merged ? 22 : 18)) return ZKHIP_ERR_ARG;
   ctx->c = c;
   ctx->merged = merged;
-  ctx->Wd = (378 + c - 1) / c;   // scalars < 2^377, +1 bit for the signed-digit carry
-  if (merged == 2) ctx->Wd = 378 / (c + 1) + 2;      // width-(c+1) NAF: digits at least c+1 bits apart, +1 for the final carry
+  ctx->Wd = plan::digits(c, merged);
   ctx->W = merged ? K : ctx->Wd;
   // plain and merged plans share the balanced layout: a table's level w is 2^(off_w) P.  (A short top window would also
   // hurt a merged plan: its n digits of a few bits would all land in a handful of the shared buckets.)
-  window_layout(c, ctx->win_off, ctx->win_bits);
+  plan::window_layout(c, ctx->win_off, ctx->win_bits);
   ctx->B = (size_t)1 << (c - 1);
   ctx->max_n = max_n;
   ctx->logL = env_int("ZKHIP_SUM_LOGL", 2, 2, 5); ctx->L = 1 << ctx->logL;      // fan-in of the reduction trees (tuning knob; the R arrays are sized for L >= 4)
@@ -1732,105 +1694,60 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventBlockingSync | hipEventDisableTiming));
   if ((size_t)ctx->Wd * max_n >= ((size_t)1 << 31)) return ZKHIP_ERR_ARG;   // entry = 31-bit point index + sign
   if ((size_t)ctx->Wd * total_terms >= ((size_t)1 << 32)) return ZKHIP_ERR_ARG;  // positions in the entry list are 32-bit
-  // geometry of the bucket sort: parts of 2^LB buckets (LB <= 10: k_bucket_sort keeps a part's counters in LDS); small bucket
-  // windows get smaller parts so that k_bucket_sort still has about a thousand workgroups to spread over the chip
-  {
-    uint32_t LB = (uint32_t)(c - 1 < 10 ? c - 1 : 10);
-    const size_t want_parts = (size_t)env_int("ZKHIP_SORT_PARTS", 1024, 64, 8192);      // (tuning knob)
-    while (LB > 6 && (nb >> LB) < want_parts && (ctx->B >> (LB - 1)) * (merged ? 1 : (size_t)ctx->Wd) <= 4096) LB--;
-    ctx->sort_LB = LB;
-    ctx->sort_NP = (uint32_t)(ctx->B >> LB);
-    ctx->sort_bins = merged ? ctx->sort_NP : ctx->sort_NP * (uint32_t)ctx->Wd;
-    if ((size_t)ctx->sort_bins * 8 > 60 * 1024) return ZKHIP_ERR_ARG;             // LDS of k_digit_pass<1>: counters + bases
-    uint32_t tile = (uint32_t)env_int("ZKHIP_SORT_TILE", 1024, 256, 16384) & ~255u;      // scalars per block of k_digit_pass (tuning knob)
-    while ((max_n + tile - 1) / tile > 1024) tile *= 2;
-    ctx->sort_tile = tile;
-    const size_t nbx = (max_n + tile - 1) / tile;
-    ctx->hist_len = (nb >> LB) * (nbx ? nbx : 1) + 1;
-  }
+  const int sort_parts = env_int("ZKHIP_SORT_PARTS", 1024, 64, 8192), sort_tile = env_int("ZKHIP_SORT_TILE", 1024, 256, 16384);      // (tuning knobs)
+  if (!plan::sort_plan(c, merged, ctx->Wd, nb, max_n, sort_parts, sort_tile, ctx->sort_LB, ctx->sort_NP, ctx->sort_bins, ctx->sort_tile, ctx->hist_len)) return ZKHIP_ERR_ARG;
   HIP_TRY(hipMalloc(&ctx->hist, ctx->hist_len * 4));
-  HIP_TRY(hipMalloc(&ctx->pairs, ((size_t)ctx->Wd * total_terms + 1) * sizeof(uint2)));
+  HIP_TRY(hipMalloc(&ctx->pairs, plan::cap_entries(ctx->Wd, total_terms) * sizeof(uint2)));
   HIP_TRY(hipMalloc(&ctx->counts, nb * 4));
   HIP_TRY(hipMalloc(&ctx->offsets, nb * 4));
   HIP_TRY(hipMalloc(&ctx->goff, (nb + 1) * 4));
   if ((size_t)ctx->Wd * total_terms * ZK_W_NEXT >= ((size_t)1 << 32)) return ZKHIP_ERR_ARG;      // slice weights are 32-bit
-  // (block totals of the scans; afterwards [0], [1] = the lengths of the two stitching lists, [2] = lock_ok)
-  const size_t ord_m = (size_t)ZK_LOCK_KEYS * nblk(nb, 1024);
-  {
-    size_t scan_m = nb > ctx->hist_len ? nb : ctx->hist_len;
-    if (ord_m > scan_m) scan_m = ord_m;
-    HIP_TRY(hipMalloc(&ctx->block_tot, (scan_m / 1024 + 4) * 4));
-  }
+  HIP_TRY(hipMalloc(&ctx->block_tot, plan::cap_block_tot(nb, ctx->hist_len, ZK_LOCK_KEYS) * 4));      // (see enqueue_scan)
   if (merged == 1 && K == 1) {      // a plan that may serve Edwards launches: the lockstep route's bucket order
     HIP_TRY(hipMalloc(&ctx->order, nb * 4));
-    HIP_TRY(hipMalloc(&ctx->ord_hist, ord_m * 4));
+    HIP_TRY(hipMalloc(&ctx->ord_hist, (size_t)ZK_LOCK_KEYS * nblk(nb, 1024) * 4));
     int dev = 0, cus = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ctx->lock_min_live = 64u * 2u * 4u * (uint32_t)(cus > 0 ? cus : 256);     // two waves for each of a CU's four SIMDs
+    ctx->lock_min_live = plan::lock_min_live(cus);
   }
-  HIP_TRY(hipMalloc(&ctx->entries, ((size_t)ctx->Wd * total_terms + 1) * 4));
-  // batched-affine levels: bounds on the level sizes, the buffers of their outputs
-  {
-    size_t m = (size_t)ctx->Wd * total_terms;
-    ctx->aff_levels = choose_aff_levels(m, nb);
-    ctx->aff_forced = msm_forced_aff_levels();
-    ctx->aff_m = (uint32_t)env_int("ZKHIP_AFF_M", 64, 4, 512);
-    ctx->aff_lanes = 1u << 18;                                           // lanes per launch: 2^18 * aff_m * 108 B of scratch
-    const size_t m_cap = (size_t)ctx->aff_m * 3 / 2;                      // a launch may use up to 1.5 aff_m outputs per lane (whole fills)
-    while ((size_t)ctx->aff_lanes * m_cap * 108 >= ((size_t)1 << 32)) ctx->aff_lanes >>= 1;         // one buffer descriptor
-    size_t bound[MSM_MAX_AFF_LEVELS + 1];
-    bound[0] = m;
-    for (int l = 0; l < ctx->aff_levels; l++) {
-      bound[l + 1] = level_bound(bound[l], nb);
-      HIP_TRY(hipMalloc(&ctx->lcnt[l], nb * 4));
-      HIP_TRY(hipMalloc(&ctx->loff[l], nb * 4));
-    }
-    if (ctx->aff_levels > 0) {
-      HIP_TRY(hipMalloc(&ctx->pbuf[0], (bound[1] + 1) * sizeof(AffPacked)));
-      if (ctx->aff_levels > 1) HIP_TRY(hipMalloc(&ctx->pbuf[1], (bound[2] + 1) * sizeof(AffPacked)));
-      size_t lanes = (bound[1] + ctx->aff_m - 1) / ctx->aff_m;
-      if (lanes < ctx->aff_lanes) ctx->aff_lanes = (uint32_t)((lanes + 255) & ~(size_t)255);
-      HIP_TRY(hipMalloc(&ctx->aff_scratch, (size_t)ctx->aff_lanes * m_cap * 108));
-    }
-    ctx->m_acc_max = bound[ctx->aff_levels];
+  HIP_TRY(hipMalloc(&ctx->entries, plan::cap_entries(ctx->Wd, total_terms) * 4));
+  // Batched-affine levels before the XYZZ accumulation: NONE unless forced (zkhip_set_affine_levels, ZKHIP_AFF_LEVELS; tested: the same
+  // group element; slower than the XYZZ kernel: DESIGN.md section 5).  Bounds on the level sizes, the buffers of their outputs:
+  ctx->aff_forced = msm_forced_aff_levels();
+  ctx->aff_levels = ctx->aff_forced >= 0 ? ctx->aff_forced : 0;
+  ctx->aff_m = (uint32_t)env_int("ZKHIP_AFF_M", 64, 4, 512);
+  size_t bound[MSM_MAX_AFF_LEVELS + 1];
+  bound[0] = (size_t)ctx->Wd * total_terms;
+  for (int l = 0; l < ctx->aff_levels; l++) {
+    bound[l + 1] = plan::level_bound(bound[l], nb);
+    HIP_TRY(hipMalloc(&ctx->lcnt[l], nb * 4));
+    HIP_TRY(hipMalloc(&ctx->loff[l], nb * 4));
   }
-  // slice length: every lane gets the same number of point operations; aim at a whole number of
-  // machine fills (256 CUs x 8 waves x 64 lanes at two waves per SIMD)
-  {
-    const size_t lanes = 131072, m_max = ctx->m_acc_max;
-    size_t fills = (m_max + lanes * slice_target() - 1) / (lanes * slice_target());     // ~80 entries per lane and fill
-    if (fills < 1) fills = 1;
-    size_t S = (m_max + lanes * fills - 1) / (lanes * fills);
-    if (S < 16) S = 16;
-    // the slot array (nb buckets + two boundary slots per slice) is addressed through ONE buffer descriptor: 448 bytes (four
-    // coordinates of 28 words; ec_mem.cuh) x slots < 4 GiB.  Large inputs (the five MSMs of a 2^22 key in one launch: 377 M entries) get longer slices instead of
-    // more of them.
-    const size_t max_slots = (((size_t)1 << 32) - 1) / (ZK_SLOT_WORDS * 4);
-    if (nb + 64 >= max_slots) return ZKHIP_ERR_ARG;
-    while (nb + 2 * ((m_max + S - 1) / S) >= max_slots) S += (S + 7) / 8;
-    ctx->S = (uint32_t)S;
-    ctx->T = (uint32_t)((m_max + S - 1) / S);
-    ctx->slot_stride = (uint32_t)(nb + 2 * (size_t)ctx->T);
-    if ((size_t)ctx->slot_stride * ZK_SLOT_WORDS * 4 >= ((size_t)1 << 32)) return ZKHIP_ERR_ARG;
+  ctx->aff_lanes = plan::aff_lanes(ctx->aff_m, ctx->aff_levels, plan::level_bound(bound[0], nb));
+  if (ctx->aff_levels > 0) {
+    HIP_TRY(hipMalloc(&ctx->pbuf[0], (bound[1] + 1) * sizeof(AffPacked)));
+    if (ctx->aff_levels > 1) HIP_TRY(hipMalloc(&ctx->pbuf[1], (bound[2] + 1) * sizeof(AffPacked)));
+    HIP_TRY(hipMalloc(&ctx->aff_scratch, (size_t)ctx->aff_lanes * plan::aff_m_cap(ctx->aff_m) * plan::AFF_SCRATCH_BYTES));
   }
+  ctx->m_acc_max = bound[ctx->aff_levels];
+  if (!plan::slice_plan(ctx->m_acc_max, nb, slice_target(), ZK_SLOT_WORDS, ctx->S, ctx->T, ctx->slot_stride)) return ZKHIP_ERR_ARG;
   HIP_TRY(hipMalloc(&ctx->buckets, (size_t)ctx->slot_stride * ZK_SLOT_WORDS * 4));
   if (getenv("ZKHIP_DEBUG_DUMP")) HIP_TRY(hipMalloc(&ctx->dbg_times, ((size_t)ctx->T / 64 + 8) * 32));
   HIP_TRY(hipMalloc(&ctx->prio_board, (size_t)ZK_PRIO_BOARD_WORDS * 4));          // 8 XCC x 8 SE x 2 SH x 16 CU x 4 SIMD x 16 wave slots
   HIP_TRY(hipMemset(ctx->prio_board, 0, (size_t)ZK_PRIO_BOARD_WORDS * 4));
-  ctx->prio_seq = 0;
-  HIP_TRY(hipMalloc(&ctx->fix_list, ((size_t)ctx->T / 5 + 2) * sizeof(uint2)));     // buckets of more than four F pieces: at most T / 5
-  HIP_TRY(hipMalloc(&ctx->fix_short, ((size_t)ctx->T / 2 + 2) * sizeof(uint2)));    // buckets of two to four F pieces: at most T / 2
-  // reduction scratch: S ping-pong (<= nb/L each) and R arrays (sum over levels <= nb/L * L/(L-1)), R sums
-  HIP_TRY(hipMalloc(&ctx->segS[0], (nb / 2 + 1) * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->segS[1], (nb / 2 + 1) * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->segR, (nb / 2 + 64 * (size_t)ctx->W) * 108 * 4));   // one R array per level, back to back (sum < nb/3 at L = 4)
-  HIP_TRY(hipMalloc(&ctx->sumR[0], (nb / ctx->L / ctx->L + 4 * ctx->W + 1) * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->sumR[1], (nb / ctx->L / ctx->L + 4 * ctx->W + 1) * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->Rlevels, (size_t)32 * 2 * ctx->W * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->colS[0], (nb / 2 + 1) * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->colS[1], (nb / 2 + 1) * 108 * 4));
-  HIP_TRY(hipMalloc(&ctx->hilo, ((size_t)2 * ctx->W * ((size_t)1 << ((c - 1 + 1) / 2)) + 8) * 108 * 4));
+  const size_t pt = plan::POINT_WORDS * 4;      // bytes of a point of the reduction scratch
+  HIP_TRY(hipMalloc(&ctx->fix_list, plan::cap_fix_list(ctx->T) * sizeof(uint2)));
+  HIP_TRY(hipMalloc(&ctx->fix_short, plan::cap_fix_short(ctx->T) * sizeof(uint2)));
+  HIP_TRY(hipMalloc(&ctx->segS[0], plan::cap_segS(nb) * pt));
+  HIP_TRY(hipMalloc(&ctx->segS[1], plan::cap_segS(nb) * pt));
+  HIP_TRY(hipMalloc(&ctx->segR, plan::cap_segR(nb, ctx->W) * pt));
+  HIP_TRY(hipMalloc(&ctx->sumR[0], plan::cap_sumR(nb, ctx->W, ctx->L) * pt));
+  HIP_TRY(hipMalloc(&ctx->sumR[1], plan::cap_sumR(nb, ctx->W, ctx->L) * pt));
+  HIP_TRY(hipMalloc(&ctx->Rlevels, plan::cap_Rlevels(ctx->W) * pt));
+  HIP_TRY(hipMalloc(&ctx->colS[0], plan::cap_segS(nb) * pt));
+  HIP_TRY(hipMalloc(&ctx->colS[1], plan::cap_segS(nb) * pt));
+  HIP_TRY(hipMalloc(&ctx->hilo, plan::cap_hilo(ctx->W, c) * pt));
   HIP_TRY(hipMalloc(&ctx->win_abi, (size_t)ctx->W * 48 * 8 * 2));       // (the second half: the plain totals of a NAF plan)
   HIP_TRY(hipHostMalloc(&ctx->win_host, (size_t)ctx->W * 48 * 8 * 2));
   ctx->planned = true;
@@ -1845,13 +1762,8 @@ void msm_plan_free(MsmCtx* ctx) {
                   ctx->fix_list, ctx->fix_short, ctx->dbg_times, ctx->goff, ctx->prio_board, ctx->order, ctx->ord_hist};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (ctx->win_host) (void)hipHostFree(ctx->win_host);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-  if (ctx->ev) (void)hipEventDestroy(ctx->ev);
-  if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
-  if (ctx->ev_acc0) (void)hipEventDestroy(ctx->ev_acc0);
-  if (ctx->ev_acc1) (void)hipEventDestroy(ctx->ev_acc1);
-  if (ctx->ev_done) (void)hipEventDestroy(ctx->ev_done);
+  for (hipStream_t st : {ctx->stream, ctx->stream2}) if (st) (void)hipStreamDestroy(st);
+  for (hipEvent_t ev : {ctx->ev, ctx->ev2, ctx->ev_acc0, ctx->ev_acc1, ctx->ev_done}) if (ev) (void)hipEventDestroy(ev);
   memset(ctx, 0, sizeof *ctx);
 }
 
@@ -1874,10 +1786,263 @@ int msm_launch(MsmCtx* ctx, const AffPacked* d_bases, const uint8_t* d_inf_flags
   return msm_launch_multi(ctx, 1, &job);
 }
 
+// Exclusive prefix sum of m words, in -> out (may be the same array).  block_tot holds a scan's block totals while it runs; AFTER the
+// launch's last scan its words [0], [1] are the lengths of the two stitching lists (zeroed by stage_accumulate, counted by
+// k_accumulate) and [2] is lock_ok (written by k_bucket_order<1> behind its own scan): no scan may follow that memset.
+static void enqueue_scan(hipStream_t st, const uint32_t* in, uint32_t* out, uint32_t* block_tot, size_t m) {
+  const unsigned sb = nblk(m, 1024);
+  hipLaunchKernelGGL(k_scan_local, dim3(sb), dim3(256), 0, st, in, out, block_tot, m);
+  hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, block_tot, (size_t)sb);
+  hipLaunchKernelGGL(k_scan_add, dim3(sb), dim3(256), 0, st, out, block_tot, m);
+}
+struct RedKernels {      // the stitching and reduction kernels that exist for XYZZ and for Edwards points (red_kernels)
+  void (*fold_quad)(ZK_FOLD_PARAMS), (*fold)(ZK_FOLD_PARAMS);
+  void (*sum_lds)(ZK_SUM_PARAMS), (*sum_quad)(ZK_SUM_PARAMS);
+  void (*seg)(ZK_SEG_PARAMS), (*seg_quad)(ZK_SEG_PARAMS);
+  void (*window_combine)(ZK_WCOMB_PARAMS), (*hilo_combine)(ZK_HCOMB_PARAMS);
+};
+struct Launch {      // what the stages of one msm_launch_multi share
+  int K;                                  // jobs of this launch (<= ctx->K)
+  const MsmJob* jobs;
+  size_t nb;                              // buckets of all windows
+  bool edw;                               // the Edwards accumulation and reduction (see msm_launch_multi)
+  uint32_t wf;                            // slice weight of a bucket's first entry
+  int bshift;                             // bucket -> job
+  BasePtrs bp;                            // the points the entries index: every job's bases, then the last affine level's sums
+  const uint32_t *cur_off, *cur_cnt;      // the list k_accumulate sums: the sort's, then every affine level's
+  size_t m_cur;                           // bound on its entries
+  uint32_t S_run, T_run;                  // slice length and slices for THIS launch (the plan's slot array is sized for max_n)
+  int tight;                              // slices cut by weight, not by entry count (slice_len); 0 for provers that share the chip
+  RedKernels red;                         // the XYZZ or the Edwards kernels of the stitching and the reduction
+};
+
+// (1) bucket sort: count per (part, block) in LDS, scan, place by part, then order every part by its low bucket bits.  The bucket
+// windows of the jobs this call does not use (K < ctx->K) stay empty: their rows of hist are written as zeros by grid row k.
+static int stage_sort(MsmCtx* ctx, const Launch& lp) {
+  const int KK = ctx->merged ? ctx->K : 1;                       // every bucket window's rows of hist are (re)written
+  hipStream_t st = ctx->stream;
+  WindowPlan wp = {};
+  for (int w = 0; w < ctx->Wd; w++) { wp.off[w] = ctx->win_off[w]; wp.bits[w] = ctx->win_bits[w]; }
+  DigitJobs dj = {};
+  size_t n_max = 0;      // terms of the longest job
+  for (int k = 0; k < lp.K; k++) {
+    const MsmJob& j = lp.jobs[k];
+    dj.scalars[k] = j.scalars; dj.inf_flags[k] = j.inf_flags; dj.n[k] = j.n; dj.tab_stride[k] = j.table_stride; dj.mode[k] = j.scalars_mode;
+    if (j.n > n_max) n_max = j.n;
+  }
+  SortGeom ge;
+  ge.LB = ctx->sort_LB; ge.NP = ctx->sort_NP; ge.bins = ctx->sort_bins; ge.tile = ctx->sort_tile;
+  ge.nbx = nblk(n_max, ge.tile);
+  ge.nparts = (uint32_t)(lp.nb >> ge.LB);
+  const size_t hist_m = plan::hist_m(lp.nb, ge.LB, ge.nbx);
+  if (hist_m > ctx->hist_len) return ZKHIP_ERR_ARG;
+  ctx->last_hist_m = hist_m;
+  for (int pass = 0; pass < 2; pass++) {      // (NAF digits or plain ones; LDS: the counters, in pass 1 the bases too)
+    const bool naf = ctx->merged == 2;
+    const auto digit_pass = !pass ? (naf ? k_digit_pass<0, true> : k_digit_pass<0, false>) : (naf ? k_digit_pass<1, true> : k_digit_pass<1, false>);
+    hipLaunchKernelGGL(digit_pass, dim3(ge.nbx, KK), dim3(256), (size_t)ge.bins * 4 * (pass + 1), st, dj, ctx->c, ctx->Wd, wp, ctx->merged, ge, ctx->hist, ctx->pairs);
+    if (pass == 0) enqueue_scan(st, ctx->hist, ctx->hist, ctx->block_tot, hist_m);
+  }
+  hipLaunchKernelGGL(k_bucket_sort, dim3(ge.nparts), dim3(512), 0, st, ctx->hist, ge, ctx->pairs, ctx->entries, ctx->offsets, ctx->counts);
+  HIP_TRY(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+// (2) batched-affine levels: the sorted list is summed pairwise inside every bucket, ctx->aff_levels times
+static int stage_affine_levels(MsmCtx* ctx, Launch& lp) {
+  hipStream_t st = ctx->stream;
+  ctx->acc_gen = time_base_gen();
+  if (ctx->aff_levels > 0) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));     // the timed accumulation includes the affine levels
+  for (int l = 0; l < ctx->aff_levels; l++) {
+    const size_t m_out = plan::level_bound(lp.m_cur, lp.nb);
+    hipLaunchKernelGGL(k_half_counts, dim3(nblk(lp.nb, 256)), dim3(256), 0, st, lp.cur_cnt, ctx->lcnt[l], lp.nb);
+    enqueue_scan(st, ctx->lcnt[l], ctx->loff[l], ctx->block_tot, lp.nb);
+    LevelArgs la;
+    la.bp = lp.bp; la.bshift = lp.bshift; la.entries = ctx->entries; la.src = l ? ctx->pbuf[(l - 1) & 1] : nullptr;
+    la.in_off = lp.cur_off; la.in_cnt = lp.cur_cnt; la.out_off = ctx->loff[l];
+    la.nb = (uint32_t)lp.nb; la.m = plan::aff_outputs_per_lane(m_out, ctx->aff_m); la.dst = ctx->pbuf[l & 1]; la.scratch = ctx->aff_scratch;
+    const size_t lanes_tot = (m_out + la.m - 1) / la.m;
+    for (size_t lane0 = 0; lane0 < lanes_tot; lane0 += ctx->aff_lanes) {
+      const size_t ln = lanes_tot - lane0 < ctx->aff_lanes ? lanes_tot - lane0 : ctx->aff_lanes;
+      la.lane0 = (uint32_t)lane0; la.lanes = ctx->aff_lanes;       // row length of the scratch: fixed; lanes beyond ln do not exist
+      const auto level = l == 0 ? (ctx->K == 1 ? k_affine_level<1, true> : k_affine_level<MSM_MAX_JOBS, true>) : k_affine_level<1, false>;
+      hipLaunchKernelGGL(level, dim3(nblk(ln, 256)), dim3(256), 0, st, la);
+    }
+    lp.cur_off = ctx->loff[l]; lp.cur_cnt = ctx->lcnt[l]; lp.m_cur = m_out;
+  }
+  if (ctx->aff_levels > 0) lp.bp.p[0] = ctx->pbuf[(ctx->aff_levels - 1) & 1];
+  HIP_TRY(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+// (3) slice weights, the lockstep route's bucket order, the slot array's zero fill, the accumulation between ev_acc0 and ev_acc1
+static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
+  hipStream_t st = ctx->stream;
+  const size_t nb = lp.nb;
+  const bool dense = ctx->aff_levels > 0;
+  // slice weights: goff = exclusive scan of (8 count - 7) over the non-empty buckets of the list k_accumulate sums (nb + 1 values)
+  hipLaunchKernelGGL(k_slice_weights, dim3(nblk(nb + 1, 256)), dim3(256), 0, st, lp.cur_cnt, ctx->goff, nb, lp.wf);
+  enqueue_scan(st, ctx->goff, ctx->goff, ctx->block_tot, nb + 1);
+  if (lp.edw) {      // the lockstep route's bucket order and its go / no-go word, block_tot[2]
+    const unsigned ob = nblk(nb, 1024);
+    const int lock_on = lockstep_mode();
+    const uint32_t min_live = g_lock_min_live >= 0 ? (uint32_t)g_lock_min_live : ctx->lock_min_live;
+    hipLaunchKernelGGL(k_bucket_order<0>, dim3(ob), dim3(256), 0, st, lp.cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
+    enqueue_scan(st, ctx->ord_hist, ctx->ord_hist, ctx->block_tot, (size_t)ZK_LOCK_KEYS * ob);
+    hipLaunchKernelGGL(k_bucket_order<1>, dim3(ob), dim3(256), 0, st, lp.cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
+  }
+  HIP_TRY(hipMemsetAsync(ctx->block_tot, 0, 8, st));   // the lengths of the two stitching lists: the launch's scans are done (enqueue_scan)
+  size_t n_jobs = 0;
+  for (int k = 0; k < lp.K; k++) n_jobs += lp.jobs[k].n ? 1 : 0;
+  lp.S_run = (uint32_t)plan::slice_run(lp.m_cur, slice_target(), ctx->one_stream ? (size_t)env_int("ZKHIP_STREAM_SLICE_MULT", 2, 1, 16) : 1, ctx->merged ? ctx->B * (n_jobs ? n_jobs : 1) : nb, ctx->T);
+  lp.T_run = nblk(lp.m_cur, lp.S_run);
+  lp.tight = (ctx->one_stream || dense) ? 0 : env_int("ZKHIP_TIGHT_SLICES", 1, 0, 1);      // (a streaming prover shares the chip: see slice_len)
+  // all-zero ZZ = infinity is what every reader of a slot tests first (mem_is_inf; X, Y, ZZZ of an infinite slot are copied along at
+  // most, never used): only the 27 ZZ rows of the limb-major array need the zero fill - a quarter of the bytes
+#if ZK_SLOTS_AOS
+  static const int clear_mode = env_int("ZKHIP_SLOTS_CLEAR", 0, 0, 1);      // 0: the ZZ words only (a kernel); 1: the whole array (one memset, four times the bytes, whole lines)
+  if (clear_mode == 1) HIP_TRY(hipMemsetAsync(ctx->buckets, 0, (size_t)ctx->slot_stride * ZK_SLOT_WORDS * 4, st));
+  else hipLaunchKernelGGL(k_slots_clear_zz, dim3(nblk((size_t)ctx->slot_stride * 27, 256)), dim3(256), 0, st, ctx->buckets, ctx->slot_stride);
+#else
+  HIP_TRY(hipMemsetAsync(ctx->buckets + (size_t)CZZ * 27 * ctx->slot_stride, 0, (size_t)ctx->slot_stride * 27 * 4, st));
+#endif
+  if (ctx->dbg_times) HIP_TRY(hipMemsetAsync(ctx->dbg_times, 0, ((size_t)ctx->T / 64 + 8) * 32, st));
+  if (ctx->acc_gate) HIP_TRY(hipStreamWaitEvent(st, ctx->acc_gate, 0));
+  if (!dense) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));
+  static const int acc_prio = env_int("ZKHIP_ACC_PRIO", 1, 0, 2);      // 2: by quarters of the slice only (no board)
+  const uint32_t prio_tag = (++ctx->prio_seq & 0x7fffu) + 1u;     // (see k_accumulate: the wave that is behind asks for priority; 0 = the arbiter's own order)
+  if (lp.edw)
+    hipLaunchKernelGGL(k_accumulate_edw_lock, dim3(nblk(nb, 256)), dim3(256), 0, st, lp.jobs[0].edw, ctx->entries, lp.cur_off, lp.cur_cnt, ctx->order, (uint32_t)nb, ctx->buckets, ctx->slot_stride, ctx->block_tot + 2);
+  const auto accumulate = lp.edw ? k_accumulate_edw : (ctx->K == 1 || dense) ? k_accumulate<1> : k_accumulate<MSM_MAX_JOBS>;
+  hipLaunchKernelGGL(accumulate, dim3(nblk(lp.T_run, 256)), dim3(256), 0, st, lp.bp, lp.bshift, dense ? (const uint32_t*)nullptr : ctx->entries, lp.cur_off, lp.cur_cnt, ctx->goff, (uint32_t)nb,
+                     lp.S_run, lp.tight, lp.T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
+  HIP_TRY(hipEventRecord(ctx->ev_acc1, st));
+  ctx->last_S = lp.S_run; ctx->last_T = lp.T_run; ctx->last_tight = lp.tight;
+  HIP_TRY(hipGetLastError());
+  return ZKHIP_OK;
+}
+// (stands HERE, its candidates in THIS order: the device code keeps its template kernels in the order of their first use on the host,
+// see profiles/msm_driver_refactor_codeobj.txt.  k_fixup / k_fixup_edw differ in their arguments and stay a branch.)
+static RedKernels red_kernels(bool edw) {
+  return {edw ? k_fixup_fold_edw<true> : k_fixup_fold<true>, edw ? k_fixup_fold_edw<false> : k_fixup_fold<false>,
+          edw ? k_sum_lds_edw : k_sum_lds,                   edw ? k_sum_edw<true> : k_sum<true>,
+          edw ? k_seg_edw<false> : k_seg<false>,             edw ? k_seg_edw<true> : k_seg<true>,
+          edw ? k_window_combine_edw : k_window_combine,     edw ? k_hilo_combine_edw : k_hilo_combine};
+}
+
+// (4) stitching: fold the F pieces of the buckets that have several (lists made by k_accumulate), then L + F for every cut bucket
+static int stage_stitch(MsmCtx* ctx, const Launch& lp) {
+  hipStream_t st = ctx->stream;
+  const uint32_t nb = (uint32_t)lp.nb, T_run = lp.T_run;
+  if (T_run > 2) {
+    const bool fold_quads = T_run < (1u << 18) && ctx->quad_below > 1024;     // a small launch that has the chip to itself is latency-bound
+    const uint32_t sblocks = std::min(1024u, nblk((size_t)T_run / 2 + 1, fold_quads ? 64u : 256u));      // (the list is walked with a grid stride)
+    // + 512 workgroups for the long list (a wrapping proof has ~290 buckets of 7-8 pieces; 128 workgroups took three sweeps of three rounds)
+    hipLaunchKernelGGL(fold_quads ? lp.red.fold_quad : lp.red.fold, dim3(sblocks + 512), dim3(256), 0, st, ctx->block_tot, ctx->fix_short, ctx->fix_list, sblocks, nb, ctx->buckets, ctx->slot_stride);
+  }
+  if (lp.edw)
+    hipLaunchKernelGGL(k_fixup_edw, dim3(nblk(T_run, 256)), dim3(256), 0, st, lp.cur_off, lp.cur_cnt, ctx->goff, nb, lp.S_run, lp.tight, T_run, ctx->buckets, ctx->slot_stride, lp.wf, ctx->block_tot + 2);
+  else
+    hipLaunchKernelGGL(k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, lp.cur_off, lp.cur_cnt, ctx->goff, nb, lp.S_run, lp.tight, T_run, ctx->buckets, ctx->slot_stride, lp.wf);
+  HIP_TRY(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+// out[t] = the sum of L items of `in`, row_len apart (k_sum).  Fewer outputs than quad_below: the launch is latency-bound, a quad of
+// lanes per addition finishes it sooner (at ~twice the lane-cycles: a prover that shares the chip with others lowers the threshold)
+static void enqueue_sum(MsmCtx* ctx, const Launch& lp, hipStream_t s, uint32_t* in, size_t n_in, uint32_t in_stride, int L, uint32_t row_len, uint32_t* out) {
+  const size_t n_out = n_in / L;
+  const int in_slots = (in == ctx->buckets) ? 1 : 0;          // the first level reads the slot array (an array of structures: ec_mem.cuh)
+  if (n_out >= ctx->quad_below) hipLaunchKernelGGL(lp.red.sum_lds, dim3(nblk(n_out, 256)), dim3(256), 0, s, in, n_in, in_stride, L, row_len, out, in_slots);
+  else hipLaunchKernelGGL(lp.red.sum_quad, dim3(nblk(n_out * 4, 256)), dim3(256), 0, s, in, n_in, in_stride, L, row_len, out, in_slots);
+}
+// A tree over the slot array [W][H][R]: the `left` items of every row (contiguous: col_stride 0) or column (col_stride R apart) are
+// summed to one; returns the result.  Halving-style grouping inside each row (item lo' + u * left/L): lanes of a wave read adjacent
+// slots (L CONSECUTIVE items make every lane stride L slots).  left > 1: msm_plan_init refuses c < 4, so lo_bits >= 2, hi_bits >= 1.
+static uint32_t* enqueue_tree(MsmCtx* ctx, const Launch& lp, hipStream_t s, uint32_t left, uint32_t col_stride, uint32_t* const buf[2]) {
+  uint32_t* in = ctx->buckets; uint32_t in_stride = ctx->slot_stride; size_t n_in = lp.nb; int pp = 0;
+  while (left > 1) {
+    const int L = plan::tree_fan_in(ctx->L, n_in, left, ctx->quad_below);
+    enqueue_sum(ctx, lp, s, in, n_in, in_stride, L, col_stride ? col_stride : left / L, buf[pp]);
+    n_in /= L; left /= L; in = buf[pp]; in_stride = (uint32_t)n_in; pp ^= 1;
+  }
+  return in;
+}
+
+// (5) bucket reduction: (a) two-level split of the bucket index (row sums on stream 1, column sums on stream 2: plain trees), (b) the two
+// small weighted sums per window by recursive 4-ary running sums, F(items) = sum_t R_t + L * F0(S): the k_seg chain (stream 1) produces
+// one R array per level, reducing each R array to one point per group (k_sum chain) is independent of the later levels: stream 2,
+// (c) per group Horner over the levels, then per window R * hi + lo.
+static int stage_reduce(MsmCtx* ctx, const Launch& lp) {
+  hipStream_t st = ctx->stream;
+  // the row and the column tree run side by side on two streams - unless this context shares the chip with others anyway (one_stream)
+  hipStream_t st2 = ctx->one_stream ? ctx->stream : ctx->stream2;
+  const int c = ctx->c, W = ctx->W, G = 2 * W;
+  const uint32_t Rr = 1u << plan::lo_bits(c), Hh = 1u << plan::hi_bits(c), Nn = Rr > Hh ? Rr : Hh;
+  HIP_TRY(hipEventRecord(ctx->ev, st));
+  HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
+  uint32_t* rows = enqueue_tree(ctx, lp, st, Rr, 0, ctx->segS);       // [W][H][R] -> [W][H]  (sum over lo, contiguous)
+  uint32_t* cols = enqueue_tree(ctx, lp, st2, Hh, Rr, ctx->colS);     // [W][H][R] -> [W][R]  (sum over hi, stride R)
+  HIP_TRY(hipEventRecord(ctx->ev2, st2));
+  HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
+  hipLaunchKernelGGL(k_place_hilo, dim3(nblk((size_t)G * Nn * 4, 256)), dim3(256), 0, st, rows, cols, (uint32_t)W, Hh, Rr, Nn, ctx->hilo);
+  uint32_t* cur = ctx->hilo;
+  size_t n_cur = (size_t)G * Nn, r_off = 0;   // G groups of Nn items, weights index + 1; this level's R array starts at r_off inside segR (in points)
+  int level = 0;
+  LevelShifts ls = {};
+  // (fan-in 2 here was measured and lost: every level brings its own k_seg launch, R-sum tree and hand-over: MSM phase 5.7 -> 6.6 ms)
+  while (n_cur > (size_t)G) {
+    const int L = plan::tree_fan_in(ctx->L, n_cur, (uint32_t)(n_cur / G), 0);      // (less than ctx->L on the last level only)
+    int lg = 0; while ((1 << lg) < L) lg++;
+    ls.log_l[level] = (uint8_t)lg;
+    const size_t n_out = n_cur / L;
+    uint32_t* S = ctx->segS[level & 1];
+    uint32_t* Rk = ctx->segR + r_off * plan::POINT_WORDS;
+    const bool quad = n_out < ctx->quad_below;
+    hipLaunchKernelGGL(quad ? lp.red.seg_quad : lp.red.seg, dim3(nblk(quad ? n_out * 4 : n_out, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
+    HIP_TRY(hipEventRecord(ctx->ev, st));
+    HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
+    // reduce R (n_out items, G groups) to G items: Rlevels[level]
+    uint32_t* const Rl = ctx->Rlevels + (size_t)level * plan::POINT_WORDS * G;
+    uint32_t* rc = Rk;
+    int pp = 0;
+    for (size_t rn = n_out; rn > (size_t)G; pp ^= 1) {
+      const int Ls = plan::tree_fan_in(ctx->L, rn, (uint32_t)(rn / G), 0);
+      const size_t ro = rn / Ls;
+      uint32_t* dst = (ro == (size_t)G) ? Rl : ctx->sumR[pp];
+      enqueue_sum(ctx, lp, st2, rc, rn, (uint32_t)rn, Ls, (uint32_t)(rn / G / Ls), dst);      // same coalesced grouping inside each group
+      rc = dst; rn = ro;
+    }
+    if (n_out == (size_t)G)    // R already one per group
+      HIP_TRY(hipMemcpyAsync(Rl, Rk, plan::POINT_WORDS * G * 4, hipMemcpyDeviceToDevice, st2));
+    r_off += n_out;
+    cur = S; n_cur = n_out; level++;
+  }
+  HIP_TRY(hipEventRecord(ctx->ev2, st2));
+  HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
+  // the last S (one item per group) has weight 0 at its level (o = 0 for level >= 1) and is dropped.
+  hipLaunchKernelGGL(lp.red.window_combine, dim3(nblk((size_t)G * 4, 64)), dim3(64), 0, st, ctx->Rlevels, level, G, ls, ctx->sumR[0]);
+  hipLaunchKernelGGL(lp.red.hilo_combine, dim3(nblk((size_t)W * 4, 64)), dim3(64), 0, st, ctx->sumR[0], W, plan::lo_bits(c), ctx->win_abi, ctx->merged == 2 ? cur : (uint32_t*)nullptr);
+  HIP_TRY(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+// (6) the window results to the host; ev_done ends the launch sequence
+static int stage_copy_out(MsmCtx* ctx, const Launch& lp) {
+  HIP_TRY(hipMemcpyAsync(ctx->win_host, ctx->win_abi, (size_t)ctx->W * 48 * 8 * (ctx->merged == 2 ? 2 : 1), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
+  ctx->win_edw = lp.edw;      // what win_host will hold for THIS launch (the context may serve an XYZZ set next)
+  ctx->pending = true;        // only a completely enqueued sequence is collectable; a failed launch leaves the context reusable
+  return ZKHIP_OK;
+}
+
 int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
-  const int c = ctx->c, W = ctx->W, Wd = ctx->Wd, merged = ctx->merged;
+  const int c = ctx->c, Wd = ctx->Wd, merged = ctx->merged;
   if (K < 1 || K > ctx->K) return ZKHIP_ERR_ARG;
   size_t n_tot = 0, n_eff = 0;
+  Launch lp;      // the launch sequence: the stage functions above, in stream order
+  lp.K = K;
+  lp.jobs = jobs;
   for (int k = 0; k < K; k++) {
     if (jobs[k].n > ctx->max_n) return ZKHIP_ERR_ARG;
     n_eff += msm_job_terms(jobs[k]);
@@ -1885,300 +2050,28 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
     if (merged && jobs[k].n && (jobs[k].table_stride < jobs[k].n || (size_t)(merged == 2 ? 378 : Wd) * jobs[k].table_stride >= ((size_t)1 << 31))) return ZKHIP_ERR_ARG;
     n_tot += jobs[k].n;
   }
-  const size_t B = ctx->B, nb = B * W;
-  hipStream_t st = ctx->stream;
   ctx->pending_n = n_tot;
   ctx->win_edw = false;
   if (n_tot == 0) { ctx->pending = true; return ZKHIP_OK; }
-  WindowPlan plan;
-  memset(&plan, 0, sizeof plan);
-  for (int w = 0; w < Wd; w++) { plan.off[w] = ctx->win_off[w]; plan.bits[w] = ctx->win_bits[w]; }
   // the Edwards accumulation (ec_edw.cuh): a single MSM over a one-level-per-window table that has its Edwards form, no batched-affine
   // levels in front.  The digits are XYZZ's (the table holds chi of the HALVED points); the slots, the stitching and the bucket
   // reduction hold Edwards points (the k_..._edw kernels), and the host maps the window results back (win_edw: edw_abi_to_jac).
-  const bool edw = merged == 1 && K == 1 && ctx->K == 1 && ctx->aff_levels == 0 && jobs[0].edw != nullptr;
-  const uint32_t wf = edw ? ZK_W_NEXT : ZK_W_FIRST;
-  DigitJobs dj;
-  memset(&dj, 0, sizeof dj);
-  size_t n_max = 0;
-  for (int k = 0; k < K; k++) {
-    dj.scalars[k] = jobs[k].scalars; dj.inf_flags[k] = jobs[k].inf_flags; dj.n[k] = jobs[k].n; dj.tab_stride[k] = jobs[k].table_stride;
-    dj.mode[k] = jobs[k].scalars_mode;
-    if (jobs[k].n > n_max) n_max = jobs[k].n;
-  }
-  // bucket sort: count per (part, block) in LDS, scan, place by part, then order every part by its low bucket bits.  The bucket
-  // windows of the jobs this call does not use (K < ctx->K) stay empty: their rows of hist are written as zeros by grid row k.
-  SortGeom ge;
-  ge.LB = ctx->sort_LB; ge.NP = ctx->sort_NP; ge.bins = ctx->sort_bins; ge.tile = ctx->sort_tile;
-  ge.nbx = (uint32_t)((n_max + ge.tile - 1) / ge.tile);
-  ge.nparts = (uint32_t)(nb >> ge.LB);
-  const size_t hist_m = (size_t)ge.nparts * ge.nbx + 1;
-  if (hist_m > ctx->hist_len) return ZKHIP_ERR_ARG;
-  ctx->last_hist_m = hist_m;
-  const int KK = merged ? ctx->K : 1;                            // every bucket window's rows of hist are (re)written
-  for (int k = K; k < KK; k++) dj.n[k] = 0;
-  const dim3 dgrid(ge.nbx, KK);
-  const size_t lds0 = (size_t)ge.bins * 4, lds1 = (size_t)ge.bins * 8;
-  if (merged == 2) hipLaunchKernelGGL((k_digit_pass<0, true>), dgrid, dim3(256), lds0, st, dj, c, Wd, plan, merged, ge, ctx->hist, ctx->pairs);
-  else hipLaunchKernelGGL((k_digit_pass<0, false>), dgrid, dim3(256), lds0, st, dj, c, Wd, plan, merged, ge, ctx->hist, ctx->pairs);
-  unsigned sb = nblk(hist_m, 1024);
-  hipLaunchKernelGGL(k_scan_local, dim3(sb), dim3(256), 0, st, ctx->hist, ctx->hist, ctx->block_tot, hist_m);
-  hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)sb);
-  hipLaunchKernelGGL(k_scan_add, dim3(sb), dim3(256), 0, st, ctx->hist, ctx->block_tot, hist_m);
-  if (merged == 2) hipLaunchKernelGGL((k_digit_pass<1, true>), dgrid, dim3(256), lds1, st, dj, c, Wd, plan, merged, ge, ctx->hist, ctx->pairs);
-  else hipLaunchKernelGGL((k_digit_pass<1, false>), dgrid, dim3(256), lds1, st, dj, c, Wd, plan, merged, ge, ctx->hist, ctx->pairs);
-  hipLaunchKernelGGL(k_bucket_sort, dim3(ge.nparts), dim3(512), 0, st, ctx->hist, ge, ctx->pairs, ctx->entries, ctx->offsets, ctx->counts);
-  sb = nblk(nb, 1024);                                            // (the batched-affine levels below scan arrays of nb counters)
-  BasePtrs bp;
-  for (int k = 0; k < MSM_MAX_JOBS; k++) bp.p[k] = jobs[k < K ? k : 0].bases;
-  if (edw) bp.p[0] = reinterpret_cast<const AffPacked*>(jobs[0].edw);     // (k_accumulate_edw reads it as EdwPacked)
-  const int bshift = merged ? c - 1 : 31;     // bucket -> job
-  ctx->acc_gen = time_base_gen();
-  if (ctx->aff_levels > 0) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));     // the timed accumulation includes the affine levels
-  // ---- batched-affine levels: the sorted list is summed pairwise inside every bucket, ctx->aff_levels times
-  const uint32_t *cur_off = ctx->offsets, *cur_cnt = ctx->counts;
-  size_t m_cur = (size_t)Wd * (n_eff ? n_eff : 1);       // entries that can occur: a base at infinity never produces one
-  for (int l = 0; l < ctx->aff_levels; l++) {
-    const size_t m_out = level_bound(m_cur, nb);
-    hipLaunchKernelGGL(k_half_counts, dim3(nblk(nb, 256)), dim3(256), 0, st, cur_cnt, ctx->lcnt[l], nb);
-    hipLaunchKernelGGL(k_scan_local, dim3(sb), dim3(256), 0, st, ctx->lcnt[l], ctx->loff[l], ctx->block_tot, nb);
-    hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)sb);
-    hipLaunchKernelGGL(k_scan_add, dim3(sb), dim3(256), 0, st, ctx->loff[l], ctx->block_tot, nb);
-    LevelArgs la;
-    la.bp = bp; la.bshift = bshift; la.entries = ctx->entries; la.src = l ? ctx->pbuf[(l - 1) & 1] : nullptr;
-    la.in_off = cur_off; la.in_cnt = cur_cnt; la.out_off = ctx->loff[l];
-    la.nb = (uint32_t)nb; la.m = ctx->aff_m; la.dst = ctx->pbuf[l & 1]; la.scratch = ctx->aff_scratch;
-    // outputs per lane: as close to aff_m as a whole number of machine fills allows (131072 lanes are resident at two waves per
-    // SIMD; a partial last fill runs at a fraction of the chip)
-    {
-      const size_t fill = 131072;
-      size_t rounds = (m_out + fill * ctx->aff_m / 2) / (fill * ctx->aff_m);
-      if (rounds >= 1) {
-        size_t mm = (m_out + fill * rounds - 1) / (fill * rounds);
-        la.m = (uint32_t)(mm > ctx->aff_m * 3 / 2 ? ctx->aff_m * 3 / 2 : mm);
-      }
-    }
-    const size_t lanes_tot = (m_out + la.m - 1) / la.m;
-    for (size_t lane0 = 0; lane0 < lanes_tot; lane0 += ctx->aff_lanes) {
-      const size_t ln = lanes_tot - lane0 < ctx->aff_lanes ? lanes_tot - lane0 : ctx->aff_lanes;
-      la.lane0 = (uint32_t)lane0; la.lanes = ctx->aff_lanes;       // row length of the scratch: fixed; lanes beyond ln do not exist
-      const dim3 grid(nblk(ln, 256));
-      if (l == 0) {
-        if (ctx->K == 1) hipLaunchKernelGGL((k_affine_level<1, true>), grid, dim3(256), 0, st, la);
-        else hipLaunchKernelGGL((k_affine_level<MSM_MAX_JOBS, true>), grid, dim3(256), 0, st, la);
-      } else {
-        hipLaunchKernelGGL((k_affine_level<1, false>), grid, dim3(256), 0, st, la);
-      }
-    }
-    cur_off = ctx->loff[l]; cur_cnt = ctx->lcnt[l]; m_cur = m_out;
-  }
-  const bool dense = ctx->aff_levels > 0;
-  if (dense) bp.p[0] = ctx->pbuf[(ctx->aff_levels - 1) & 1];
-  // slice weights: goff = exclusive scan of (8 count - 7) over the non-empty buckets of the list k_accumulate sums (nb + 1 values)
-  {
-    const unsigned gb = nblk(nb + 1, 1024);
-    hipLaunchKernelGGL(k_slice_weights, dim3(nblk(nb + 1, 256)), dim3(256), 0, st, cur_cnt, ctx->goff, nb, wf);
-    hipLaunchKernelGGL(k_scan_local, dim3(gb), dim3(256), 0, st, ctx->goff, ctx->goff, ctx->block_tot, nb + 1);
-    hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)gb);
-    hipLaunchKernelGGL(k_scan_add, dim3(gb), dim3(256), 0, st, ctx->goff, ctx->block_tot, nb + 1);
-  }
-  // the lockstep route's bucket order and its go / no-go word (block_tot[2], written last: the scans above and below use block_tot)
-  if (edw) {
-    const unsigned ob = nblk(nb, 1024), os = nblk((size_t)ZK_LOCK_KEYS * ob, 1024);
-    const int lock_on = lockstep_mode();
-    const uint32_t min_live = g_lock_min_live >= 0 ? (uint32_t)g_lock_min_live : ctx->lock_min_live;
-    hipLaunchKernelGGL(k_bucket_order<0>, dim3(ob), dim3(256), 0, st, cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
-    hipLaunchKernelGGL(k_scan_local, dim3(os), dim3(256), 0, st, ctx->ord_hist, ctx->ord_hist, ctx->block_tot, (size_t)ZK_LOCK_KEYS * ob);
-    hipLaunchKernelGGL(k_scan_tot, dim3(1), dim3(1024), 0, st, ctx->block_tot, (size_t)os);
-    hipLaunchKernelGGL(k_scan_add, dim3(os), dim3(256), 0, st, ctx->ord_hist, ctx->block_tot, (size_t)ZK_LOCK_KEYS * ob);
-    hipLaunchKernelGGL(k_bucket_order<1>, dim3(ob), dim3(256), 0, st, cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
-  }
-  HIP_TRY(hipMemsetAsync(ctx->block_tot, 0, 8, st));   // block_tot[0], [1] are reused as the lengths of the two stitching lists (scans are done)
-  // slice length for THIS n (the plan's slot array is sized for max_n)
-  uint32_t S_run, T_run;
-  {
-    const size_t lanes = 131072, m = m_cur;
-    size_t fills = (m + lanes * slice_target() - 1) / (lanes * slice_target());
-    if (fills < 1) fills = 1;
-    size_t S = (m + lanes * fills - 1) / (lanes * fills);
-    if (S < 16) S = 16;
-    // provers that share the chip (the streaming pipeline) take slices twice as long - half as many lanes a launch, half as many
-    // buckets cut by a slice boundary to stitch afterwards; the other proofs in flight fill the chip.  Measured on the wrapping key,
-    // 24 provers in flight, device side only: x1 349 proofs/s, x2 361, x3 358, x4 352 (tools/acc_probe.py --prove-stream).
-    if (ctx->one_stream) S *= (size_t)env_int("ZKHIP_STREAM_SLICE_MULT", 2, 1, 16);
-    // a bucket should not span more than ~3 slices (the stitching folds 2 .. 4 pieces by one lane; longer chains go through a
-    // workgroup each, which is for the few heavy buckets of a witness, not for every bucket of a small MSM with a narrow window)
-    {
-      size_t n_jobs = 0;
-      for (int k = 0; k < K; k++) n_jobs += jobs[k].n ? 1 : 0;
-      const size_t live_buckets = merged ? B * (n_jobs ? n_jobs : 1) : nb, avg = m / (live_buckets ? live_buckets : 1);
-      if (S < (avg + 1) / 2) S = (avg + 1) / 2;
-    }
-    while ((m + S - 1) / S > ctx->T) S++;
-    S_run = (uint32_t)S; T_run = (uint32_t)((m + S - 1) / S);
-  }
-  const int tight = (ctx->one_stream || dense) ? 0 : env_int("ZKHIP_TIGHT_SLICES", 1, 0, 1);      // (a streaming prover shares the chip: see slice_len)
-  // all-zero ZZ = infinity is what every reader of a slot tests first (mem_is_inf; X, Y, ZZZ of an infinite slot are copied along at
-  // most, never used): only the 27 ZZ rows of the limb-major array need the zero fill - a quarter of the bytes
-#if ZK_SLOTS_AOS
-  {
-    static const int clear_mode = env_int("ZKHIP_SLOTS_CLEAR", 0, 0, 1);      // 0: the ZZ words only (a kernel); 1: the whole array (one memset, four times the bytes, whole lines)
-    if (clear_mode == 1) HIP_TRY(hipMemsetAsync(ctx->buckets, 0, (size_t)ctx->slot_stride * ZK_SLOT_WORDS * 4, st));
-    else hipLaunchKernelGGL(k_slots_clear_zz, dim3(nblk((size_t)ctx->slot_stride * 27, 256)), dim3(256), 0, st, ctx->buckets, ctx->slot_stride);
-  }
-#else
-  HIP_TRY(hipMemsetAsync(ctx->buckets + (size_t)CZZ * 27 * ctx->slot_stride, 0, (size_t)ctx->slot_stride * 27 * 4, st));
-#endif
-  if (ctx->dbg_times) HIP_TRY(hipMemsetAsync(ctx->dbg_times, 0, ((size_t)ctx->T / 64 + 8) * 32, st));
-  if (ctx->acc_gate) HIP_TRY(hipStreamWaitEvent(st, ctx->acc_gate, 0));
-  if (ctx->aff_levels == 0) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));
-  const uint32_t* acc_entries = dense ? nullptr : ctx->entries;
-  static const int acc_prio = env_int("ZKHIP_ACC_PRIO", 1, 0, 2);      // 2: by quarters of the slice only (no board)
-  const uint32_t prio_tag = (++ctx->prio_seq & 0x7fffu) + 1u;     // (see k_accumulate: the wave that is behind asks for priority; 0 = the arbiter's own order)
-  if (edw) {
-    hipLaunchKernelGGL(k_accumulate_edw_lock, dim3(nblk(nb, 256)), dim3(256), 0, st, jobs[0].edw, ctx->entries, cur_off, cur_cnt, ctx->order, (uint32_t)nb,
-                       ctx->buckets, ctx->slot_stride, ctx->block_tot + 2);
-    hipLaunchKernelGGL(k_accumulate_edw, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off, cur_cnt, ctx->goff,
-                       (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
-  } else if (ctx->K == 1 || dense)
-    hipLaunchKernelGGL(k_accumulate<1>, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off, cur_cnt, ctx->goff,
-                       (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
-  else
-    hipLaunchKernelGGL(k_accumulate<MSM_MAX_JOBS>, dim3(nblk(T_run, 256)), dim3(256), 0, st, bp, bshift, acc_entries, cur_off,
-                       cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
-  HIP_TRY(hipEventRecord(ctx->ev_acc1, st));
-  ctx->last_S = S_run; ctx->last_T = T_run; ctx->last_tight = tight;
-  // fold the F pieces of the buckets that have several (lists made by k_accumulate), then L + F for every cut bucket
-  if (T_run > 2) {
-    const bool fold_quads = T_run < (1u << 18) && ctx->quad_below > 1024;     // a small launch that has the chip to itself is latency-bound
-    const uint32_t per = fold_quads ? 64u : 256u;
-    uint32_t sblocks = nblk((size_t)T_run / 2 + 1, per);
-    if (sblocks > 1024) sblocks = 1024;                                        // (the list is walked with a grid stride)
-    // + 512 workgroups for the long list: a wrapping proof has ~290 buckets of 7-8 pieces (values that occur a couple of hundred
-    // times in the assignment, in every window): with 128 workgroups they took three sweeps of three rounds each
-    auto fold = fold_quads ? (edw ? k_fixup_fold_edw<true> : k_fixup_fold<true>) : (edw ? k_fixup_fold_edw<false> : k_fixup_fold<false>);
-    hipLaunchKernelGGL(fold, dim3(sblocks + 512), dim3(256), 0, st, ctx->block_tot, ctx->fix_short, ctx->fix_list, sblocks, (uint32_t)nb, ctx->buckets,
-                       ctx->slot_stride);
-  }
-  if (edw)
-    hipLaunchKernelGGL(k_fixup_edw, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets,
-                       ctx->slot_stride, wf, ctx->block_tot + 2);
-  else
-    hipLaunchKernelGGL(k_fixup, dim3(nblk(T_run, 256)), dim3(256), 0, st, cur_off, cur_cnt, ctx->goff, (uint32_t)nb, S_run, tight, T_run, ctx->buckets,
-                       ctx->slot_stride, wf);
-  HIP_TRY(hipGetLastError());
-
-  // ---- bucket reduction -------------------------------------------------------------------------------
-  // (1) two-level split of the bucket index (row sums on stream 1, column sums on stream 2: plain trees),
-  // (2) the two small weighted sums per window by recursive 4-ary running sums:
-  //     F(items) = sum_t R_t + L * F0(S); the k_seg chain (stream 1) produces one R array per level, reducing
-  //     each R array to one point per group (k_sum chain) is independent of the later levels: stream 2,
-  // (3) per group Horner over the levels, then per window R * hi + lo.
-  // fewer additions than this: the launch is latency-bound, a quad of lanes per addition finishes it sooner (at ~twice the lane-cycles:
-  // a prover that shares the chip with others lowers the threshold, msm.h quad_below)
-  const size_t QUAD_BELOW = ctx->quad_below;
-  // the row and the column tree run side by side on two streams - unless this context shares the chip with others anyway (one_stream:
-  // same throughput, no cross-stream events to wait on, ~0.8 host cores less for fourteen provers)
-  hipStream_t st2 = ctx->one_stream ? ctx->stream : ctx->stream2;
-  const int lo_bits = (c - 1 + 1) / 2, hi_bits = (c - 1) - lo_bits;
-  const uint32_t Rr = 1u << lo_bits, Hh = 1u << hi_bits, Nn = Rr > Hh ? Rr : Hh;
-  auto launch_sum = [&](hipStream_t s_, uint32_t* in, size_t n_in, uint32_t in_stride, int L, uint32_t row_len, uint32_t* out) {
-    size_t n_out = n_in / L;
-    const int in_slots = (in == ctx->buckets) ? 1 : 0;          // the first level reads the slot array (an array of structures: ec_mem.cuh)
-    if (n_out >= QUAD_BELOW) hipLaunchKernelGGL(edw ? k_sum_lds_edw : k_sum_lds, dim3(nblk(n_out, 256)), dim3(256), 0, s_, in, n_in, in_stride, L, row_len, out, in_slots);
-    else hipLaunchKernelGGL(edw ? k_sum_edw<true> : k_sum<true>, dim3(nblk(n_out * 4, 256)), dim3(256), 0, s_, in, n_in, in_stride, L, row_len, out, in_slots);
-  };
-  HIP_TRY(hipEventRecord(ctx->ev, st));
-  HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
-  uint32_t *rows = nullptr, *cols = nullptr;
-  {
-    // row tree: [W][H][R] -> [W][H]  (sum over lo, contiguous)
-    uint32_t* in = ctx->buckets; uint32_t in_stride = ctx->slot_stride; size_t n_in = nb; uint32_t left = Rr; int pp = 0;
-    if (left == 1) rows = in;   // (c <= 2 never happens: c >= 4)
-    // fan-in of a tree level: 4 while the level is throughput-bound (one lane per output, three additions each, fewer passes over
-    // the data); 2 once it is latency-bound (a quad per output): ONE addition deep instead of three - the chain of dependent
-    // additions of a row / column tree shrinks from 3 log4 to log2 of its length
-    auto tree_fan_in = [&](size_t n_in_, uint32_t left_) {
-      int L = ctx->L;
-      if (n_in_ / (size_t)L < QUAD_BELOW) L = 2;
-      while ((uint32_t)L > left_) L >>= 1;
-      return L;
-    };
-    while (left > 1) {
-      const int L = tree_fan_in(n_in, left);
-      uint32_t* out = ctx->segS[pp];
-      // halving-style grouping inside each row of `left` items (item lo' + u * left/L): lanes of a wave read adjacent
-      // slots (summing L CONSECUTIVE items instead makes every lane stride L slots: a quarter of each sector used)
-      launch_sum(st, in, n_in, in_stride, L, left / L, out);
-      n_in /= L; left /= L; in = out; in_stride = (uint32_t)n_in; pp ^= 1; rows = out;
-    }
-    // column tree: [W][H][R] -> [W][R]  (sum over hi, stride R)
-    in = ctx->buckets; in_stride = ctx->slot_stride; n_in = nb; left = Hh; pp = 0;
-    if (left == 1) { cols = ctx->colS[0]; launch_sum(st2, in, n_in, in_stride, 1, Rr, cols); }
-    while (left > 1) {
-      const int L = tree_fan_in(n_in, left);
-      uint32_t* out = ctx->colS[pp];
-      launch_sum(st2, in, n_in, in_stride, L, Rr, out);
-      n_in /= L; left /= L; in = out; in_stride = (uint32_t)n_in; pp ^= 1; cols = out;
-    }
-  }
-  HIP_TRY(hipEventRecord(ctx->ev2, st2));
-  HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
-  const int G = 2 * W;
-  hipLaunchKernelGGL(k_place_hilo, dim3(nblk((size_t)G * Nn * 4, 256)), dim3(256), 0, st, rows, cols, (uint32_t)W, Hh, Rr, Nn, ctx->hilo);
-
-  uint32_t* cur = ctx->hilo;
-  size_t n_cur = (size_t)G * Nn;   // G groups of Nn items, weights index + 1
-  int level = 0;
-  LevelShifts ls;
-  memset(&ls, 0, sizeof ls);
-  size_t r_off = 0;                  // this level's R array starts here inside segR (in points)
-  // (fan-in 2 in this recursion was measured and lost: 8 levels instead of 4 halve the chain of dependent point operations on paper,
-  //  but every level brings its own k_seg launch, R-sum tree and cross-stream hand-over: one wrapping proof's MSM phase 5.7 -> 6.6 ms)
-  while (n_cur > (size_t)G) {
-    int L = ctx->L;
-    while ((size_t)L > n_cur / G) L >>= 1;      // last level: fewer items per group than L
-    int lg = 0; while ((1 << lg) < L) lg++;
-    ls.log_l[level] = (uint8_t)lg;
-    size_t n_out = n_cur / L;
-    uint32_t* S = ctx->segS[level & 1];
-    uint32_t* Rk = ctx->segR + r_off * 108;
-    if (n_out >= QUAD_BELOW)
-      hipLaunchKernelGGL(edw ? k_seg_edw<false> : k_seg<false>, dim3(nblk(n_out, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
-    else
-      hipLaunchKernelGGL(edw ? k_seg_edw<true> : k_seg<true>, dim3(nblk(n_out * 4, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
-    HIP_TRY(hipEventRecord(ctx->ev, st));
-    HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
-    // reduce R (n_out items, G groups) to G items: Rlevels[level]
-    uint32_t* rc = Rk;
-    size_t rn = n_out;
-    int pp = 0;
-    while (rn > (size_t)G) {
-      int Ls = ctx->L;
-      while ((size_t)Ls > rn / G) Ls >>= 1;
-      size_t ro = rn / Ls;
-      uint32_t* dst = (ro == (size_t)G) ? ctx->Rlevels + (size_t)level * 108 * G : ctx->sumR[pp];
-      launch_sum(st2, rc, rn, (uint32_t)rn, Ls, (uint32_t)(rn / G / Ls), dst);      // same coalesced grouping inside each group
-      rc = dst; rn = ro; pp ^= 1;
-    }
-    if (n_out == (size_t)G) {   // R already one per group
-      HIP_TRY(hipMemcpyAsync(ctx->Rlevels + (size_t)level * 108 * G, Rk, (size_t)108 * G * 4, hipMemcpyDeviceToDevice, st2));
-    }
-    r_off += n_out;
-    cur = S; n_cur = n_out; level++;
-  }
-  HIP_TRY(hipEventRecord(ctx->ev2, st2));
-  HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
-  // the last S (one item per group) has weight 0 at its level (o = 0 for level >= 1) and is dropped.
-  hipLaunchKernelGGL(edw ? k_window_combine_edw : k_window_combine, dim3(nblk((size_t)G * 4, 64)), dim3(64), 0, st, ctx->Rlevels, level, G, ls, ctx->sumR[0]);
-  hipLaunchKernelGGL(edw ? k_hilo_combine_edw : k_hilo_combine, dim3(nblk((size_t)W * 4, 64)), dim3(64), 0, st, ctx->sumR[0], W, lo_bits, ctx->win_abi,
-                     ctx->merged == 2 ? cur : (uint32_t*)nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(ctx->win_host, ctx->win_abi, (size_t)W * 48 * 8 * (ctx->merged == 2 ? 2 : 1), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipEventRecord(ctx->ev_done, st));
-  ctx->win_edw = edw;         // what win_host will hold for THIS launch (the context may serve an XYZZ set next)
-  ctx->pending = true;        // only a completely enqueued sequence is collectable; a failed launch leaves the context reusable
-  return ZKHIP_OK;
+  lp.edw = merged == 1 && K == 1 && ctx->K == 1 && ctx->aff_levels == 0 && jobs[0].edw != nullptr;
+  lp.wf = lp.edw ? ZK_W_NEXT : ZK_W_FIRST;
+  lp.red = red_kernels(lp.edw);
+  lp.nb = ctx->B * ctx->W;
+  lp.bshift = merged ? c - 1 : 31;
+  for (int k = 0; k < MSM_MAX_JOBS; k++) lp.bp.p[k] = jobs[k < K ? k : 0].bases;
+  if (lp.edw) lp.bp.p[0] = reinterpret_cast<const AffPacked*>(jobs[0].edw);     // (k_accumulate_edw reads it as EdwPacked)
+  lp.cur_off = ctx->offsets;
+  lp.cur_cnt = ctx->counts;
+  lp.m_cur = (size_t)Wd * (n_eff ? n_eff : 1);       // entries that can occur: a base at infinity never produces one
+  int r = stage_sort(ctx, lp);
+  if (!r) r = stage_affine_levels(ctx, lp);
+  if (!r) r = stage_accumulate(ctx, lp);
+  if (!r) r = stage_stitch(ctx, lp);
+  if (!r) r = stage_reduce(ctx, lp);
+  return r ? r : stage_copy_out(ctx, lp);
 }
 
 // Wait for the MSM enqueued by msm_launch and finish it on the host.
@@ -2263,9 +2156,9 @@ int msm_finish(MsmCtx* ctx, uint64_t out_jac[36]) {
 int msm_table_build(AffPacked* d_table, uint8_t* d_tinf, size_t n, int c, int naf, char* errbuf, size_t errlen) {
   const int levels = msm_table_levels(c, naf);
   if (n == 0 || levels < 2) return ZKHIP_OK;
-  WindowPlan plan;
-  memset(&plan, 0, sizeof plan);
-  window_layout(c, plan.off, plan.bits);
+  WindowPlan wp;
+  memset(&wp, 0, sizeof wp);
+  plan::window_layout(c, wp.off, wp.bits);
   // points per launch: (levels - 1) * chunk slots of 135 words, at most 4M slots (2.2 GB of work space)
   size_t chunk = ((size_t)1 << 22) / (size_t)(levels - 1);
   chunk &= ~(size_t)255;
@@ -2275,7 +2168,7 @@ int msm_table_build(AffPacked* d_table, uint8_t* d_tinf, size_t n, int c, int na
   hipError_t e = hipMalloc(&work, (size_t)stride * 135 * 4);
   for (size_t i0 = 0; e == hipSuccess && i0 < n; i0 += chunk) {
     uint32_t cn = (uint32_t)((n - i0 < chunk) ? n - i0 : chunk);
-    hipLaunchKernelGGL(k_table_build, dim3(nblk(cn, 256)), dim3(256), 0, 0, d_table, d_tinf, n, i0, cn, plan, levels, naf ? 1 : 0, work, stride);
+    hipLaunchKernelGGL(k_table_build, dim3(nblk(cn, 256)), dim3(256), 0, 0, d_table, d_tinf, n, i0, cn, wp, levels, naf ? 1 : 0, work, stride);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
