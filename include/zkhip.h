@@ -326,9 +326,11 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
  * and the same equation as zkhip_groth16_verify above, for MANY proofs under one key at once: the reduced Tate pairing of
  * zkhip_groth16_verify as gfx950 kernels (pairing.cuh / pairing.hip), eight lanes per verification, and
  * acc = ABC_0 + sum x_i ABC_i per proof on the device.  Verdicts equal zkhip_groth16_verify's on every input that meets the
- * PRECONDITIONS, which - as in the host route's pairing - are NOT checked here: every point of the key and of the proofs is on its
- * curve and of order r, or the point at infinity (all zero).  Encodings, the fixed G2 generator paired with acc, and "a pair with a
- * member at infinity contributes 1" are the host route's.
+ * PRECONDITIONS: every coordinate and input is fully reduced, and every point of the key and of the proofs is on its curve and of
+ * order r, or the point at infinity (all zero).  zkhip_verifier_new and zkhip_verifier_verify_batch do NOT check them (their result
+ * on other inputs is undefined) and are for proofs the caller made or has checked; for proofs from anybody else use the CHECKED
+ * route below (zkhip_verifier_new_checked / zkhip_verifier_verify_batch_checked), which validates every point on the device before
+ * the pairing.  The fixed G2 generator paired with acc, and "a pair with a member at infinity contributes 1" are the host route's.
  * A handle owns its stream and work space and lives on the calling thread's library device (zkhip_set_device); ONE batch is in
  * flight per handle, several handles - one host thread each - run beside each other and beside provers.  There is no CPU fallback:
  * ZKHIP_ERR_NO_DEVICE / ZKHIP_ERR_STATE without an initialised device.  count == 0 returns ZKHIP_OK; n_inputs == 0 is valid.
@@ -340,6 +342,43 @@ int zkhip_verifier_new(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2
 size_t zkhip_verifier_num_inputs(const zkhip_verifier* v);
 int zkhip_verifier_verify_batch(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* ok);
 void zkhip_verifier_free(zkhip_verifier* v);
+
+/* ---- checked batches: the verifier for proofs somebody else made --------------------------------------------------------------
+ * One status byte per proof.  Low nibble: the code below.  High nibble: the elements of the proof that fail with that code
+ * (ZKHIP_VERIFY_MASK_*; zero for ACCEPT and REJECT).  The code is the FIRST of ENCODING, OFF_CURVE, NOT_ORDER_R that applies to any
+ * element of the proof, and the mask names exactly the elements failing with that code, so the byte is a function of the proof alone
+ * and the device and the host routes give the same one.  The all-zero point is the point at infinity and passes the point checks
+ * (the pairing then decides as in the unchecked route); a point with x = 0 and y != 0 is not infinity. */
+#define ZKHIP_VERIFY_ACCEPT 0       /* all checks pass and the pairing product is one */
+#define ZKHIP_VERIFY_REJECT 1       /* all checks pass, the pairing product is not one */
+#define ZKHIP_VERIFY_ENCODING 2     /* a coordinate's 12 limbs are >= q, or an input's 6 limbs are >= r (not fully reduced Montgomery form) */
+#define ZKHIP_VERIFY_OFF_CURVE 3    /* encodings fine; a point is neither all-zero nor on its curve (A, C: y^2 = x^3 - 1; B: y^2 = x^3 + 4) */
+#define ZKHIP_VERIFY_NOT_ORDER_R 4  /* encodings fine, every point on its curve; [r] P != O for some point */
+#define ZKHIP_VERIFY_MASK_A 0x10
+#define ZKHIP_VERIFY_MASK_B 0x20
+#define ZKHIP_VERIFY_MASK_C 0x40
+#define ZKHIP_VERIFY_MASK_INPUT 0x80
+/* zkhip_verifier_new_checked: as zkhip_verifier_new, but first validates the key's n_inputs + 4 points on the device (the kernel the
+ * batches use, once): each is fully reduced and either at infinity or on its curve and of order r.  A key that fails is refused with
+ * ZKHIP_ERR_ARG, zkhip_last_error() naming the first offending element (alpha, beta, delta, ABC[i]) and its code.  Only handles
+ * made here serve zkhip_verifier_verify_batch_checked (ZKHIP_ERR_STATE otherwise); they serve zkhip_verifier_verify_batch as well.
+ * zkhip_verifier_verify_batch_checked: before the pairing, one lane per proof point compares the raw limbs with q, checks the curve
+ * equation and computes [r] P (double-and-add, 377 doublings and 135 additions); the inputs are compared with r.  A refused proof
+ * enters the pairing kernels as points at infinity and zeros, its status comes from the checks alone.  Same chunking, stream and
+ * synchronisation as the unchecked route; on every proof with status 0 or 1, status == 0 equals zkhip_verifier_verify_batch's ok.
+ * count == 0 returns ZKHIP_OK.  status: count bytes. */
+int zkhip_verifier_new_checked(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                               const uint64_t* vk_abc, size_t n_inputs, zkhip_verifier** out);
+int zkhip_verifier_verify_batch_checked(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                                        uint8_t* status);
+/* The same checks on the host (no device, no zkhip_init): the reference the device route is pinned on.
+ * zkhip_bw6_761_point_check: *code = 0, ZKHIP_VERIFY_ENCODING, _OFF_CURVE or _NOT_ORDER_R for one point (x | y); g2 != 0 selects
+ * y^2 = x^3 + 4.  zkhip_groth16_verify_checked: the status byte zkhip_verifier_verify_batch_checked gives for this proof (its
+ * verdict, where nothing is refused, is zkhip_groth16_verify's); ZKHIP_ERR_ARG for a key that fails the checks. */
+int zkhip_bw6_761_point_check(const uint64_t p[24], int g2, int* code);
+int zkhip_groth16_verify_checked(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                 const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_affine[72],
+                                 uint8_t* status);
 
 /* ---- the wrapping (aggregator) circuit: host code, no device needed ------------------------------- */
 /* Nested objects are over BLS12-377, whose base field is Fr of BW6-761: coordinates are 6-limb Montgomery

@@ -2,6 +2,10 @@
 """Groth16 verification of the batch-2 wrapping key's proofs: the GPU pairing kernels (zkhip.Verifier) against the host route
 (zkhip.groth16_verify) on 16 threads, measured in the same run, and the wrapping stream's rate with and without a Verifier checking
 every proof beside it.  Writes profiles/verify_gpu.txt (or --out).  Each block runs once; the first GPU call (work space) is not timed.
+The checked route (Verifier(vk, checked=True).verify_batch_checked: every proof point validated on the device first) is timed beside
+the unchecked one on the same batches, no proof refused so that every point walks all 377 bits of r: unchecked, checked, three
+times over at every count, the median of each.  GATE 2: checked <= 1.25 x unchecked at 1,024 proofs.
+profiles/verify_checked.txt is a run with --out profiles/verify_checked.txt (profiles/verify_gpu.txt is the run before this column).
 Usage: python tools/verify_ab.py [--out FILE] [--stream N] [--gpu-slots K]"""
 import argparse
 import os
@@ -14,6 +18,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HOST_THREADS = 16
+CHECKED_GATE = 1.25                 # checked ms / unchecked ms at 1,024 proofs
+ROUNDS = 3
 COUNTS = (1, 64, 1024, 16384)
 EXTRA = (16, 32, 128, 256)          # more points for the count at which the GPU overtakes the host
 BATCH = 256
@@ -68,22 +74,37 @@ def main():
     # ---- GPU route
     ver = zkhip.Verifier(vk)
     ver.verify_batch(pool_in[:1], pool[:1])
-    say("%8s %12s %16s %14s %s" % ("count", "ms/batch", "verifications/s", "host ms (16 t)", "GPU faster"))
-    gpu_ms = {}
+    chk = zkhip.Verifier(vk, checked=True)
+    chk.verify_batch_checked(pool_in[:1], pool[:1])
+    say("%8s %12s %16s %14s %-10s %12s %8s" % ("count", "ms/batch", "verifications/s", "host ms (16 t)", "GPU faster", "checked ms", "ratio"))
+    gpu_ms, chk_ms = {}, {}
     for count in sorted(COUNTS + EXTRA):
         idx = np.arange(count) % args.pool
         inp, prf = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
-        t = time.perf_counter()
-        ok = ver.verify_batch(inp, prf)
-        dt = time.perf_counter() - t
-        assert list(ok) == [i != args.pool - 1 for i in idx], "GPU verdicts at count %d" % count
-        gpu_ms[count] = dt * 1e3
+        want = [i != args.pool - 1 for i in idx]
+        plain, checked = [], []
+        for _ in range(ROUNDS):                                  # the two routes take turns on the same batch
+            t = time.perf_counter()
+            ok = ver.verify_batch(inp, prf)
+            plain.append(time.perf_counter() - t)
+            assert list(ok) == want, "GPU verdicts at count %d" % count
+            t = time.perf_counter()
+            codes, masks = chk.verify_batch_checked(inp, prf)
+            checked.append(time.perf_counter() - t)
+            assert list(codes) == [0 if w else 1 for w in want] and not masks.any(), "checked statuses at count %d" % count
+        dt, dc = sorted(plain)[ROUNDS // 2], sorted(checked)[ROUNDS // 2]
+        gpu_ms[count], chk_ms[count] = dt * 1e3, dc * 1e3
         host_ms = count / host_rate * 1e3 if count >= HOST_THREADS else 1e3 / (host_rate / HOST_THREADS)
-        say("%8d %12.1f %16.1f %14.1f %s%s" % (count, dt * 1e3, count / dt, host_ms, "yes" if dt * 1e3 < host_ms else "no", "" if count in COUNTS else "   (crossover probe)"))
+        say("%8d %12.1f %16.1f %14.1f %-10s %12.1f %8.3f%s" % (count, dt * 1e3, count / dt, host_ms, "yes" if dt * 1e3 < host_ms else "no", dc * 1e3, dc / dt,
+                                                             "" if count in COUNTS else "   (crossover probe)"))
     over = [c for c in sorted(gpu_ms) if gpu_ms[c] < (c / host_rate * 1e3 if c >= HOST_THREADS else 1e3 / (host_rate / HOST_THREADS))]
     say("the GPU overtakes the %d host threads at count %s (smallest measured count at which its batch is faster)" % (HOST_THREADS, over[0] if over else "none measured"))
     gate = gpu_ms[1024] < 1024 / host_rate * 1e3
     say("GATE (GPU faster than %d host threads at 1,024 proofs): %s  (%.1fx)" % (HOST_THREADS, "met" if gate else "MISSED", (1024 / host_rate * 1e3) / gpu_ms[1024]))
+    ratio = chk_ms[1024] / gpu_ms[1024]
+    gate2 = ratio <= CHECKED_GATE
+    say("GATE 2 (checked batch <= %.2f x unchecked at 1,024 proofs, medians of %d alternating runs): %s  (%.3fx: %.1f ms of checks on %.1f ms)"
+        % (CHECKED_GATE, ROUNDS, "met" if gate2 else "MISSED", ratio, chk_ms[1024] - gpu_ms[1024], gpu_ms[1024]))
 
     # ---- the wrapping stream with and without a Verifier beside it (interleaved: without, with, without, with)
     if args.stream:
@@ -128,11 +149,11 @@ def main():
             say("  %-18s %8.1f" % ("with Verifier" if w else "without Verifier", r))
         for p_ in provers:
             p_.free()
-    ver.free(); crs.free(); kp.free(); agg.free()
+    ver.free(); chk.free(); crs.free(); kp.free(); agg.free()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
-    return 0 if gate else 1
+    return 0 if gate and gate2 else 1
 
 
 if __name__ == "__main__":

@@ -17,6 +17,8 @@
 // LAZY BOUNDS ([k]: value < k p, limbs normalised; fp29.cuh: a b + c d < 2^10 R p, R / p > 2^22, fp_sub<K>(a, b) needs b <= K p):
 //   Fq6 coefficients in memory are [4]; -4 x of a [4] value is [16]; line coefficients l3, l4 are [2], l0 is [6]; Jacobian X [18], Y [4], Z [4].
 #pragma once
+#include "../../include/zkhip.h"
+#include "ec.cuh"
 #include "fp29.cuh"
 
 namespace zkhip {
@@ -127,6 +129,80 @@ ZK_HD ZK_INL bool miller_add_step(MillerPoint& T, const MillerConst& c, bool don
   T.X = X3;
   T.Z = D;                                                                // [2]
   return done;
+}
+
+// ---- checked batches: encoding, curve membership and order of one point, one lane per point.
+// A point is 24 ABI limbs (x | y); all zero is the point at infinity and passes (it is in the group).  The codes are zkhip.h's
+// ZKHIP_VERIFY_*: 0 fine, ENCODING (a coordinate >= q), OFF_CURVE, NOT_ORDER_R.  A lane stops at its first failure: a point that is not
+// reduced is never multiplied, a point off its curve never enters the group law.
+
+// x (N64 raw ABI limbs) >= the modulus: the borrow of x - p, no branches
+template <class PR>
+ZK_HD ZK_INL bool abi_geq_modulus(const uint64_t* x) {
+  uint64_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < PR::N64; i++) {
+    const uint64_t a = x[i], m = PR::P64[i], d = a - m;
+    borrow = (uint64_t)(a < m) | (uint64_t)(d < borrow);
+  }
+  return borrow == 0;
+}
+
+// y^2 = x^3 + b (b = -1 on G1's curve, 4 on G2's) for x, y [2].  Both sides go into ONE difference that is reduced below 2 p before it
+// is compared with zero (the idiom of ec_edw.cuh edw_from_affine): nothing lazily bounded is ever compared.
+ZK_HD ZK_INL bool point_on_curve(const Fq& x, const Fq& y, bool g2) {
+  const Fq one = fp_one<FqParams>(), zero = fp_zero<FqParams>();            // one is canonical: [1]
+  const Fq yy = fp_sqr(y);                                                  // [2]
+  const Fq xxx = fp_mul(fp_sqr(x), x);                                      // [2]
+  const Fq lhs = fp_add(yy, fq_select(g2, zero, one));                      // [3]   y^2 (+ 1 on G1)
+  const Fq rhs = fp_add(xxx, fq_select(g2, fp_dbl(fp_dbl(one)), zero));     // [6]   x^3 (+ 4 on G2)
+  const Fq d = fp_sub<FqParams, 8>(lhs, rhs);                               // [11]  lhs - rhs + 8 p          (rhs is [6] <= 8)
+  return fp_is_zero_2p(fp_cond_sub_kp<FqParams, 2>(fp_cond_sub_kp<FqParams, 4>(fp_cond_sub_kp<FqParams, 8>(d))));   // < 16 p -> < 2 p
+}
+
+// [r] P = O by double-and-add over r's 377 bits, most significant first; r_order: six 64-bit words, the same bit for every lane.
+// x, y [2] (fp_from_abi of reduced limbs), P on its curve.  The formulas of ec.cuh never use b, so one path serves G1 and G2, and they
+// are complete: xyzz_madd opens from infinity, takes the same-x branch (every valid point ends with (r - 1) P + P = -P + P = O there;
+// a point of order 3 reaches it in the second iteration) and xyzz_dbl sends a point of order 2 (Y = 0) to ZZ = 0.
+// Bounds: acc leaves xyzz_dbl with X [6], Y [4] and xyzz_madd with X [10], Y [4] (or [2], [2] opened from P; [6], [4] doubled from P):
+// always within xyzz_dbl's and xyzz_madd's X [10], Y [4]; ZZ, ZZZ are products [2] or exact zeros.
+ZK_HD ZK_INL bool point_has_order_r(const Fq& x, const Fq& y, const uint64_t* r_order) {
+  XYZZ acc = xyzz_infinity();
+#pragma unroll 1
+  for (int i = PAIRING_MILLER_STEPS; i >= 0; i--) {
+    acc = xyzz_dbl(acc);                                                    // X [6], Y [4]
+    if ((r_order[i >> 6] >> (i & 63)) & 1) xyzz_madd(acc, x, y);            // X [10], Y [4]
+  }
+  return xyzz_is_inf(acc);
+}
+
+ZK_HD ZK_INL int point_check(const uint64_t* p /* 24 ABI limbs */, bool g2, const uint64_t* r_order) {
+  if (abi_geq_modulus<FqParams>(p) || abi_geq_modulus<FqParams>(p + 12)) return ZKHIP_VERIFY_ENCODING;
+  uint64_t nz = 0;
+#pragma unroll
+  for (int k = 0; k < 24; k++) nz |= p[k];
+  if (nz == 0) return ZKHIP_VERIFY_ACCEPT;                                  // the point at infinity
+  const Fq x = fp_from_abi<FqParams>(p), y = fp_from_abi<FqParams>(p + 12); // [2]
+  if (!point_on_curve(x, y, g2)) return ZKHIP_VERIFY_OFF_CURVE;
+  return point_has_order_r(x, y, r_order) ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_NOT_ORDER_R;
+}
+
+// any of `n` scalars (6 raw ABI limbs each) >= r
+ZK_HD ZK_INL int inputs_check(const uint64_t* inputs, size_t n) {
+  bool bad = false;
+  for (size_t i = 0; i < n; i++) bad = bad || abi_geq_modulus<FrParams>(inputs + i * 6);
+  return bad ? ZKHIP_VERIFY_ENCODING : ZKHIP_VERIFY_ACCEPT;
+}
+
+// The codes of a proof's elements (A, B, C, the inputs as one) -> its status byte, 0 when nothing is refused: the first of ENCODING,
+// OFF_CURVE, NOT_ORDER_R that any element has, and in the high nibble the elements that have exactly that code.
+ZK_HD ZK_INL uint8_t verify_refusal(const uint8_t e[4]) {
+  for (int code = ZKHIP_VERIFY_ENCODING; code <= ZKHIP_VERIFY_NOT_ORDER_R; code++) {
+    int mask = 0;
+    for (int k = 0; k < 4; k++) if (e[k] == code) mask |= ZKHIP_VERIFY_MASK_A << k;
+    if (mask) return (uint8_t)(code | mask);
+  }
+  return 0;
 }
 
 }  // namespace zkhip

@@ -12,15 +12,21 @@ namespace zkhip {
 struct PairingCtx;
 
 // vk_* null: a context for pairing_products only.  Otherwise the key of zkhip_verifier_new (ABI limbs, host memory).
+// checked: the key's n_inputs + 4 points go through the point-check kernel first; ZKHIP_ERR_ARG names the first one that fails.
 int pairing_ctx_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc,
-                    size_t n_inputs, PairingCtx** out, char* errbuf, size_t errlen);
+                    size_t n_inputs, bool checked, PairingCtx** out, char* errbuf, size_t errlen);
+bool pairing_ctx_checked(const PairingCtx* c);     // made with checked set, and the key passed
+// the message of a refused key: element 0, 1, 2 = alpha, beta, delta, 3 + i = ABC[i]; code = ZKHIP_VERIFY_ENCODING, _OFF_CURVE or _NOT_ORDER_R
+void pairing_key_refusal(size_t element, int code, char* buf, size_t len);
 void pairing_ctx_free(PairingCtx* c);
 size_t pairing_ctx_num_inputs(const PairingCtx* c);
 
 // out[i] = prod_{p < pairs} t(g1[i][p], g2[i][p]), reduced GT value, 6 x 12 ABI limbs.  pairs in 1 .. 4.
 int pairing_products(PairingCtx* c, const uint64_t* g1, const uint64_t* g2, int pairs, size_t count, uint64_t* out, char* errbuf, size_t errlen);
-// ok[i] = e(A_i, B_i) e(acc_i, -g2) e(alpha, -beta) e(C_i, -delta) == 1
-int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, uint8_t* ok, char* errbuf, size_t errlen);
+// ok[i] = e(A_i, B_i) e(acc_i, -g2) e(alpha, -beta) e(C_i, -delta) == 1.  checked (a context whose key was checked, else
+// ZKHIP_ERR_STATE): every proof point is validated on the device first and ok[i] is the status byte of zkhip.h (ZKHIP_VERIFY_*).
+int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, char* errbuf,
+                         size_t errlen);
 // op 0: a b, 1: a^2, 2: a (b0 + b3 w^3 + b4 w^4) through the lane bodies of pairing.cuh; a, b, out: n x 72 ABI limbs
 int pairing_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen);
 

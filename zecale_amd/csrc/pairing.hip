@@ -7,6 +7,10 @@
 // the lines of the four pairs and their running points.  Every loop has a fixed trip count (376 Miller iterations, the exponent's bit
 // length, the scalar's 377 bits); the only synchronisation is the workgroup barrier, which every thread of a workgroup reaches the same
 // number of times: groups past the end of the batch recompute the last verification and store nothing.  No waits, no spins, no atomics.
+//
+// Checked batches put k_point_check in front: one lane per proof point (and per key point, once), no LDS and no barrier, so a lane
+// leaves at its first failure.  It writes one code per element; a proof with any code set is FLAGGED, and the kernels behind read its
+// points and inputs as the point at infinity and zero (the `flags` arguments, null on the unchecked route).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -27,9 +31,17 @@ constexpr size_t PAIRING_CHUNK = 16384;                        // verifications 
 // ---- ABI points -> the constants of a Miller loop.  One lane per pair.
 __global__ void __launch_bounds__(64) k_pair_prep(const uint64_t* __restrict__ g1, const uint64_t* __restrict__ g2,
                                                   const uint64_t* __restrict__ quarter /* 1/4, -1/4 (ABI) */, size_t n,
-                                                  MillerConst* __restrict__ pairs, uint32_t* __restrict__ inf) {
+                                                  MillerConst* __restrict__ pairs, uint32_t* __restrict__ inf,
+                                                  const uint32_t* __restrict__ flags /* per product, or null */, int np) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (flags && flags[i / np]) {                    // a flagged proof: its four pairs are pairs of points at infinity, its product is 1
+    MillerConst z;
+    z.px = z.py = z.xq4 = z.yq4n = fp_zero<FqParams>();
+    pairs[i] = z;
+    inf[i] = 1u;
+    return;
+  }
   uint64_t nz1 = 0, nz2 = 0;
   for (int k = 0; k < 24; k++) { nz1 |= g1[i * 24 + k]; nz2 |= g2[i * 24 + k]; }
   MillerConst c;
@@ -138,6 +150,27 @@ __global__ void __launch_bounds__(PAIRING_BLOCK) k_fq6_selftest(int op, const ui
   }
 }
 
+// ---- checked batches: encoding, curve and order of every point (pairing.cuh point_check), one lane per point.
+// key == 0, the staged chunk of pairing_verify_batch: lane t checks element t % 3 of proof t / 3 - A (first G1 slot), B (first G2 slot),
+// C (fourth G1 slot) - and A's lane also compares the proof's inputs with r.  codes: four bytes per proof (A, B, C, inputs); the
+// kernels behind read them as one word, non-zero = flagged.
+// key == 1, a verification key: g1 holds alpha | beta | delta | ABC_0 .., point 1 and 2 are G2's; codes: one byte per point.
+__global__ void __launch_bounds__(64) k_point_check(const uint64_t* __restrict__ g1, const uint64_t* __restrict__ g2, const uint64_t* __restrict__ inputs,
+                                                    size_t n_inputs, size_t total, int key, const uint64_t* __restrict__ r_order,
+                                                    uint8_t* __restrict__ codes) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  if (key) {
+    codes[t] = (uint8_t)point_check(g1 + t * 24, t == 1 || t == 2, r_order);
+    return;
+  }
+  const size_t j = t / 3;
+  const int e = (int)(t % 3);
+  if (e == 0) codes[j * 4 + 3] = (uint8_t)inputs_check(inputs + j * n_inputs * 6, n_inputs);
+  const uint64_t* p = e == 1 ? g2 + j * 4 * 24 : g1 + (j * 4 + (e == 2 ? 3 : 0)) * 24;
+  codes[j * 4 + e] = (uint8_t)point_check(p, e == 1, r_order);
+}
+
 // ---- acc = ABC_0 + sum x_i ABC_i.  The key's points in device form: x, y (27 limbs each) and an infinity flag.
 struct AbcDev {
   Fq x, y;
@@ -156,9 +189,13 @@ __global__ void __launch_bounds__(64) k_abc_prep(const uint64_t* __restrict__ ab
 // one lane per (proof, input): x_i ABC_i by double-and-add over the scalar's 377 bits, most significant first (the scalar is shifted
 // through its twelve words, so no word is ever picked by a run-time index).  terms[t] = (X, Y, ZZ, ZZZ), 4 x 27 limbs.
 __global__ void __launch_bounds__(64) k_acc_terms(const uint64_t* __restrict__ inputs, const AbcDev* __restrict__ abc, size_t n_inputs, size_t total,
-                                                  XYZZ* __restrict__ terms) {
+                                                  XYZZ* __restrict__ terms, const uint32_t* __restrict__ flags /* per proof, or null */) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
+  if (flags && flags[t / n_inputs]) {              // a flagged proof: its inputs are zeros, its terms the point at infinity
+    terms[t] = xyzz_infinity();
+    return;
+  }
   const AbcDev* base = abc + 1 + t % n_inputs;
   uint32_t w[12];
   fp_abi_to_canonical_words<FrParams>(inputs + t * 6, w);
@@ -181,9 +218,13 @@ __global__ void __launch_bounds__(64) k_acc_terms(const uint64_t* __restrict__ i
 
 // one lane per proof: ABC_0 + the proof's terms, to affine with one inversion, ABI limbs into the product's second G1 slot
 __global__ void __launch_bounds__(64) k_acc_sum(const XYZZ* __restrict__ terms, const AbcDev* __restrict__ abc, size_t n_inputs, size_t count,
-                                                uint64_t* __restrict__ g1 /* count x 4 x 24 */) {
+                                                uint64_t* __restrict__ g1 /* count x 4 x 24 */, const uint32_t* __restrict__ flags /* per proof, or null */) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= count) return;
+  if (flags && flags[j]) {                         // a flagged proof: acc is the point at infinity
+    for (int k = 0; k < 24; k++) g1[(j * 4 + 1) * 24 + k] = 0;
+    return;
+  }
   XYZZ acc = abc[0].inf ? xyzz_infinity() : xyzz_from_affine(abc[0].x, abc[0].y);
 #pragma unroll 1
   for (size_t i = 0; i < n_inputs; i++) {
@@ -239,8 +280,10 @@ struct PairingCtx {
   MillerConst* d_pairs = nullptr;
   uint32_t* d_inf = nullptr;
   Fq* d_f = nullptr;
+  uint8_t* d_codes = nullptr;       // checked batches: four codes per proof (k_point_check), one word per proof as the flag array
   // verifier handles
   bool has_key = false;
+  bool checked = false;             // the key passed k_point_check (pairing_ctx_new with checked set)
   size_t n_inputs = 0;
   AbcDev* d_abc = nullptr;
   uint64_t* d_inputs = nullptr;
@@ -248,11 +291,12 @@ struct PairingCtx {
   size_t in_cap = 0;
   uint64_t alpha[24], neg_g2[24], neg_beta[24], neg_delta[24];
   std::vector<uint64_t> h_g1, h_g2, h_gt;
+  std::vector<uint8_t> h_codes;
 };
 
 static void ctx_release_work(PairingCtx* c) {
-  for (void* p : {(void*)c->d_g1, (void*)c->d_g2, (void*)c->d_gt, (void*)c->d_pairs, (void*)c->d_inf, (void*)c->d_f}) if (p) (void)hipFree(p);
-  c->d_g1 = c->d_g2 = c->d_gt = nullptr; c->d_pairs = nullptr; c->d_inf = nullptr; c->d_f = nullptr; c->cap = 0;
+  for (void* p : {(void*)c->d_g1, (void*)c->d_g2, (void*)c->d_gt, (void*)c->d_pairs, (void*)c->d_inf, (void*)c->d_f, (void*)c->d_codes}) if (p) (void)hipFree(p);
+  c->d_g1 = c->d_g2 = c->d_gt = nullptr; c->d_pairs = nullptr; c->d_inf = nullptr; c->d_f = nullptr; c->d_codes = nullptr; c->cap = 0;
 }
 
 static int ctx_reserve(PairingCtx* c, size_t count, char* errbuf, size_t errlen) {
@@ -264,6 +308,7 @@ static int ctx_reserve(PairingCtx* c, size_t count, char* errbuf, size_t errlen)
   PAIR_HIP(hipMalloc(&c->d_pairs, count * 4 * sizeof(MillerConst)));
   PAIR_HIP(hipMalloc(&c->d_inf, count * 4 * sizeof(uint32_t)));
   PAIR_HIP(hipMalloc(&c->d_f, count * 6 * sizeof(Fq)));
+  PAIR_HIP(hipMalloc(&c->d_codes, count * 4));
   c->cap = count;
   return ZKHIP_OK;
 }
@@ -277,9 +322,47 @@ void pairing_ctx_free(PairingCtx* c) {
 }
 
 size_t pairing_ctx_num_inputs(const PairingCtx* c) { return c ? c->n_inputs : 0; }
+bool pairing_ctx_checked(const PairingCtx* c) { return c && c->checked; }
+
+void pairing_key_refusal(size_t element, int code, char* buf, size_t len) {
+  static const char* const names[3] = {"alpha", "beta", "delta"};
+  const char* what = code == ZKHIP_VERIFY_ENCODING ? "ZKHIP_VERIFY_ENCODING" : code == ZKHIP_VERIFY_OFF_CURVE ? "ZKHIP_VERIFY_OFF_CURVE" : "ZKHIP_VERIFY_NOT_ORDER_R";
+  if (element < 3) snprintf(buf, len, "verification key refused: %s: %s (%d)", names[element], what, code);
+  else snprintf(buf, len, "verification key refused: ABC[%zu]: %s (%d)", element - 3, what, code);
+}
+
+// the key's n_inputs + 4 points through k_point_check, once: ZKHIP_ERR_ARG naming the first element that fails
+static int ctx_check_key(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc,
+                         size_t n_inputs, char* errbuf, size_t errlen) {
+  const size_t n = n_inputs + 4;
+  std::vector<uint64_t> pts(n * 24);
+  memcpy(&pts[0], vk_alpha_g1, 192); memcpy(&pts[24], vk_beta_g2, 192); memcpy(&pts[48], vk_delta_g2, 192);
+  memcpy(&pts[72], vk_abc, (n_inputs + 1) * 192);
+  std::vector<uint8_t> codes(n);
+  uint64_t* d_pts = nullptr;
+  uint8_t* d_kc = nullptr;
+  hipError_t e = hipMalloc(&d_pts, n * 192);
+  if (e == hipSuccess) e = hipMalloc(&d_kc, n);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_pts, pts.data(), n * 192, hipMemcpyHostToDevice, c->st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_point_check, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, d_pts, nullptr, nullptr, 0, n, 1, c->d_const, d_kc);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(codes.data(), d_kc, n, hipMemcpyDeviceToHost, c->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+  for (void* p : {(void*)d_pts, (void*)d_kc}) if (p) (void)hipFree(p);
+  PAIR_HIP(e);
+  for (size_t i = 0; i < n; i++) {
+    if (!codes[i]) continue;
+    if (errbuf) pairing_key_refusal(i, codes[i], errbuf, errlen);
+    return ZKHIP_ERR_ARG;
+  }
+  c->checked = true;
+  return ZKHIP_OK;
+}
 
 static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc,
-                    size_t n_inputs, char* errbuf, size_t errlen) {
+                    size_t n_inputs, bool checked, char* errbuf, size_t errlen) {
   using host::HFq;
   PAIR_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
   uint64_t k[6 + 66 + 24];
@@ -298,6 +381,10 @@ static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* 
   PAIR_HIP(hipMemcpyAsync(c->d_const, k, sizeof k, hipMemcpyHostToDevice, c->st));
   PAIR_HIP(hipStreamSynchronize(c->st));
   if (!vk_alpha_g1) return ZKHIP_OK;
+  if (checked) {                                   // before any host or device arithmetic on the key's points
+    const int rc = ctx_check_key(c, vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, errbuf, errlen);
+    if (rc != ZKHIP_OK) return rc;
+  }
   c->has_key = true;
   c->n_inputs = n_inputs;
   memcpy(c->alpha, vk_alpha_g1, 192);
@@ -323,24 +410,28 @@ static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* 
 }
 
 int pairing_ctx_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc, size_t n_inputs,
-                    PairingCtx** out, char* errbuf, size_t errlen) {
+                    bool checked, PairingCtx** out, char* errbuf, size_t errlen) {
   PairingCtx* c = new PairingCtx();
-  const int rc = ctx_init(c, vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, errbuf, errlen);
+  const int rc = ctx_init(c, vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, checked, errbuf, errlen);
   if (rc != ZKHIP_OK) { pairing_ctx_free(c); return rc; }
   *out = c;
   return ZKHIP_OK;
 }
 
-// d_g1 / d_g2 hold `count` products of `pairs` pairs: Miller loop, final exponentiation, GT values to the host
-static int run_products(PairingCtx* c, int pairs, size_t count, uint64_t* out, char* errbuf, size_t errlen) {
+// d_g1 / d_g2 hold `count` products of `pairs` pairs: Miller loop, final exponentiation, GT values to the host.
+// flags: null, or the checked route's word per product (non-zero: the product's pairs are read as points at infinity); codes_out: null,
+// or where the checked route's count x 4 codes go, in the same synchronisation as the GT values
+static int run_products(PairingCtx* c, int pairs, size_t count, uint64_t* out, const uint32_t* flags, uint8_t* codes_out, char* errbuf, size_t errlen) {
   const size_t n = count * (size_t)pairs;
-  hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_const + 72, n, c->d_pairs, c->d_inf);
+  hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_const + 72, n, c->d_pairs, c->d_inf, flags,
+                     pairs);
   hipLaunchKernelGGL(k_miller, dim3(blocks_for(count, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs, c->d_inf, pairs, count,
                      c->d_const, c->d_f);
   hipLaunchKernelGGL(k_final_exp, dim3(blocks_for(count, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_f, c->d_const + 6, c->fe_bits, count,
                      c->d_gt);
   PAIR_HIP(hipGetLastError());
   PAIR_HIP(hipMemcpyAsync(out, c->d_gt, count * 72 * 8, hipMemcpyDeviceToHost, c->st));
+  if (codes_out) PAIR_HIP(hipMemcpyAsync(codes_out, c->d_codes, count * 4, hipMemcpyDeviceToHost, c->st));
   PAIR_HIP(hipStreamSynchronize(c->st));
   return ZKHIP_OK;
 }
@@ -352,13 +443,20 @@ int pairing_products(PairingCtx* c, const uint64_t* g1, const uint64_t* g2, int 
     if (rc != ZKHIP_OK) return rc;
     PAIR_HIP(hipMemcpyAsync(c->d_g1, g1 + lo * pairs * 24, m * pairs * 192, hipMemcpyHostToDevice, c->st));
     PAIR_HIP(hipMemcpyAsync(c->d_g2, g2 + lo * pairs * 24, m * pairs * 192, hipMemcpyHostToDevice, c->st));
-    if ((rc = run_products(c, pairs, m, out + lo * 72, errbuf, errlen)) != ZKHIP_OK) return rc;
+    if ((rc = run_products(c, pairs, m, out + lo * 72, nullptr, nullptr, errbuf, errlen)) != ZKHIP_OK) return rc;
   }
   return ZKHIP_OK;
 }
 
-int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, uint8_t* ok, char* errbuf, size_t errlen) {
+// checked == false: ok[i] = 1 / 0.  checked == true: ok[i] is the status byte of zkhip.h (ZKHIP_VERIFY_*), k_point_check runs on the staged
+// chunk in front of k_acc_terms and its codes flag the refused proofs for the kernels behind.
+int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, char* errbuf,
+                         size_t errlen) {
   using host::HFq;
+  if (checked && !c->checked) {
+    if (errbuf) snprintf(errbuf, errlen, "checked batches need a handle of zkhip_verifier_new_checked");
+    return ZKHIP_ERR_STATE;
+  }
   const size_t ni = c->n_inputs;
   // the chunk also bounds the terms of a launch: 2^21 of them are 0.9 GB of work space
   size_t chunk = PAIRING_CHUNK;
@@ -389,13 +487,22 @@ int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* 
     }
     PAIR_HIP(hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
     PAIR_HIP(hipMemcpyAsync(c->d_g2, c->h_g2.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
-    if (ni) {
-      PAIR_HIP(hipMemcpyAsync(c->d_inputs, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
-      hipLaunchKernelGGL(k_acc_terms, dim3(blocks_for(m * ni, 64)), dim3(64), 0, c->st, c->d_inputs, c->d_abc, ni, m * ni, c->d_terms);
+    const uint32_t* flags = checked ? reinterpret_cast<const uint32_t*>(c->d_codes) : nullptr;
+    if (ni) PAIR_HIP(hipMemcpyAsync(c->d_inputs, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
+    if (checked) {
+      c->h_codes.resize(m * 4);
+      hipLaunchKernelGGL(k_point_check, dim3(blocks_for(m * 3, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_inputs, ni, m * 3, 0, c->d_const,
+                         c->d_codes);
     }
-    hipLaunchKernelGGL(k_acc_sum, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_terms, c->d_abc, ni, m, c->d_g1);
-    if ((rc = run_products(c, 4, m, c->h_gt.data(), errbuf, errlen)) != ZKHIP_OK) return rc;
-    for (size_t j = 0; j < m; j++) ok[lo + j] = memcmp(&c->h_gt[j * 72], one, sizeof one) == 0 ? 1 : 0;
+    if (ni) hipLaunchKernelGGL(k_acc_terms, dim3(blocks_for(m * ni, 64)), dim3(64), 0, c->st, c->d_inputs, c->d_abc, ni, m * ni, c->d_terms, flags);
+    hipLaunchKernelGGL(k_acc_sum, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_terms, c->d_abc, ni, m, c->d_g1, flags);
+    if ((rc = run_products(c, 4, m, c->h_gt.data(), flags, checked ? c->h_codes.data() : nullptr, errbuf, errlen)) != ZKHIP_OK) return rc;
+    for (size_t j = 0; j < m; j++) {
+      const bool is_one = memcmp(&c->h_gt[j * 72], one, sizeof one) == 0;
+      if (!checked) { ok[lo + j] = is_one ? 1 : 0; continue; }
+      const uint8_t refused = verify_refusal(&c->h_codes[j * 4]);
+      ok[lo + j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
+    }
   }
   return ZKHIP_OK;
 }

@@ -10,6 +10,7 @@
 #pragma once
 #include <vector>
 
+#include "../../include/zkhip.h"
 #include "host_field.hpp"
 
 namespace zkhip {
@@ -127,6 +128,18 @@ inline Fq6 pairing_product_value(const std::vector<const uint64_t*>& g1, const s
       for (auto& m : ms) if (!m.done) miller_add(m, f);
   }
   return f.pow_limbs(FqParams::FINAL_EXP, FqParams::FINAL_EXP_LIMBS);
+}
+
+// The checks of the checked verifier for one point (x | y, 24 ABI limbs), in their order: 0, or ZKHIP_VERIFY_ENCODING (a
+// coordinate >= q), ZKHIP_VERIFY_OFF_CURVE (neither all-zero nor on y^2 = x^3 - 1 / x^3 + 4), ZKHIP_VERIFY_NOT_ORDER_R ([r] P != O).
+// The all-zero point is the point at infinity and passes.  HJac's addition is complete, so points of any order go through mul_canonical.
+inline int point_check_host(const uint64_t* p, bool g2) {
+  if (HFq::geq_p(p) || HFq::geq_p(p + 12)) return ZKHIP_VERIFY_ENCODING;
+  const HFq x = HFq::from_limbs(p), y = HFq::from_limbs(p + 12);
+  if (x.is_zero() && y.is_zero()) return 0;
+  const HFq b = g2 ? HFq::one().dbl().dbl() : HFq::one().neg();
+  if (y.sqr() != x.sqr() * x + b) return ZKHIP_VERIFY_OFF_CURVE;
+  return HJac::from_affine(x, y).mul_canonical(FqParams::R_ORDER64, 6).is_inf() ? 0 : ZKHIP_VERIFY_NOT_ORDER_R;
 }
 
 // prod_i t(P_i, Q_i) == 1 ?

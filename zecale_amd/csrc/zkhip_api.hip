@@ -15,6 +15,7 @@
 #include "ntt.h"
 #include "qap.h"
 #include "pairing_host.hpp"
+#include "pairing.cuh"
 #include "pairing.h"
 #include "witness.h"
 #include <chrono>
@@ -1580,17 +1581,58 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
   return ZKHIP_OK;
 }
 
+// ---- the checks of the checked verifier on the host (pairing_host.hpp point_check_host): no device
+int zkhip_bw6_761_point_check(const uint64_t p[24], int g2, int* code) {
+  if (!p || !code) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *code = host::point_check_host(p, g2 != 0);
+  return ZKHIP_OK;
+}
+
+int zkhip_groth16_verify_checked(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                 const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_affine[72],
+                                 uint8_t* status) {
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !proof_affine || !status || (n_inputs && !inputs))
+    return fail(ZKHIP_ERR_ARG, "null pointer");
+  const uint64_t* key[3] = {vk_alpha_g1, vk_beta_g2, vk_delta_g2};
+  for (size_t i = 0; i < n_inputs + 4; i++) {      // the order and the words of the device route's key check
+    const int code = host::point_check_host(i < 3 ? key[i] : vk_abc + (i - 3) * 24, i == 1 || i == 2);
+    if (!code) continue;
+    pairing_key_refusal(i, code, t_err, sizeof t_err);
+    return ZKHIP_ERR_ARG;
+  }
+  uint8_t e[4];
+  e[0] = (uint8_t)host::point_check_host(proof_affine, false);
+  e[1] = (uint8_t)host::point_check_host(proof_affine + 24, true);
+  e[2] = (uint8_t)host::point_check_host(proof_affine + 48, false);
+  e[3] = ZKHIP_VERIFY_ACCEPT;
+  for (size_t i = 0; i < n_inputs; i++) if (host::HFr::geq_p(inputs + i * 6)) e[3] = ZKHIP_VERIFY_ENCODING;
+  if ((*status = verify_refusal(e)) != 0) return ZKHIP_OK;
+  int ok = 0;
+  const int rc = zkhip_groth16_verify(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, inputs, n_inputs, proof_affine, &ok);
+  if (rc != ZKHIP_OK) return rc;
+  *status = ok ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT;
+  return ZKHIP_OK;
+}
+
 // ---- Groth16 verification in batches on the device (pairing.hip)
-int zkhip_verifier_new(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
-                       size_t n_inputs, zkhip_verifier** out) {
+static int verifier_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc, size_t n_inputs,
+                        bool checked, zkhip_verifier** out) {
   if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called (the pairing kernels are the only batch verifier)");
   BIND_CUR();
   if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
   PairingCtx* ctx = nullptr;
-  const int rc = pairing_ctx_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, &ctx, t_err, sizeof t_err);
+  const int rc = pairing_ctx_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, checked, &ctx, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
   *out = new zkhip_verifier{ctx, cur_dev()};
   return ZKHIP_OK;
+}
+int zkhip_verifier_new(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                       size_t n_inputs, zkhip_verifier** out) {
+  return verifier_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, false, out);
+}
+int zkhip_verifier_new_checked(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                               size_t n_inputs, zkhip_verifier** out) {
+  return verifier_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, true, out);
 }
 size_t zkhip_verifier_num_inputs(const zkhip_verifier* v) { return v ? pairing_ctx_num_inputs(v->ctx) : 0; }
 int zkhip_verifier_verify_batch(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* ok) {
@@ -1598,7 +1640,15 @@ int zkhip_verifier_verify_batch(zkhip_verifier* v, const uint64_t* inputs, const
   if (count == 0) return ZKHIP_OK;
   if (!proofs_affine || !ok || (pairing_ctx_num_inputs(v->ctx) && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
   BIND(v);
-  return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, ok, t_err, sizeof t_err);
+  return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, false, ok, t_err, sizeof t_err);
+}
+int zkhip_verifier_verify_batch_checked(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* status) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (!pairing_ctx_checked(v->ctx)) return fail(ZKHIP_ERR_STATE, "checked batches need a handle of zkhip_verifier_new_checked");
+  if (count == 0) return ZKHIP_OK;
+  if (!proofs_affine || !status || (pairing_ctx_num_inputs(v->ctx) && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  BIND(v);
+  return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, true, status, t_err, sizeof t_err);
 }
 void zkhip_verifier_free(zkhip_verifier* v) {
   if (!v) return;
@@ -1630,7 +1680,7 @@ int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t
   if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called");
   BIND_CUR();
   PairingCtx* ctx = nullptr;
-  int rc = pairing_ctx_new(nullptr, nullptr, nullptr, nullptr, 0, &ctx, t_err, sizeof t_err);
+  int rc = pairing_ctx_new(nullptr, nullptr, nullptr, nullptr, 0, false, &ctx, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
   rc = pairing_products(ctx, g1, g2, (int)pairs_per_product, count, out, t_err, sizeof t_err);
   pairing_ctx_free(ctx);

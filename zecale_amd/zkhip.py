@@ -40,6 +40,7 @@ EXPORTS = [
     "zkhip_aggregator_witness_app", "zkhip_groth16_prove_app", "zkhip_prover_prove_app", "zkhip_prover_prove_app_dev", "zkhip_gpu_witness_run_batched_app",
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
     "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path",
+    "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
 ]
 
 
@@ -202,6 +203,10 @@ def load():
     lib.zkhip_verifier_num_inputs.restype = ctypes.c_size_t
     lib.zkhip_verifier_verify_batch.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
     lib.zkhip_verifier_free.argtypes = [ctypes.c_void_p]
+    lib.zkhip_verifier_new_checked.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, vpp]
+    lib.zkhip_verifier_verify_batch_checked.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.zkhip_bw6_761_point_check.argtypes = [c_u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.zkhip_groth16_verify_checked.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.c_void_p]
     lib.zkhip_internal_fq6_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
     lib.zkhip_internal_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
     _lib = lib
@@ -676,6 +681,35 @@ def groth16_verify(vk, inputs, proof):
     return bool(ok.value)
 
 
+# status of a proof on the checked routes (include/zkhip.h ZKHIP_VERIFY_*): the low nibble of its byte; the high nibble is the mask of
+# the elements that fail with that code
+VERIFY_ACCEPT, VERIFY_REJECT, VERIFY_ENCODING, VERIFY_OFF_CURVE, VERIFY_NOT_ORDER_R = range(5)
+VERIFY_MASK_A, VERIFY_MASK_B, VERIFY_MASK_C, VERIFY_MASK_INPUT = 0x10, 0x20, 0x40, 0x80
+
+
+def bw6_761_point_check(point, g2):
+    """Host code: 0, VERIFY_ENCODING, VERIFY_OFF_CURVE or VERIFY_NOT_ORDER_R for one point (24 limbs, x | y; all zero is the point at
+    infinity and passes).  g2: the point belongs on y^2 = x^3 + 4, else on y^2 = x^3 - 1."""
+    pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(24)
+    code = ctypes.c_int(-1)
+    _check(load().zkhip_bw6_761_point_check(_p(pt), 1 if g2 else 0, ctypes.byref(code)))
+    return code.value
+
+
+def groth16_verify_checked(vk, inputs, proof):
+    """groth16_verify behind the checks of the checked batch verifier, on the host: returns the proof's status byte (code in the low
+    nibble, mask of the failing elements in the high one), the byte Verifier.verify_batch_checked gives.  A key that fails the checks
+    raises (ZKHIP_ERR_ARG)."""
+    c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+    abc = c(vk["ABC"]).reshape(-1, 24)
+    inp = c(inputs).reshape(-1, 6)
+    assert abc.shape[0] == inp.shape[0] + 1
+    st = np.zeros(1, dtype=np.uint8)
+    _check(load().zkhip_groth16_verify_checked(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), _p(inp), inp.shape[0],
+                                               _p(c(proof)), st.ctypes.data))
+    return int(st[0])
+
+
 # the batch verifier's kernels (zecale_amd/csrc/pairing.cuh / pairing.hip): a verification owns eight lanes, so one wave holds
 # VERIFIER_GROUP of them and one 128-thread workgroup VERIFIER_WORKGROUP (tests size their batches around both)
 VERIFIER_GROUP = 8
@@ -685,14 +719,20 @@ VERIFIER_WORKGROUP = 16
 class Verifier:
     """Groth16 verification in batches on the GPU (zkhip_verifier): the pairing of groth16_verify as gfx950 kernels.  vk as for
     groth16_verify.  The handle owns its stream and work space on the calling thread's device; one batch in flight per handle,
-    several handles - one host thread each - run side by side.  Points must be on their curves and of order r (or infinity):
-    unlike groth16_verify this route checks nothing."""
+    several handles - one host thread each - run side by side.
+    verify_batch checks nothing: every coordinate and input must be fully reduced and every point on its curve and of order r (or
+    infinity), or its result is undefined - it is for proofs the caller made.  For anybody else's proofs make the handle with
+    checked=True: the key's points are validated on the device (a key that fails raises, the message names the element), and
+    verify_batch_checked validates encoding, curve and order of every proof point before the pairing and says per proof why it
+    was refused."""
 
-    def __init__(self, vk):
+    def __init__(self, vk, checked=False):
         c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
         abc = c(vk["ABC"]).reshape(-1, 24)
         self.handle = ctypes.c_void_p()
-        _check(load().zkhip_verifier_new(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), abc.shape[0] - 1, ctypes.byref(self.handle)))
+        self.checked = bool(checked)
+        new = load().zkhip_verifier_new_checked if checked else load().zkhip_verifier_new
+        _check(new(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), abc.shape[0] - 1, ctypes.byref(self.handle)))
         self.n_inputs = int(load().zkhip_verifier_num_inputs(self.handle))
 
     def verify_batch(self, inputs, proofs):
@@ -702,6 +742,16 @@ class Verifier:
         ok = np.zeros(pr.shape[0], dtype=np.uint8)
         _check(load().zkhip_verifier_verify_batch(self.handle, _p(inp), _p(pr), pr.shape[0], ok.ctypes.data))
         return ok.astype(bool)
+
+    def verify_batch_checked(self, inputs, proofs):
+        """As verify_batch on a handle made with checked=True, every proof point validated first.  Returns (codes, masks), uint8 arrays:
+        codes[i] is VERIFY_ACCEPT, VERIFY_REJECT, or the first of VERIFY_ENCODING, VERIFY_OFF_CURVE, VERIFY_NOT_ORDER_R that an element
+        of proof i has; masks[i] the elements that have it (VERIFY_MASK_A | _B | _C | _INPUT, zero for ACCEPT and REJECT)."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        st = np.zeros(pr.shape[0], dtype=np.uint8)
+        _check(load().zkhip_verifier_verify_batch_checked(self.handle, _p(inp), _p(pr), pr.shape[0], st.ctypes.data))
+        return st & np.uint8(0x0F), st & np.uint8(0xF0)
 
     def free(self):
         if self.handle:
