@@ -28,8 +28,7 @@ for f in aggregator witness_tape; do
   g++ -O2 -std=c++17 -fPIC -pthread -c $W/zecale_amd/csrc/$f.cpp -o $W/obj/$f.o &
 done
 wait
-objs=""
-for o in msm ntt qap zkhip_api witness pipeline multi_device; do objs="$objs $ROOT/build/$o.o"; done
+objs=$(ls $ROOT/build/*.o | grep -v -e '/aggregator\.o$' -e '/witness_tape\.o$')      # every object of the tree but the two rebuilt here
 hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $W/libzkhip.so $objs $W/obj/aggregator.o $W/obj/witness_tape.o
 cd $ROOT
 set +e

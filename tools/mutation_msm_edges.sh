@@ -46,7 +46,7 @@ EOF
 }
 
 if [ "$1" = build ]; then
-  for o in msm ntt qap zkhip_api witness aggregator witness_tape pipeline multi_device; do [ -f $ROOT/build/$o.o ]; done
+  [ -f $ROOT/build/msm.o ]
   rm -rf $W && mkdir -p $W
   for m in $MUTANTS; do
     mkdir -p $W/$m/include $W/$m/zecale_amd                  # (msm.h includes ../../include/zkhip.h)
@@ -54,7 +54,7 @@ if [ "$1" = build ]; then
     cp $ROOT/include/*.h* $W/$m/include/
     mutate $m $W/$m/zecale_amd/csrc
     ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -DZK_MUL_INLINE=1 -fPIC -c $W/$m/zecale_amd/csrc/msm.hip -o $W/$m/msm.o &&
-      objs="$W/$m/msm.o" && for o in ntt qap zkhip_api witness aggregator witness_tape pipeline multi_device; do objs="$objs $ROOT/build/$o.o"; done &&
+      objs="$W/$m/msm.o $(ls $ROOT/build/*.o | grep -v '/msm\.o$')" &&      # every object of the tree but the one rebuilt here
       hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $W/$m/libzkhip.so $objs && echo "built $m" ) &
   done
   wait

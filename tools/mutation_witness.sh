@@ -54,7 +54,7 @@ EOF
 
 if [ "$1" = build ]; then
   [ -n "$2" ] && MUTANTS="$2"
-  for o in msm ntt qap zkhip_api witness aggregator witness_tape pipeline multi_device; do [ -f $ROOT/build/$o.o ]; done
+  [ -f $ROOT/build/witness.o ]
   [ -n "$2" ] || rm -rf $W
   mkdir -p $W
   for m in $MUTANTS; do
@@ -63,7 +63,7 @@ if [ "$1" = build ]; then
     cp $ROOT/include/*.h* $W/$m/include/
     mutate $m $W/$m/zecale_amd/csrc
     ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -DZK_MUL_INLINE=1 -fPIC -c $W/$m/zecale_amd/csrc/witness.hip -o $W/$m/witness.o &&
-      objs="$W/$m/witness.o" && for o in msm ntt qap zkhip_api aggregator witness_tape pipeline multi_device; do objs="$objs $ROOT/build/$o.o"; done &&
+      objs="$W/$m/witness.o $(ls $ROOT/build/*.o | grep -v '/witness\.o$')" &&      # every object of the tree but the one rebuilt here
       hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $W/$m/libzkhip.so $objs && rm -rf $W/$m/zecale_amd $W/$m/include $W/$m/witness.o && echo "built $m" ) &
   done
   wait

@@ -6,10 +6,10 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 if [ "$1" = build ]; then
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -DZK_MUL_INLINE=1 -fPIC -DZK_SLOTS_AOS=0 -c $ROOT/zecale_amd/csrc/msm.hip -o $ROOT/build/msm_limb.o
-  objs=""
-  for o in ntt qap zkhip_api witness aggregator witness_tape pipeline multi_device; do objs="$objs $ROOT/build/$o.o"; done
-  hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $ROOT/build/libzkhip_limb.so $ROOT/build/msm_limb.o $objs
+  mkdir -p $ROOT/build/limb
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -DZK_MUL_INLINE=1 -fPIC -DZK_SLOTS_AOS=0 -c $ROOT/zecale_amd/csrc/msm.hip -o $ROOT/build/limb/msm.o
+  objs=$(ls $ROOT/build/*.o | grep -v '/msm\.o$')      # every object of the tree but the one rebuilt here (kept out of build/*.o)
+  hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $ROOT/build/libzkhip_limb.so $ROOT/build/limb/msm.o $objs
   ls -la $ROOT/build/libzkhip_limb.so
   exit 0
 fi

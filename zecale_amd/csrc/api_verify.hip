@@ -1,0 +1,175 @@
+// C ABI (include/zkhip.h): Groth16 verification - on the host, and in batches on the device (pairing.hip).
+#include <string.h>
+
+#include "api_internal.hpp"
+#include "ec.cuh"
+#include "pairing_host.hpp"
+#include "pairing.cuh"
+#include "pairing.h"
+
+using namespace zkhip::api;
+
+#pragma GCC visibility push(hidden)      // this file's own helpers and handle structs
+
+struct zkhip_verifier {
+  PairingCtx* ctx;
+  int device;
+};
+
+// ---- Groth16 verification in batches on the device (pairing.hip)
+static int verifier_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc, size_t n_inputs,
+                        bool checked, zkhip_verifier** out) {
+  if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called (the pairing kernels are the only batch verifier)");
+  BIND_CUR();
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  PairingCtx* ctx = nullptr;
+  const int rc = pairing_ctx_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, checked, &ctx, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  *out = new zkhip_verifier{ctx, cur_dev()};
+  return ZKHIP_OK;
+}
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                         const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_affine[72],
+                         int* ok) {
+  using namespace host;
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !proof_affine || !ok || (n_inputs && !inputs))
+    return fail(ZKHIP_ERR_ARG, "null pointer");
+  auto aff = [](const uint64_t* p) { return HJac::from_affine(HFq::from_limbs(p), HFq::from_limbs(p + 12)); };
+  // well-formedness first (libsnark: proof.is_well_formed()): G1 is y^2 = x^3 - 1, G2 is y^2 = x^3 + 4, both over Fq;
+  // the all-zero encoding of the point at infinity passes.  An off-curve point would put the pairing in an invalid-curve setting.
+  auto on_curve = [](const uint64_t* p, bool g2) {
+    HFq x = HFq::from_limbs(p), y = HFq::from_limbs(p + 12);
+    if (x.is_zero() && y.is_zero()) return true;
+    HFq four = HFq::one().dbl().dbl();
+    HFq rhs = x.sqr() * x + (g2 ? four : HFq::one().neg());
+    return y.sqr() == rhs;
+  };
+  bool wf = on_curve(proof_affine, false) && on_curve(proof_affine + 24, true) && on_curve(proof_affine + 48, false) &&
+            on_curve(vk_alpha_g1, false) && on_curve(vk_beta_g2, true) && on_curve(vk_delta_g2, true);
+  for (size_t i = 0; i <= n_inputs && wf; i++) wf = on_curve(vk_abc + i * 24, false);
+  if (!wf) { *ok = 0; return ZKHIP_OK; }
+  // acc = ABC_0 + sum x_i ABC_i
+  HJac acc = aff(vk_abc);
+  for (size_t i = 0; i < n_inputs; i++) {
+    uint64_t k[6];
+    HFr::from_limbs(inputs + i * 6).to_canonical(k);
+    acc = acc.add(aff(vk_abc + (i + 1) * 24).mul_canonical(k, 6));
+  }
+  uint64_t acc_aff[24], neg_g2[24], neg_beta[24], neg_delta[24];
+  HFq x, y;
+  acc.to_affine(x, y); x.to_limbs(acc_aff); y.to_limbs(acc_aff + 12);
+  auto neg_pt = [](const uint64_t* p, uint64_t* o) {
+    memcpy(o, p, 96);
+    HFq yy = HFq::from_limbs(p + 12);
+    bool inf = HFq::from_limbs(p).is_zero() && yy.is_zero();
+    (inf ? yy : yy.neg()).to_limbs(o + 12);
+  };
+  uint64_t g2[24];
+  memcpy(g2, FqParams::G2_GEN_X64, 96); memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
+  neg_pt(g2, neg_g2); neg_pt(vk_beta_g2, neg_beta); neg_pt(vk_delta_g2, neg_delta);
+  std::vector<const uint64_t*> p1 = {proof_affine, acc_aff, vk_alpha_g1, proof_affine + 48};
+  std::vector<const uint64_t*> p2 = {proof_affine + 24, neg_g2, neg_beta, neg_delta};
+  *ok = pairing_product_is_one(p1, p2) ? 1 : 0;
+  return ZKHIP_OK;
+}
+
+// ---- the checks of the checked verifier on the host (pairing_host.hpp point_check_host): no device
+int zkhip_bw6_761_point_check(const uint64_t p[24], int g2, int* code) {
+  if (!p || !code) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *code = host::point_check_host(p, g2 != 0);
+  return ZKHIP_OK;
+}
+
+int zkhip_groth16_verify_checked(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                 const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_affine[72],
+                                 uint8_t* status) {
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !proof_affine || !status || (n_inputs && !inputs))
+    return fail(ZKHIP_ERR_ARG, "null pointer");
+  const uint64_t* key[3] = {vk_alpha_g1, vk_beta_g2, vk_delta_g2};
+  for (size_t i = 0; i < n_inputs + 4; i++) {      // the order and the words of the device route's key check
+    const int code = host::point_check_host(i < 3 ? key[i] : vk_abc + (i - 3) * 24, i == 1 || i == 2);
+    if (!code) continue;
+    pairing_key_refusal(i, code, t_err, sizeof t_err);
+    return ZKHIP_ERR_ARG;
+  }
+  uint8_t e[4];
+  e[0] = (uint8_t)host::point_check_host(proof_affine, false);
+  e[1] = (uint8_t)host::point_check_host(proof_affine + 24, true);
+  e[2] = (uint8_t)host::point_check_host(proof_affine + 48, false);
+  e[3] = ZKHIP_VERIFY_ACCEPT;
+  for (size_t i = 0; i < n_inputs; i++) if (host::HFr::geq_p(inputs + i * 6)) e[3] = ZKHIP_VERIFY_ENCODING;
+  if ((*status = verify_refusal(e)) != 0) return ZKHIP_OK;
+  int ok = 0;
+  const int rc = zkhip_groth16_verify(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, inputs, n_inputs, proof_affine, &ok);
+  if (rc != ZKHIP_OK) return rc;
+  *status = ok ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT;
+  return ZKHIP_OK;
+}
+
+int zkhip_verifier_new(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                       size_t n_inputs, zkhip_verifier** out) {
+  return verifier_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, false, out);
+}
+int zkhip_verifier_new_checked(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                               size_t n_inputs, zkhip_verifier** out) {
+  return verifier_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, true, out);
+}
+size_t zkhip_verifier_num_inputs(const zkhip_verifier* v) { return v ? pairing_ctx_num_inputs(v->ctx) : 0; }
+int zkhip_verifier_verify_batch(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* ok) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (count == 0) return ZKHIP_OK;
+  if (!proofs_affine || !ok || (pairing_ctx_num_inputs(v->ctx) && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  BIND(v);
+  return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, false, ok, t_err, sizeof t_err);
+}
+int zkhip_verifier_verify_batch_checked(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, uint8_t* status) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (!pairing_ctx_checked(v->ctx)) return fail(ZKHIP_ERR_STATE, "checked batches need a handle of zkhip_verifier_new_checked");
+  if (count == 0) return ZKHIP_OK;
+  if (!proofs_affine || !status || (pairing_ctx_num_inputs(v->ctx) && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  BIND(v);
+  return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, true, status, t_err, sizeof t_err);
+}
+void zkhip_verifier_free(zkhip_verifier* v) {
+  if (!v) return;
+  if (bind_dev(v->device) == ZKHIP_OK) pairing_ctx_free(v->ctx);
+  delete v;
+}
+
+int zkhip_internal_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  BIND_CUR();
+  if (op < 0 || op > 2 || (n && (!a || !b || !out)) || n > (1u << 20)) return fail(ZKHIP_ERR_ARG, "op 0 (mul), 1 (sqr) or 2 (mul_line), at most 2^20 sets");
+  if (n == 0) return ZKHIP_OK;
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return pairing_fq6_selftest(op, a, b, n, out, t_err, sizeof t_err);
+}
+
+int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out) {
+  if ((route != 0 && route != 1) || pairs_per_product < 1 || pairs_per_product > 4) return fail(ZKHIP_ERR_ARG, "route 0 (host) or 1 (GPU), 1 .. 4 pairs per product");
+  if (count && (!g1 || !g2 || !out)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (count == 0) return ZKHIP_OK;
+  if (route == 0) {
+    for (size_t i = 0; i < count; i++) {
+      std::vector<const uint64_t*> p1, p2;
+      for (size_t p = 0; p < pairs_per_product; p++) { p1.push_back(g1 + (i * pairs_per_product + p) * 24); p2.push_back(g2 + (i * pairs_per_product + p) * 24); }
+      const host::Fq6 v = host::pairing_product_value(p1, p2);
+      for (int k = 0; k < 6; k++) v.c[k].to_limbs(out + i * 72 + k * 12);
+    }
+    return ZKHIP_OK;
+  }
+  if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called");
+  BIND_CUR();
+  PairingCtx* ctx = nullptr;
+  int rc = pairing_ctx_new(nullptr, nullptr, nullptr, nullptr, 0, false, &ctx, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  rc = pairing_products(ctx, g1, g2, (int)pairs_per_product, count, out, t_err, sizeof t_err);
+  pairing_ctx_free(ctx);
+  return rc;
+}
+
+}  // extern "C"
