@@ -392,6 +392,32 @@ int zkhip_bls12_377_groth16_verify(const uint64_t vk_alpha_g1[12], const uint64_
                                    const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs,
                                    const uint64_t proof_a[12], const uint64_t proof_b[24], const uint64_t proof_c[12], int* ok);
 
+/* ---- nested (BLS12-377) Groth16 verification in batches on the device ----------------------------- */
+/* stands beside: nsnark::verify (libzecale/tests/circuits/dummy_application_test.cpp:32-44), one proof per call on the host in the
+ * reference and in zkhip_bls12_377_groth16_verify above; the reference has no batched counterpart.  The optimal-ate pairing of that
+ * function as gfx950 kernels (csrc/pairing_bls.cuh / pairing_bls.hip): sixteen lanes per verification, the lines of the key's -beta,
+ * -delta and of the negated generator and the doubling chains 2^j ABC_i prepared once per handle on the host.
+ * nested_vk, nested_proofs and nested_inputs are laid out as above; inputs_per_proof 0 .. 16.
+ * PRECONDITION: every coordinate and input is FULLY REDUCED (below the modulus of Fr of BW6-761); the device does not look.
+ * zkhip_nested_verifier_new checks the key on the HOST before it touches a device: a point off its curve, or a key whose own
+ * chains meet a degenerate chord-and-tangent step (an ABC_i, i >= 1, with a multiple 2^j ABC_i of y = 0 - (-1, 0) for one; a zero
+ * slope denominator in the line schedule of beta, delta) is refused with ZKHIP_ERR_ARG, zkhip_last_error() naming the element.
+ * ok[i] equals the *ok of zkhip_bls12_377_groth16_verify on the same key, inputs and proof: A, B, C are checked against their curves on
+ * the device (off the curve, all-zero included: 0), and a proof for which a step of the host's affine arithmetic is degenerate (the input
+ * accumulator meets +-2^j ABC_i at step j of input i, whether bit j is set or clear - the host forms that sum at every bit and
+ * selects afterwards; a zero among the 69 slope denominators of B) is not decided on the device but handed to that host function
+ * inside the call; zkhip_nested_verifier_last_fallbacks says how many of the last batch went that way.
+ * Threads: as zkhip_verifier - the handle owns its stream and work space on the calling thread's library device, one batch in
+ * flight per handle, handles run beside each other and beside provers.  There is no CPU fallback for a batch as a whole:
+ * ZKHIP_ERR_NO_DEVICE / ZKHIP_ERR_STATE without an initialised device.  count == 0 returns ZKHIP_OK. */
+typedef struct zkhip_nested_verifier zkhip_nested_verifier;
+int zkhip_nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof, zkhip_nested_verifier** out);
+size_t zkhip_nested_verifier_num_inputs(const zkhip_nested_verifier* v);
+int zkhip_nested_verifier_verify_batch(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
+                                       uint8_t* ok);
+int zkhip_nested_verifier_last_fallbacks(const zkhip_nested_verifier* v, size_t* out);
+void zkhip_nested_verifier_free(zkhip_nested_verifier* v);
+
 /* replaces: libzecale::aggregator_circuit<wppT, wsnarkT, nverifierT, NumProofs>(inputs_per_nested_proof)
  * (libzecale/circuits/aggregator_circuit.hpp:32-114; constructor .tcc:17-98): builds the constraint system.
  * num_proofs 1 .. 32 (one result bit per nested proof, packed into one primary input), inputs_per_proof 1 .. 16; anything else:
@@ -621,6 +647,16 @@ int zkhip_internal_last_acc_path(int* out);
  * zkhip_groth16_verify (needs no device); route 1: the kernels of zkhip_verifier_verify_batch. */
 int zkhip_internal_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
 int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out);
+/* Test hooks of the nested pairing kernels (no counterpart).
+ * fq12_selftest: n independent operand sets through the per-lane bodies of pairing_bls.cuh inside a real kernel, sixteen lanes per
+ * set: op 0 = a b, 1 = a^2, 2 = a (b_0 + b_1 w + b_3 w^3 + b_7 w^7 + b_9 w^9) (the sparse line product; b's other coefficients are
+ * ignored) in Fq12 = Fq[w]/(w^12 + 5) over the nested base field.  a, b, out: n x 12 coefficients x 6 ABI limbs.
+ * nested_pairing_product: out[i] = prod_{p < pairs_per_product} e(g1[i][p], g2[i][p]), the REDUCED value f^(3 (q^12 - 1) / r)
+ * (12 x 6 ABI limbs, canonical); g1: 12 limbs per point, g2: 24; pairs_per_product in 1 .. 4.  route 0: the host code
+ * (multi_miller_loop and final_exponentiation of csrc/circuit/bls12_377.hpp, needs no device); route 1: the kernels of
+ * zkhip_nested_verifier_verify_batch.  A point off its curve: ZKHIP_ERR_ARG on both routes. */
+int zkhip_internal_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+int zkhip_internal_nested_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out);
 /* Test hook (no counterpart), HOST ONLY - works without a device: the prover's tail (row a9) on the paths a healthy proof never
  * takes: `rounds` proofs abandoned between the start of the tail's key-only scalar multiplications and their collection, the key's
  * tables freed at once (run under the CPU AddressSanitizer build); a delta of small order (`small_order_g1`, e.g. (1, 0)) whose

@@ -1,0 +1,175 @@
+// C ABI (include/zkhip.h): nested (BLS12-377) Groth16 verification in batches on the device (pairing_bls.hip).  The host side of a
+// handle lives here: what it derives from its key (nested_key.hpp: the curve checks, the lines of -beta, -delta and the negated
+// generator, the doubling chains 2^j ABC_i), the host route of the test hook and the fallback of proofs the device does not decide.
+#include <string.h>
+#include <stdexcept>
+#include <string>
+
+#include "api_internal.hpp"
+#include "circuit/sections.hpp"
+#include "nested_key.hpp"
+#include "pairing_bls.h"
+
+using namespace zkhip::api;
+namespace C = zkhip::circuit;
+
+#pragma GCC visibility push(hidden)      // this file's own helpers and handle structs
+
+struct zkhip_nested_verifier {
+  NestedCtx* ctx;
+  int device;
+  size_t n_inputs;
+  std::vector<uint64_t> vk;              // the key as given: the fallback verifies under it
+  size_t last_fallbacks;
+  std::vector<uint8_t> status;
+};
+
+namespace {
+
+using C::HFr;
+using C::NF;
+
+using zkhip::nested_key::g1_on_curve;
+using zkhip::nested_key::g2_on_curve;
+using zkhip::nested_key::put;
+using zkhip::nested_key::PreparedKey;
+
+// the constants every context needs: the Frobenius scalings and the twist's -1/5
+struct NestedConsts {
+  std::vector<uint64_t> frob, fifth_neg;
+  NestedConsts() {
+    for (int i = 0; i < 12; i++) put(frob, C::fq12_consts().frob[i]);
+    put(fifth_neg, C::small_consts().fifth_neg);
+  }
+};
+const NestedConsts& nested_consts() { static NestedConsts c; return c; }
+
+NestedKeyData consts_only() {
+  NestedKeyData kd = {};
+  kd.frob = nested_consts().frob.data();
+  kd.fifth_neg = nested_consts().fifth_neg.data();
+  return kd;
+}
+
+}  // namespace
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int zkhip_nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof, zkhip_nested_verifier** out) {
+  if (!nested_vk || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (inputs_per_proof > 16) return fail(ZKHIP_ERR_ARG, "inputs_per_proof 0 .. 16");
+  PreparedKey pk;
+  try {
+    std::string why;                                                    // on the host, before a device is touched
+    if (!zkhip::nested_key::prepare_key(nested_vk, inputs_per_proof, &pk, &why)) return fail(ZKHIP_ERR_ARG, why.c_str());
+  } catch (const std::exception& e) {
+    return fail(ZKHIP_ERR_STATE, e.what());
+  }
+  if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called (the nested pairing kernels are the only batch verifier)");
+  BIND_CUR();
+  NestedKeyData kd = consts_only();
+  kd.alpha = nested_vk;
+  kd.abc0 = nested_vk + 60;
+  kd.lines = pk.lines.data();
+  kd.chain = pk.chain.data();
+  kd.n_inputs = inputs_per_proof;
+  NestedCtx* ctx = nullptr;
+  const int rc = nested_ctx_new(&kd, &ctx, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  zkhip_nested_verifier* v = new zkhip_nested_verifier{ctx, cur_dev(), inputs_per_proof, {}, 0, {}};
+  v->vk.assign(nested_vk, nested_vk + 60 + 12 * (inputs_per_proof + 1));
+  *out = v;
+  return ZKHIP_OK;
+}
+
+size_t zkhip_nested_verifier_num_inputs(const zkhip_nested_verifier* v) { return v ? v->n_inputs : 0; }
+
+int zkhip_nested_verifier_verify_batch(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
+                                       uint8_t* ok) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  v->last_fallbacks = 0;
+  if (count == 0) return ZKHIP_OK;
+  if (!nested_proofs || !ok || (v->n_inputs && !nested_inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  BIND(v);
+  v->status.resize(count);
+  const int rc = nested_verify_batch(v->ctx, nested_inputs, nested_proofs, count, ok, v->status.data(), t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  // what the device marked degenerate is decided by the host's verifier
+  const uint64_t* vk = v->vk.data();
+  size_t fallbacks = 0;
+  for (size_t i = 0; i < count; i++) {
+    if (!(v->status[i] & NESTED_DEGENERATE)) continue;
+    fallbacks++;
+    const uint64_t* pr = nested_proofs + i * 48;
+    int one = 0;
+    const int rc2 = zkhip_bls12_377_groth16_verify(vk, vk + 12, vk + 36, vk + 60, v->n_inputs ? nested_inputs + i * v->n_inputs * 6 : nullptr, v->n_inputs,
+                                                   pr, pr + 12, pr + 36, &one);
+    if (rc2 != ZKHIP_OK) return fail(rc2, "the host verifier refused a proof the device handed back");
+    ok[i] = one ? 1 : 0;
+  }
+  v->last_fallbacks = fallbacks;
+  return ZKHIP_OK;
+}
+
+int zkhip_nested_verifier_last_fallbacks(const zkhip_nested_verifier* v, size_t* out) {
+  if (!v || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *out = v->last_fallbacks;
+  return ZKHIP_OK;
+}
+
+void zkhip_nested_verifier_free(zkhip_nested_verifier* v) {
+  if (!v) return;
+  if (bind_dev(v->device) == ZKHIP_OK) nested_ctx_free(v->ctx);
+  delete v;
+}
+
+int zkhip_internal_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  BIND_CUR();
+  if (op < 0 || op > 2 || (n && (!a || !b || !out)) || n > (1u << 20)) return fail(ZKHIP_ERR_ARG, "op 0 (mul), 1 (sqr) or 2 (mul_line), at most 2^20 sets");
+  if (n == 0) return ZKHIP_OK;
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return nested_fq12_selftest(op, a, b, n, out, t_err, sizeof t_err);
+}
+
+int zkhip_internal_nested_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out) {
+  if ((route != 0 && route != 1) || pairs_per_product < 1 || pairs_per_product > 4) return fail(ZKHIP_ERR_ARG, "route 0 (host) or 1 (GPU), 1 .. 4 pairs per product");
+  if (count && (!g1 || !g2 || !out)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (count == 0) return ZKHIP_OK;
+  const size_t np = pairs_per_product;
+  try {
+    for (size_t i = 0; i < count * np; i++)
+      if (!g1_on_curve(C::g1_from<NF>(g1 + i * 12, false)) || !g2_on_curve(C::g2_from<NF>(g2 + i * 24, false)))
+        return fail(ZKHIP_ERR_ARG, "a point is off its curve");
+    if (route == 0) {
+      for (size_t i = 0; i < count; i++) {
+        std::vector<C::G2<NF>> Qs;
+        for (size_t p = 0; p < np; p++) Qs.push_back(C::g2_from<NF>(g2 + (i * np + p) * 24, false));
+        const std::vector<C::G2Lines<NF>> lines = C::g2_precompute<NF>(Qs);
+        std::vector<C::MillerPair<NF>> ps;
+        for (size_t p = 0; p < np; p++) ps.push_back({&lines[p], C::g1_from<NF>(g1 + (i * np + p) * 12, false)});
+        const C::Fq12<NF> v = C::final_exponentiation(C::multi_miller_loop(ps));
+        for (int k = 0; k < 12; k++) v.c[k].v.to_limbs(out + i * 72 + k * 6);
+      }
+      return ZKHIP_OK;
+    }
+  } catch (const std::exception& e) {
+    return fail(ZKHIP_ERR_STATE, e.what());
+  }
+  if (cur_dev() < 0) return fail(ZKHIP_ERR_NO_DEVICE, "zkhip_init not called");
+  BIND_CUR();
+  const NestedKeyData kd = consts_only();
+  NestedCtx* ctx = nullptr;
+  int rc = nested_ctx_new(&kd, &ctx, t_err, sizeof t_err);
+  if (rc != ZKHIP_OK) return rc;
+  std::vector<uint8_t> status(count);
+  rc = nested_products(ctx, g1, g2, (int)np, count, out, status.data(), t_err, sizeof t_err);
+  nested_ctx_free(ctx);
+  if (rc != ZKHIP_OK) return rc;
+  for (size_t i = 0; i < count; i++)
+    if (status[i]) return fail(ZKHIP_ERR_STATE, "the line schedule of a G2 point is degenerate (a slope denominator is zero)");
+  return ZKHIP_OK;
+}
+
+}  // extern "C"

@@ -405,6 +405,7 @@ template <class F> inline std::vector<std::vector<std::array<HFr, 2>>> accumulat
     for (size_t i = 0; i < where.size(); i++) zs[where[i]] = var[i];
   }
 #else
+  if (zs.empty()) return out;                                    // a key without inputs: nothing to invert (the tree needs one element)
   for (const HFr& zv : zs) if (zv.is_zero()) return {};          // a degenerate step: the caller keeps the affine chain
   batch_inv_tree(zs);
 #endif

@@ -1,0 +1,368 @@
+// Nested (BLS12-377) Groth16 verification in batches on the device: the optimal-ate pairing of circuit/bls12_377.hpp (the reference's
+// nsnark::verify, libzecale/tests/circuits/dummy_application_test.cpp:32-44) as kernels over the lane bodies of pairing_bls.cuh.
+//
+// A verification owns a GROUP of sixteen lanes (pairing_bls.cuh explains the cut); a workgroup of 128 threads holds 8 of them, a wave 4.
+// The group's state lives in LDS: the accumulator twice (an operation reads one copy and writes the other, so ONE barrier separates
+// two operations) and the lines of the four pairs; the final exponentiation keeps eight Fq12 registers there.  Every loop has a fixed
+// trip count (the 63 bits of u, the program's length); the only synchronisation is the workgroup barrier, which every thread of a
+// workgroup reaches the same number of times: groups past the end of the batch recompute the last verification and store nothing.
+// No waits, no spins, no atomics.
+//
+// In front run the one-lane-per-proof kernels without LDS or barriers: k_nested_prep (curve checks of A, B, C - a lane leaves at its
+// first failure - and the 69 lines of B) and k_nested_acc (acc = ABC_0 + sum x_i ABC_i along the host's chain).  They write one status
+// byte each per proof; a proof with a status continues on stand-in values and the host ignores its product.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+
+#include "pairing_bls.cuh"
+#include "pairing_bls.h"
+
+namespace zkhip {
+
+constexpr int NESTED_BLOCK = 128;
+constexpr int NESTED_WG = NESTED_BLOCK / NESTED_GROUP;      // verifications per workgroup
+constexpr size_t NESTED_CHUNK = 8192;                       // verifications per launch sequence (bounds the work space: 15.5 KB of lines each)
+
+// where the pairs of a product find their G1 point (x, y in device form) and their lines: base + slot * stride (strides in elements;
+// zero for what the key shares among all proofs)
+struct NestedMillerArgs {
+  const Fr* g1[NESTED_MAX_PAIRS];
+  size_t g1_stride[NESTED_MAX_PAIRS];
+  const NestedLine* lines[NESTED_MAX_PAIRS];
+  size_t line_stride[NESTED_MAX_PAIRS];
+  const NestedLine* standin;            // pair 0's lines for a slot whose own were never written (status NESTED_OFF_CURVE), or null
+  const uint8_t* status;
+};
+
+// ---- ABI limbs -> device form, one lane per element (keys, constants, the G1 points of a product)
+__global__ void __launch_bounds__(64) k_nested_from_abi(const uint64_t* __restrict__ in, size_t n, Fr* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = fp_from_abi<FrParams>(in + i * 6);
+}
+
+// ---- the lines of one G2 point per lane (products); status: NESTED_DEGENERATE when a denominator of its schedule is zero
+__global__ void __launch_bounds__(64) k_nested_g2_lines(const uint64_t* __restrict__ g2, size_t n, NestedLine* __restrict__ lines,
+                                                        uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t* q = g2 + i * 24;
+  const Fr2 qx{fp_from_abi<FrParams>(q), fp_from_abi<FrParams>(q + 6)}, qy{fp_from_abi<FrParams>(q + 12), fp_from_abi<FrParams>(q + 18)};
+  status[i] = g2_lines_lane(qx, qy, lines + i * NESTED_LINES) ? 0 : NESTED_DEGENERATE;
+}
+
+// ---- one lane per proof (a | b | c, 48 ABI limbs): A and C to device form (slots 0 and 2 of the proof's three G1 points), the curve
+// checks, the lines of B.  consts[12] is -1/5.
+__global__ void __launch_bounds__(64) k_nested_prep(const uint64_t* __restrict__ proofs, size_t count, const Fr* __restrict__ consts,
+                                                    Fr* __restrict__ g1 /* count x 3 x 2 */, NestedLine* __restrict__ lines,
+                                                    uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const uint64_t* pr = proofs + i * 48;
+  const Fr ax = fp_from_abi<FrParams>(pr), ay = fp_from_abi<FrParams>(pr + 6);
+  const Fr cx = fp_from_abi<FrParams>(pr + 36), cy = fp_from_abi<FrParams>(pr + 42);
+  g1[i * 6 + 0] = ax; g1[i * 6 + 1] = ay;
+  g1[i * 6 + 4] = cx; g1[i * 6 + 5] = cy;
+  if (!nested_g1_on_curve(ax, ay)) { status[i] = NESTED_OFF_CURVE; return; }
+  const Fr2 bx{fp_from_abi<FrParams>(pr + 12), fp_from_abi<FrParams>(pr + 18)}, by{fp_from_abi<FrParams>(pr + 24), fp_from_abi<FrParams>(pr + 30)};
+  if (!nested_g2_on_curve(bx, by, consts[12])) { status[i] = NESTED_OFF_CURVE; return; }
+  if (!nested_g1_on_curve(cx, cy)) { status[i] = NESTED_OFF_CURVE; return; }
+  status[i] = g2_lines_lane(bx, by, lines + i * NESTED_LINES) ? 0 : NESTED_DEGENERATE;
+}
+
+// ---- one lane per proof: the input accumulator into slot 1 of the proof's G1 points; its own status byte
+__global__ void __launch_bounds__(64) k_nested_acc(const uint64_t* __restrict__ inputs, size_t n_inputs, size_t count, const Fr* __restrict__ abc0,
+                                                   const Fr* __restrict__ chain, Fr* __restrict__ g1, uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  Fr out[2];
+  const bool fine = nested_acc_lane(abc0, chain, inputs + i * n_inputs * 6, n_inputs, out);
+  g1[i * 6 + 2] = out[0]; g1[i * 6 + 3] = out[1];
+  status[i] = fine ? 0 : NESTED_DEGENERATE;
+}
+
+// ---- f = prod_p f_{u,Q_p}(P_p): multi_miller_loop over precomputed lines, `np` pairs per product
+__global__ void __launch_bounds__(NESTED_BLOCK) k_nested_miller(NestedMillerArgs args, int np, size_t count, Fr* __restrict__ f_out) {
+  __shared__ Fr sF[NESTED_WG][2][12];
+  __shared__ Fr sL[NESTED_WG][NESTED_MAX_PAIRS][5];
+  const int g = threadIdx.x / NESTED_GROUP, k = threadIdx.x % NESTED_GROUP;
+  size_t slot = (size_t)blockIdx.x * NESTED_WG + g;
+  const bool live = slot < count;
+  if (!live) slot = count - 1;
+  const int p = k - 12;                                     // lanes 12 .. 15 prepare the lines of pair p
+  const bool ln = p >= 0 && p < np;
+  const NestedLine* lines = nullptr;
+  Fr px = fp_zero<FrParams>(), py = fp_zero<FrParams>();
+  if (ln) {
+    lines = args.lines[p] + slot * args.line_stride[p];
+    if (p == 0 && args.standin && (args.status[slot] & NESTED_OFF_CURVE)) lines = args.standin;
+    const Fr* pt = args.g1[p] + slot * args.g1_stride[p];
+    px = pt[0]; py = pt[1];
+  }
+  if (k < 12) sF[g][0][k] = k == 0 ? fp_one<FrParams>() : fp_zero<FrParams>();
+  __syncthreads();
+  int cur = 0, at = 0;
+#pragma unroll 1
+  for (int i = 62; i >= 0; i--) {
+#pragma unroll 1
+    for (int add = 0; add < 2; add++) {
+      if (add && !((NESTED_U >> i) & 1)) break;             // the same bit for every thread
+      // the accumulator's squaring on the coefficient lanes and the pairs' lines on lanes 12 .. 15 touch disjoint state
+      if (!add && k < 12) sF[g][cur ^ 1][k] = fq12_mul_coeff(k, sF[g][cur], sF[g][cur]);
+      if (ln) nested_line_at(lines[at], px, py, sL[g][p]);
+      __syncthreads();
+      if (!add) cur ^= 1;
+#pragma unroll 1
+      for (int q = 0; q < np; q++) {                        // f <- f * line_q: read copy `cur`, write the other, barrier
+        if (k < 12) sF[g][cur ^ 1][k] = fq12_mul_line_coeff(k, sF[g][cur], sL[g][q]);
+        __syncthreads();
+        cur ^= 1;
+      }
+      at++;
+    }
+  }
+  if (live && k < 12) f_out[slot * 12 + k] = sF[g][cur][k];
+}
+
+// ---- f^(3 (q^12 - 1) / r): the program of pairing_bls.cuh over eight Fq12 registers in LDS, then ABI limbs
+__global__ void __launch_bounds__(NESTED_BLOCK) k_nested_final_exp(const Fr* __restrict__ f_in, const Fq12Op* __restrict__ prog, int n_ops,
+                                                                   const Fr* __restrict__ frob, size_t count, uint64_t* __restrict__ gt) {
+  __shared__ Fr sR[NESTED_WG][FQ12_REGS][12];
+  const int g = threadIdx.x / NESTED_GROUP, k = threadIdx.x % NESTED_GROUP;
+  size_t slot = (size_t)blockIdx.x * NESTED_WG + g;
+  const bool live = slot < count;
+  if (!live) slot = count - 1;
+  if (k < 12) sR[g][0][k] = f_in[slot * 12 + k];
+  __syncthreads();
+#pragma unroll 1
+  for (int i = 0; i < n_ops; i++) {
+    const Fq12Op o = prog[i];                               // the same operation for every thread
+    if (k < 12) fq12_op_lane(o, k, sR[g], frob);
+    __syncthreads();
+  }
+  if (live && k < 12) fp_to_abi<FrParams>(sR[g][0][k], gt + slot * 72 + k * 6);       // [8] -> canonical
+}
+
+// ---- the lane bodies on operands given as ABI limbs (zkhip_internal_fq12_selftest)
+__global__ void __launch_bounds__(NESTED_BLOCK) k_fq12_selftest(int op, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, size_t n,
+                                                                uint64_t* __restrict__ out) {
+  __shared__ Fr sA[NESTED_WG][12];
+  __shared__ Fr sB[NESTED_WG][12];
+  __shared__ Fr sL[NESTED_WG][5];
+  const int g = threadIdx.x / NESTED_GROUP, k = threadIdx.x % NESTED_GROUP;
+  size_t slot = (size_t)blockIdx.x * NESTED_WG + g;
+  const bool live = slot < n;
+  if (!live) slot = n - 1;
+  if (k < 12) {
+    sA[g][k] = fp_from_abi<FrParams>(a + slot * 72 + k * 6);
+    sB[g][k] = fp_from_abi<FrParams>(b + slot * 72 + k * 6);
+    const int li = k == 0 ? 0 : k == 1 ? 1 : k == 3 ? 2 : k == 7 ? 3 : k == 9 ? 4 : -1;
+    if (li >= 0) sL[g][li] = sB[g][k];
+  }
+  __syncthreads();
+  if (live && k < 12) {
+    const Fr r = op == 0 ? fq12_mul_coeff(k, sA[g], sB[g]) : op == 1 ? fq12_mul_coeff(k, sA[g], sA[g]) : fq12_mul_line_coeff(k, sA[g], sL[g]);
+    fp_to_abi<FrParams>(r, out + slot * 72 + k * 6);
+  }
+}
+
+#define NEST_HIP(x)                                                                                   \
+  do {                                                                                                \
+    hipError_t e_ = (x);                                                                              \
+    if (e_ != hipSuccess) {                                                                           \
+      if (errbuf) snprintf(errbuf, errlen, "nested pairing: %s: %s", #x, hipGetErrorString(e_));      \
+      return ZKHIP_ERR_HIP;                                                                           \
+    }                                                                                                 \
+  } while (0)
+
+namespace {
+unsigned blocks_for(size_t n, size_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+}  // namespace
+
+// the constants and the key on the device, in elements of d_fr
+constexpr size_t NK_FROB = 0, NK_FIFTH = 12, NK_ALPHA = 13, NK_ABC0 = 15, NK_LINES = 17, NK_CHAIN = NK_LINES + 3 * NESTED_LINES * 4;
+
+struct NestedCtx {
+  hipStream_t st = nullptr;
+  Fr* d_fr = nullptr;               // constants, then the key (NK_*)
+  Fq12Op* d_prog = nullptr;
+  int n_ops = 0;
+  bool has_key = false;
+  size_t n_inputs = 0;
+  size_t cap = 0;                   // products (of four pairs) the work space holds
+  uint64_t *d_in1 = nullptr, *d_in2 = nullptr, *d_gt = nullptr;     // staged ABI limbs: proofs or G1 points / inputs or G2 points; GT values
+  Fr *d_g1 = nullptr, *d_f = nullptr;
+  NestedLine* d_lines = nullptr;
+  uint8_t* d_status = nullptr;      // cap x 4: per proof of a chunk of m at [0, m) and [m, 2 m) (prep, accumulator); per G2 point (products)
+  std::vector<uint64_t> h_gt;
+  std::vector<uint8_t> h_status;
+};
+
+static void nctx_release_work(NestedCtx* c) {
+  for (void* p : {(void*)c->d_in1, (void*)c->d_in2, (void*)c->d_gt, (void*)c->d_g1, (void*)c->d_f, (void*)c->d_lines, (void*)c->d_status}) if (p) (void)hipFree(p);
+  c->d_in1 = c->d_in2 = c->d_gt = nullptr; c->d_g1 = c->d_f = nullptr; c->d_lines = nullptr; c->d_status = nullptr; c->cap = 0;
+}
+
+// work space for `count` products of four pairs (a proof is one): 4 G2 points of 24 limbs or a proof's 48; 16 inputs of 6 limbs at most
+static int nctx_reserve(NestedCtx* c, size_t count, char* errbuf, size_t errlen) {
+  if (count <= c->cap) return ZKHIP_OK;
+  nctx_release_work(c);
+  NEST_HIP(hipMalloc(&c->d_in1, count * 48 * 8));
+  NEST_HIP(hipMalloc(&c->d_in2, count * 96 * 8));
+  NEST_HIP(hipMalloc(&c->d_gt, count * 72 * 8));
+  NEST_HIP(hipMalloc(&c->d_g1, count * 8 * sizeof(Fr)));
+  NEST_HIP(hipMalloc(&c->d_f, count * 12 * sizeof(Fr)));
+  NEST_HIP(hipMalloc(&c->d_lines, count * 4 * NESTED_LINES * sizeof(NestedLine)));
+  NEST_HIP(hipMalloc(&c->d_status, count * 4));
+  c->cap = count;
+  return ZKHIP_OK;
+}
+
+void nested_ctx_free(NestedCtx* c) {
+  if (!c) return;
+  nctx_release_work(c);
+  for (void* p : {(void*)c->d_fr, (void*)c->d_prog}) if (p) (void)hipFree(p);
+  if (c->st) (void)hipStreamDestroy(c->st);
+  delete c;
+}
+
+size_t nested_ctx_num_inputs(const NestedCtx* c) { return c ? c->n_inputs : 0; }
+
+static int nctx_init(NestedCtx* c, const NestedKeyData* key, char* errbuf, size_t errlen) {
+  NEST_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  const bool has_key = key->alpha != nullptr;
+  const size_t n = has_key ? NK_CHAIN + key->n_inputs * NESTED_INPUT_BITS_DEV * 2 : NK_ALPHA;
+  std::vector<uint64_t> abi(n * 6);
+  memcpy(&abi[NK_FROB * 6], key->frob, 12 * 48);
+  memcpy(&abi[NK_FIFTH * 6], key->fifth_neg, 48);
+  if (has_key) {
+    memcpy(&abi[NK_ALPHA * 6], key->alpha, 96);
+    memcpy(&abi[NK_ABC0 * 6], key->abc0, 96);
+    memcpy(&abi[NK_LINES * 6], key->lines, (size_t)3 * NESTED_LINES * 4 * 48);
+    if (key->n_inputs) memcpy(&abi[NK_CHAIN * 6], key->chain, key->n_inputs * NESTED_INPUT_BITS_DEV * 2 * 48);
+  }
+  const std::vector<Fq12Op> prog = fq12_final_exp_program();
+  c->n_ops = (int)prog.size();
+  uint64_t* d_abi = nullptr;
+  NEST_HIP(hipMalloc(&c->d_fr, n * sizeof(Fr)));
+  NEST_HIP(hipMalloc(&c->d_prog, prog.size() * sizeof(Fq12Op)));
+  NEST_HIP(hipMalloc(&d_abi, n * 48));
+  hipError_t e = hipMemcpyAsync(d_abi, abi.data(), n * 48, hipMemcpyHostToDevice, c->st);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->d_prog, prog.data(), prog.size() * sizeof(Fq12Op), hipMemcpyHostToDevice, c->st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_nested_from_abi, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, d_abi, n, c->d_fr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->st);       // (abi and prog are read by the copies until here)
+  (void)hipFree(d_abi);
+  NEST_HIP(e);
+  c->has_key = has_key;
+  c->n_inputs = has_key ? key->n_inputs : 0;
+  return ZKHIP_OK;
+}
+
+int nested_ctx_new(const NestedKeyData* key, NestedCtx** out, char* errbuf, size_t errlen) {
+  NestedCtx* c = new NestedCtx();
+  const int rc = nctx_init(c, key, errbuf, errlen);
+  if (rc != ZKHIP_OK) { nested_ctx_free(c); return rc; }
+  *out = c;
+  return ZKHIP_OK;
+}
+
+// Miller loop and final exponentiation of `count` products, GT values and `n_status` status bytes to the host
+static int nested_run(NestedCtx* c, const NestedMillerArgs& args, int pairs, size_t count, uint64_t* out, size_t n_status, char* errbuf, size_t errlen) {
+  hipLaunchKernelGGL(k_nested_miller, dim3(blocks_for(count, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, args, pairs, count, c->d_f);
+  hipLaunchKernelGGL(k_nested_final_exp, dim3(blocks_for(count, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, c->d_f, c->d_prog, c->n_ops,
+                     c->d_fr + NK_FROB, count, c->d_gt);
+  NEST_HIP(hipGetLastError());
+  c->h_status.resize(n_status);
+  NEST_HIP(hipMemcpyAsync(out, c->d_gt, count * 72 * 8, hipMemcpyDeviceToHost, c->st));
+  NEST_HIP(hipMemcpyAsync(c->h_status.data(), c->d_status, n_status, hipMemcpyDeviceToHost, c->st));
+  NEST_HIP(hipStreamSynchronize(c->st));
+  return ZKHIP_OK;
+}
+
+int nested_products(NestedCtx* c, const uint64_t* g1, const uint64_t* g2, int pairs, size_t count, uint64_t* out, uint8_t* status, char* errbuf,
+                    size_t errlen) {
+  for (size_t lo = 0; lo < count; lo += NESTED_CHUNK) {
+    const size_t m = count - lo < NESTED_CHUNK ? count - lo : NESTED_CHUNK, n = m * (size_t)pairs;
+    const int rc = nctx_reserve(c, m, errbuf, errlen);
+    if (rc != ZKHIP_OK) return rc;
+    NEST_HIP(hipMemcpyAsync(c->d_in1, g1 + lo * pairs * 12, n * 96, hipMemcpyHostToDevice, c->st));
+    NEST_HIP(hipMemcpyAsync(c->d_in2, g2 + lo * pairs * 24, n * 192, hipMemcpyHostToDevice, c->st));
+    hipLaunchKernelGGL(k_nested_from_abi, dim3(blocks_for(n * 2, 64)), dim3(64), 0, c->st, c->d_in1, n * 2, c->d_g1);
+    hipLaunchKernelGGL(k_nested_g2_lines, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_in2, n, c->d_lines, c->d_status);
+    NestedMillerArgs args = {};
+    for (int p = 0; p < pairs; p++) {
+      args.g1[p] = c->d_g1 + p * 2; args.g1_stride[p] = (size_t)pairs * 2;
+      args.lines[p] = c->d_lines + (size_t)p * NESTED_LINES; args.line_stride[p] = (size_t)pairs * NESTED_LINES;
+    }
+    int rc2 = nested_run(c, args, pairs, m, out + lo * 72, n, errbuf, errlen);
+    if (rc2 != ZKHIP_OK) return rc2;
+    for (size_t j = 0; j < m; j++) {
+      uint8_t s = 0;
+      for (int p = 0; p < pairs; p++) s |= c->h_status[j * pairs + p];
+      status[lo + j] = s;
+    }
+  }
+  return ZKHIP_OK;
+}
+
+int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, uint8_t* ok, uint8_t* status, char* errbuf,
+                        size_t errlen) {
+  if (!c->has_key) {
+    if (errbuf) snprintf(errbuf, errlen, "nested pairing: a context without a key");
+    return ZKHIP_ERR_STATE;
+  }
+  const size_t ni = c->n_inputs;
+  uint64_t one[72] = {0};
+  memcpy(one, FrParams::ONE64, 48);
+  const NestedLine* key_lines = reinterpret_cast<const NestedLine*>(c->d_fr + NK_LINES);
+  for (size_t lo = 0; lo < count; lo += NESTED_CHUNK) {
+    const size_t m = count - lo < NESTED_CHUNK ? count - lo : NESTED_CHUNK;
+    const int rc = nctx_reserve(c, m, errbuf, errlen);
+    if (rc != ZKHIP_OK) return rc;
+    NEST_HIP(hipMemcpyAsync(c->d_in1, proofs + lo * 48, m * 48 * 8, hipMemcpyHostToDevice, c->st));
+    if (ni) NEST_HIP(hipMemcpyAsync(c->d_in2, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
+    hipLaunchKernelGGL(k_nested_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1, m, c->d_fr, c->d_g1, c->d_lines, c->d_status);
+    hipLaunchKernelGGL(k_nested_acc, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in2, ni, m, c->d_fr + NK_ABC0, c->d_fr + NK_CHAIN, c->d_g1,
+                       c->d_status + m);
+    NestedMillerArgs args = {};
+    args.g1[0] = c->d_g1;     args.g1_stride[0] = 6; args.lines[0] = c->d_lines;                    args.line_stride[0] = NESTED_LINES;   // e(A, B)
+    args.g1[1] = c->d_g1 + 2; args.g1_stride[1] = 6; args.lines[1] = key_lines + 2 * NESTED_LINES;  args.line_stride[1] = 0;              // e(acc, -g2)
+    args.g1[2] = c->d_fr + NK_ALPHA; args.g1_stride[2] = 0; args.lines[2] = key_lines;              args.line_stride[2] = 0;              // e(alpha, -beta)
+    args.g1[3] = c->d_g1 + 4; args.g1_stride[3] = 6; args.lines[3] = key_lines + NESTED_LINES;      args.line_stride[3] = 0;              // e(C, -delta)
+    args.standin = key_lines;
+    args.status = c->d_status;
+    c->h_gt.resize(m * 72);
+    const int rc2 = nested_run(c, args, 4, m, c->h_gt.data(), 2 * m, errbuf, errlen);
+    if (rc2 != ZKHIP_OK) return rc2;
+    for (size_t j = 0; j < m; j++) {
+      const uint8_t prep = c->h_status[j];
+      const uint8_t s = (prep & NESTED_OFF_CURVE) ? NESTED_OFF_CURVE : (uint8_t)(prep | c->h_status[m + j]);
+      status[lo + j] = s;
+      ok[lo + j] = (s == 0 && memcmp(&c->h_gt[j * 72], one, sizeof one) == 0) ? 1 : 0;
+    }
+  }
+  return ZKHIP_OK;
+}
+
+int nested_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen) {
+  uint64_t *da = nullptr, *db = nullptr, *dr = nullptr;
+  hipError_t e = hipMalloc(&da, n * 576);
+  if (e == hipSuccess) e = hipMalloc(&db, n * 576);
+  if (e == hipSuccess) e = hipMalloc(&dr, n * 576);
+  if (e == hipSuccess) e = hipMemcpy(da, a, n * 576, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(db, b, n * 576, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_fq12_selftest, dim3(blocks_for(n, NESTED_WG)), dim3(NESTED_BLOCK), 0, 0, op, da, db, n, dr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dr, n * 576, hipMemcpyDeviceToHost);
+  for (void* p : {(void*)da, (void*)db, (void*)dr}) if (p) (void)hipFree(p);
+  NEST_HIP(e);
+  return ZKHIP_OK;
+}
+
+}  // namespace zkhip

@@ -197,6 +197,10 @@ class ApplicationPool:
         self.vk_limbs = E.nested_verification_key_from_json(vk_json)
         self._heap, self._order = [], itertools.count()
         self.quarantined = []          # transactions of batches that failed for good (see requeue / drop)
+        # One request per application at a time screens and pops.  While a screening runs its entries are OUT of the pool: a second
+        # request that popped meanwhile would report "insufficient entries" although enough are queued.  It waits here instead;
+        # submissions and other applications (the service's own lock) do not.  Taken only by a service whose prover screens.
+        self.screen_mu = threading.Lock()
 
     def add_tx(self, tx):
         heapq.heappush(self._heap, (-tx["fee_in_wei"], next(self._order), tx))
@@ -229,6 +233,19 @@ class ApplicationPool:
                 back += 1
         return back
 
+    def take_unscreened(self):
+        """The entries that no screening has passed yet, out of the queue, in queue order (AggregatorService._screen): the caller puts
+        back the ones that pass (restore) with their fee and arrival order."""
+        taken = sorted((e for e in self._heap if not e[2].get("screened")), key=lambda e: e[:2])
+        if taken:
+            self._heap = [e for e in self._heap if e[2].get("screened")]
+            heapq.heapify(self._heap)
+        return taken
+
+    def restore(self, entries):
+        for e in entries:
+            heapq.heappush(self._heap, e)
+
     def drop(self, entries):
         """A batch whose proof failed for a reason that will not go away (malformed or degenerate input): the reference loses it
         (aggregator_server.cpp:283-340 pops the batch before proving and never puts it back); kept aside for the operator."""
@@ -253,8 +270,11 @@ class GpuProver:
     """The wrapping prover behind the service: circuit, keypair (file or fresh setup), HBM-resident key, streaming pipeline."""
     snark_name = "GROTH16"
 
-    def __init__(self, keypair_file=None, device=0, gpu_slots=32, witness_workers=10, gpu_witness=False, devices=None, hybrid_witness=False):
-        """devices: the GPUs of the node this ONE server process drives (the reference server is one process that owns its prover:
+    def __init__(self, keypair_file=None, device=0, gpu_slots=32, witness_workers=10, gpu_witness=False, devices=None, hybrid_witness=False,
+                 screen_nested=False):
+        """screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier) before a batch is popped, so
+        that an invalid one costs no slot of a wrapping proof (`screen`; off: the service never asks).
+        devices: the GPUs of the node this ONE server process drives (the reference server is one process that owns its prover:
         aggregator_server.cpp:106-118, 390-416) - a resident copy of the key and a streaming pipeline on each, behind a dispatcher
         (zkhip_dispatcher_*); an index may repeat (two contexts on one GPU).  None / one entry: that GPU alone (`device`)."""
         from . import zkhip
@@ -262,6 +282,8 @@ class GpuProver:
         devices = [int(d) for d in devices] if devices else [int(device)]
         device = devices[0]
         self.devices = devices
+        self.screen_nested = bool(screen_nested)
+        self._screens, self._screen_mu = {}, threading.Lock()      # nested key bytes -> (NestedVerifier or None, its lock)
         self.gpu_slots = gpu_slots * len(devices)        # (the handler pool is as deep as the node has proofs in flight)
         zkhip.init(device)
         self.agg = zkhip.AggregatorCircuit(BATCH_SIZE, NUM_INPUTS_PER_NESTED_PROOF)
@@ -299,11 +321,36 @@ class GpuProver:
         """RegisterApplication's part in the prover (aggregator_server.cpp:170-235 stores the key): the streaming prover computes the
         key's constants now (zkhip_aggregator_app: the key's share of every assignment and of four of the five MSMs), so that the
         application's first batch does not pay for them.  A degenerate key gets no handle and is proved by the plain path."""
+        if self.screen_nested:
+            self._screen_handle(nested_vk_limbs)
         try:
             self.pipe.register_app(nested_vk_limbs)
             return True
         except self.zk.ZkhipError:
             return False
+
+    def _screen_handle(self, nested_vk_limbs):
+        """The application's NestedVerifier and the lock that keeps one batch in flight on it; (None, lock) for a key the handle
+        refuses (its own chains are degenerate): such a key keeps the host route."""
+        key = np.ascontiguousarray(nested_vk_limbs, dtype=np.uint64).tobytes()
+        with self._screen_mu:
+            if key not in self._screens:
+                try:
+                    v = self.zk.NestedVerifier(nested_vk_limbs, NUM_INPUTS_PER_NESTED_PROOF)
+                except self.zk.ZkhipError as e:
+                    if e.code != -1:                                             # only ZKHIP_ERR_ARG is a property of the key
+                        raise
+                    v = None
+                self._screens[key] = (v, threading.Lock())
+            return self._screens[key]
+
+    def screen(self, nested_vk_limbs, proofs, inputs):
+        """One verdict per nested proof (proofs: n x 48 limbs, inputs: n x k x 6), all of them in ONE batch on the GPU."""
+        v, lock = self._screen_handle(nested_vk_limbs)
+        if v is None:
+            return [bool(self.zk.bls12_377_groth16_verify(nested_vk_limbs, i, p)) for p, i in zip(proofs, inputs)]
+        with lock:
+            return [bool(b) for b in v.verify_batch(np.array(inputs), np.array(proofs))]
 
     def check_nested_proof(self, nested_vk_limbs, proof_limbs):
         """Well-formedness of ONE nested proof at submission time (libsnark's proof.is_well_formed(): every point on its curve).
@@ -319,6 +366,10 @@ class GpuProver:
         return E.extended_proof_to_json(proof, prim)
 
     def close(self):
+        for v, _ in self._screens.values():
+            if v is not None:
+                v.free()
+        self._screens = {}
         self.pipe.free()
         if self.crs is not None:
             self.crs.free()
@@ -333,6 +384,7 @@ class AggregatorService:
         self.prover = prover
         self.pools = {}
         self.mu = threading.Lock()
+        self.screen_dropped = 0          # nested transactions a prover's `screen` refused (never proved, kept in the pool's `screen_refused`)
 
     # --- RPCs (aggregator_server.cpp:130-348) ---
     def GetConfiguration(self, request, context):
@@ -394,13 +446,25 @@ class AggregatorService:
     def GenerateAggregatedTransaction(self, request, context):
         def run():
             name = request.application_name
-            with self.mu:
-                pool = self._pool(name)
-                entries = pool.pop_batch_entries()
-                if not entries:
-                    raise RuntimeError("insufficient entries in pool")                   # aggregator_server.cpp:298-300
-                batch = [e[2] for e in entries]
-                vk_limbs = pool.vk_limbs
+            screen = getattr(self.prover, "screen", None) if getattr(self.prover, "screen_nested", True) else None
+            def pop():
+                with self.mu:
+                    pool = self._pool(name)
+                    late = pool.take_unscreened() if screen is not None else []  # arrived during the screening: they wait for the next one
+                    entries = pool.pop_batch_entries()
+                    pool.restore(late)
+                    if not entries:
+                        raise RuntimeError("insufficient entries in pool")               # aggregator_server.cpp:298-300
+                    return pool, entries, pool.vk_limbs
+            if screen is not None:
+                with self.mu:
+                    screen_mu = self._pool(name).screen_mu
+                with screen_mu:
+                    self._screen(name, screen)
+                    pool, entries, vk_limbs = pop()
+            else:
+                pool, entries, vk_limbs = pop()
+            batch = [e[2] for e in entries]
             try:
                 ep = self.prover.prove(vk_limbs, [tx["proof"] for tx in batch], [tx["inputs"] for tx in batch])
             except Exception as e:                                                        # noqa: BLE001
@@ -423,6 +487,33 @@ class AggregatorService:
         return self._guard(context, run, message_class("zecale_proto.AggregatedTransaction"))
 
     # --- helpers ---
+    def _screen(self, name, screen):
+        """Every queued transaction of the application that no screening has passed yet goes through the prover's `screen` in ONE
+        call, outside the lock (submissions go on meanwhile).  What passes goes back with its fee and arrival order and is never
+        screened again; what fails is set aside and counted.  If the screening itself fails, all of them go back unmarked."""
+        with self.mu:
+            pool = self._pool(name)
+            taken = pool.take_unscreened()
+            vk_limbs = pool.vk_limbs
+        if not taken:
+            return
+        try:
+            verdicts = list(screen(vk_limbs, [e[2]["proof"] for e in taken], [e[2]["inputs"] for e in taken]))
+            if len(verdicts) != len(taken):
+                raise RuntimeError("screen returned %d verdicts for %d proofs" % (len(verdicts), len(taken)))
+        except Exception:
+            with self.mu:
+                pool.restore(taken)
+            raise
+        with self.mu:
+            good = [e for e, ok in zip(taken, verdicts) if ok]
+            for e in good:
+                e[2]["screened"] = True
+            pool.restore(good)
+            bad = [e[2] for e, ok in zip(taken, verdicts) if not ok]
+            pool.screen_refused = getattr(pool, "screen_refused", []) + bad
+            self.screen_dropped += len(bad)
+
     def _pool(self, name):
         if name not in self.pools:
             raise KeyError("map::at")                                                    # std::map::at throws; e.what() reaches the client
@@ -524,9 +615,11 @@ def main(argv=None):
                                                                "(round 5: 421 proofs/s on 2.2 cores against 439 on 4.1)")
     ap.add_argument("--hybrid-witness", action="store_true", help="host generators beside the GPU generator, taking what its launches leave: between the two "
                                                                    "modes in host cores, up to the host mode's proofs/s")
+    ap.add_argument("--screen-nested", action="store_true", help="verify the queued nested proofs in batches on the GPU before a batch is popped: "
+                                                                 "an invalid one is dropped instead of taking a slot of a wrapping proof")
     args = ap.parse_args(argv)
     print("[INFO] Init params of both curves")
-    prover = GpuProver(args.keypair, device=args.device, gpu_witness=args.gpu_witness, hybrid_witness=args.hybrid_witness,
+    prover = GpuProver(args.keypair, device=args.device, gpu_witness=args.gpu_witness, hybrid_witness=args.hybrid_witness, screen_nested=args.screen_nested,
                        devices=[int(x) for x in args.devices.split(",")] if args.devices else None)
     print("[INFO] Circuit has %d constraints" % prover.agg.num_constraints)
     print("[INFO] Setup successful, starting the server...")

@@ -41,6 +41,8 @@ EXPORTS = [
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
     "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path",
     "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
+    "zkhip_nested_verifier_new", "zkhip_nested_verifier_num_inputs", "zkhip_nested_verifier_verify_batch", "zkhip_nested_verifier_last_fallbacks",
+    "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
 ]
 
 
@@ -209,6 +211,14 @@ def load():
     lib.zkhip_groth16_verify_checked.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.c_void_p]
     lib.zkhip_internal_fq6_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
     lib.zkhip_internal_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
+    lib.zkhip_nested_verifier_new.argtypes = [c_u64p, ctypes.c_size_t, vpp]
+    lib.zkhip_nested_verifier_num_inputs.argtypes = [ctypes.c_void_p]
+    lib.zkhip_nested_verifier_num_inputs.restype = ctypes.c_size_t
+    lib.zkhip_nested_verifier_verify_batch.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.zkhip_nested_verifier_last_fallbacks.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    lib.zkhip_nested_verifier_free.argtypes = [ctypes.c_void_p]
+    lib.zkhip_internal_fq12_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
+    lib.zkhip_internal_nested_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
     _lib = lib
     return lib
 
@@ -791,6 +801,67 @@ def bls12_377_groth16_verify(nested_vk, inputs, proof):
     _check(load().zkhip_bls12_377_groth16_verify(_p(vk[:12]), _p(vk[12:36]), _p(vk[36:60]), _p(vk[60:]), _p(inp), inp.shape[0],
                                                  _p(pr[:12]), _p(pr[12:36]), _p(pr[36:]), ctypes.byref(ok)))
     return bool(ok.value)
+
+
+# the nested batch verifier's kernels (zecale_amd/csrc/pairing_bls.cuh / pairing_bls.hip): a verification owns sixteen lanes, so one
+# wave holds NESTED_VERIFIER_GROUP of them and one 128-thread workgroup NESTED_VERIFIER_WORKGROUP
+NESTED_VERIFIER_GROUP = 4
+NESTED_VERIFIER_WORKGROUP = 8
+
+
+class NestedVerifier:
+    """Nested (BLS12-377) Groth16 verification in batches on the GPU (zkhip_nested_verifier): the verdicts of bls12_377_groth16_verify
+    from gfx950 kernels.  nested_vk: 60 + 12 (k + 1) limbs (alpha | beta | delta | ABC), k = inputs_per_proof.  The key is checked on
+    the host when the handle is made (a refused key raises, the message names the element).  Every coordinate and input must be fully
+    reduced.  One batch in flight per handle; handles run side by side, one host thread each."""
+
+    def __init__(self, nested_vk, inputs_per_proof):
+        vk = np.ascontiguousarray(nested_vk, dtype=np.uint64).reshape(-1)
+        assert vk.size == 60 + 12 * (inputs_per_proof + 1)
+        self.handle = ctypes.c_void_p()
+        _check(load().zkhip_nested_verifier_new(_p(vk), inputs_per_proof, ctypes.byref(self.handle)))
+        self.n_inputs = int(load().zkhip_nested_verifier_num_inputs(self.handle))
+
+    def verify_batch(self, inputs, proofs):
+        """inputs: count x n_inputs x 6 limbs; proofs: count x 48 limbs (a | b | c).  Returns a bool array, one verdict per proof."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 48)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        ok = np.zeros(pr.shape[0], dtype=np.uint8)
+        _check(load().zkhip_nested_verifier_verify_batch(self.handle, _p(inp), _p(pr), pr.shape[0], ok.ctypes.data))
+        return ok.astype(bool)
+
+    def last_fallbacks(self):
+        """How many proofs of the last batch the device handed to the host verifier (a degenerate chord-and-tangent step)."""
+        n = ctypes.c_size_t(0)
+        _check(load().zkhip_nested_verifier_last_fallbacks(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def free(self):
+        if self.handle:
+            load().zkhip_nested_verifier_free(self.handle)
+            self.handle = None
+
+
+def fq12_selftest(op, a, b):
+    """Test hook: the nested pairing kernels' per-lane Fq12 bodies.  op "mul" / "sqr" / "mul_line" (b_0 + b_1 w + b_3 w^3 + b_7 w^7 +
+    b_9 w^9); a, b: n x 12 x 6 ABI limbs; returns n x 12 x 6 limbs."""
+    x = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 12, 6)
+    y = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 12, 6)
+    assert x.shape == y.shape
+    out = np.zeros_like(x)
+    _check(load().zkhip_internal_fq12_selftest({"mul": 0, "sqr": 1, "mul_line": 2}[op], _p(x), _p(y), x.shape[0], _p(out)))
+    return out
+
+
+def nested_pairing_product(route, g1, g2):
+    """Test hook: reduced GT values of products of BLS12-377 pairings.  g1: count x pairs x 12 limbs, g2: count x pairs x 24 (pairs <= 4);
+    route "host" or "gpu".  Returns count x 12 x 6 ABI limbs."""
+    x = np.ascontiguousarray(g1, dtype=np.uint64)
+    y = np.ascontiguousarray(g2, dtype=np.uint64)
+    assert x.ndim == 3 and y.ndim == 3 and x.shape[:2] == y.shape[:2] and x.shape[2] == 12 and y.shape[2] == 24
+    out = np.zeros((x.shape[0], 12, 6), dtype=np.uint64)
+    _check(load().zkhip_internal_nested_pairing_product({"host": 0, "gpu": 1}[route], _p(x), _p(y), x.shape[1], x.shape[0], _p(out)))
+    return out
 
 
 class AggregatorCircuit:
