@@ -624,6 +624,21 @@ int zkhip_measure_fq_mul_rate(double* fq_mul_per_s);
  * untimed, HIP events on the stream the passes run on.  *ms_per_transform = elapsed / (reps x batch).  dir / coset as zkhip_ntt.
  * replaces: nothing - the measurement behind bench.py's ntt roofline (2 d 48 B per transform). */
 int zkhip_measure_ntt(unsigned log_d, int dir, int coset, int batch, int reps, double* ms_per_transform);
+/* Test hooks of the transform passes in device layout (no counterpart).
+ * ntt_packed: the engine's batched transform once on `nbuf` (1 .. 3) host vectors of 2^log_d elements, back to back in `data`, in
+ * place.  Elements are in device LOCATION order: element i of a host vector goes to location i of its device buffer and comes back
+ * from location i - the hook permutes nothing.  A vector of 2^12 elements or more is in natural order on one side of a transform and
+ * in TRANSPOSED order on the other (K = 2^ceil(log_d / 2), N2 = 2^log_d / K: element k1 + K k2 at location k1 N2 + k2);
+ * in_transposed says on which side the input is and is ignored below 2^12.  form 0: ABI limbs, 6 x u64 per element, canonical;
+ * form 1: the packed device words, 12 x u32 per element, holding value 2^406 mod r plus any multiple of r with the total below
+ * 2^384, copied in and out untouched (the transforms' input contract: below 8 r, below 64 r for the forward coset transform).  dir / coset as zkhip_ntt.  A bad argument -
+ * a forward coset transform with in_transposed at 2^12 or more among them - gives ZKHIP_ERR_ARG; nothing is launched and `data` is
+ * left as it was.
+ * ntt_set_one_each_max: process-wide override of ZKHIP_NTT_ONE_EACH_MAX - sizes up to 2^log_d_max take one sub-transform per
+ * workgroup, larger ones the wide tiles (2048 elements per workgroup); -1: the environment / default (22).  A test and measurement
+ * knob: results do not depend on it. */
+int zkhip_internal_ntt_packed(void* data, int form, int nbuf, unsigned log_d, int dir, int coset, int in_transposed);
+int zkhip_internal_ntt_set_one_each_max(int log_d_max);   /* -1: the environment / default (22) */
 /* Test hook (no counterpart): the device build's three multiplier bodies - the code every kernel runs (fp29.cuh / fp29_chain.cuh) - on
  * operands given limb by limb: field 0 = Fq (27 limbs of 29 bits), 1 = Fr (14); limbs_in holds n cases of (a, b, c, d), limbs_out
  * receives n x { a b / R, a^2 / R, (a b + c d) / R } in the device's own form (R = 2^783 / 2^406).  Operands must respect the

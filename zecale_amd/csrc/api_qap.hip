@@ -96,4 +96,19 @@ int zkhip_measure_ntt(unsigned log_d, int dir, int coset, int batch, int reps, d
   return ntt_measure((int)log_d, dir, coset, batch, reps, ms_per_transform, t_err, sizeof t_err);
 }
 
+// Test hooks of the transform passes in device layout (ntt.hip ntt_packed_hook, one_each_max)
+int zkhip_internal_ntt_packed(void* data, int form, int nbuf, unsigned log_d, int dir, int coset, int in_transposed) {
+  BIND_CUR();
+  if (!data) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if ((form != 0 && form != 1) || nbuf < 1 || nbuf > 3 || log_d > 22 || (dir != 0 && dir != 1) || (coset != 0 && coset != 1) || (in_transposed != 0 && in_transposed != 1))
+    return fail(ZKHIP_ERR_ARG, "form, dir, coset, in_transposed 0 or 1; 1 to 3 vectors; log_d <= 22");
+  if (!dir && coset && in_transposed && log_d >= 12) return fail(ZKHIP_ERR_ARG, "ntt: a forward coset transform takes its input in natural order");
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return ntt_packed_hook(data, form, nbuf, (int)log_d, dir, coset, in_transposed, t_err, sizeof t_err);
+}
+int zkhip_internal_ntt_set_one_each_max(int log_d_max) {
+  if (ntt_set_one_each_max(log_d_max) != ZKHIP_OK) return fail(ZKHIP_ERR_ARG, "log_d_max must be in [-1, 22]");
+  return ZKHIP_OK;
+}
+
 }  // extern "C"

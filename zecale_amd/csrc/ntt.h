@@ -16,6 +16,9 @@ int ntt_dev_packed_batch(uint32_t* const* d_bufs, int nbuf, int log_d, int inver
 int ntt_layout_logk(int log_d);
 int ntt_measure(int log_d, int inverse, int coset, int batch, int reps, double* ms_per_transform, char* err, size_t errlen);   // the passes alone, HIP events
 int ntt_dev_abi(uint64_t* d_data, int log_d, int inverse, int coset, char* err, size_t errlen);
+// test hooks (zkhip.h: zkhip_internal_ntt_packed, zkhip_internal_ntt_set_one_each_max)
+int ntt_packed_hook(void* data, int form, int nbuf, int log_d, int inverse, int coset, int in_transposed, char* err, size_t errlen);   // arguments checked by the caller
+int ntt_set_one_each_max(int log_d_max);   // -1: the environment / default; which tile shape runs a size - results do not depend on it
 void fr_abi_to_dev(const uint64_t* d_in, uint32_t* d_out, size_t n, hipStream_t st);
 void fr_abi_to_dev_merge(const uint64_t* d_in, const uint64_t* d_in2, uint32_t* d_out, size_t n, hipStream_t st);   // limb-wise OR of two disjoint parts
 void fr_dev_to_abi(const uint32_t* d_in, uint64_t* d_out, size_t n, hipStream_t st);

@@ -28,6 +28,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -126,7 +127,25 @@ __device__ __forceinline__ uint32_t lds_sw(uint32_t p) {
   return p ^ ((h & 1u) * 5u) ^ (((h >> 1) & 1u) * 26u) ^ (h & 0xcu) ^ (((h >> 4) & 1u) * 24u) ^ (((h >> 5) & 1u) * 17u);
 }
 
-// Inputs < 8r (every producer here stores < 2r); values grow by at most 2r per stage (< 2^7 r = 2^384 at the end).
+// Inputs < 8r where the first stage subtracts raw operands (fp_sub<.., 16>: every kind but the forward coset transform); values grow
+// by at most 2r per stage (< 2^7 r = 2^384 at the end).  The forward coset transform's first stage multiplies the subtrahend
+// (tw_scaled): its raw operands are only added to, or are the minuend of fp_sub<.., 2>, and it takes inputs < 64r (x0 + t1 < 66r,
+// 2r more in each of up to 10 later stages: < 86r).  2^384 = 152.3 r: the stores (fp_pack32 keeps 384 bits) lose no bit.
+// What each producer of a transform's input stores (qap.hip unless said otherwise):
+//   k_fr_abi_to_dev[_merge]          fp_from_abi, a product                                                  < 2r
+//   k_spmv                           every path ends in fp_mul(acc, 1) or copies a k_fr_abi_to_dev value     < 2r
+//   k_h_pointwise                    fp_mul(t, zinv)                                                         < 2r
+//   k_step_half<false>               fp_cond_sub_p of a product                                              < r
+//   a store that ends in a product (mid / post_k / post_const): pass 1 of every two-pass kind, the inverse coset
+//   kind, the one-tile inverse kinds                                                                         < 2r
+//   a last pass WITHOUT a product: the forward kinds, and the two-pass plain inverse (its 1 / d is in pass 1's table).  L stages on
+//   an input < B r (B <= 8): the first radix-4 round gives < (2 B + 16) r (x0 - x1 + 16r < (B + 16) r, then y0 - y2 + 16r, y1 + u3), every
+//   later stage adds 2r: < (2 B + 12 + 2 L) r.  The second pass of a two-pass kind (B = 2, L <= 11) stores < 38r, a one-tile forward
+//   transform of an input < 8r stores < 50r.
+// Who reads the un-multiplied outputs: the forward kinds feed k_h_pointwise alone, which multiplies them (any bound below 2^10 r).
+// The plain inverse (< 38r) feeds the forward coset transform (< 64r, above), k_step_half (a factor of a product, or the minuend of
+// fp_sub<.., 2>) and k_fr_dev_to_abi (a product).  No other transform reads them: only ntt_measure runs a plain kind on its own
+// output again - it times the passes, and its vectors' values mean nothing after the first repetition.
 // A workgroup of the QAP map's kernels that becomes resident beside the provers takes the place of one of a CU's two k_accumulate
 // workgroups (displacement), whose waves raise their own priority as they go: at the default priority a short
 // kernel's waves get the issue slots the accumulation leaves and hold their CU slot several times longer than their work takes.
@@ -388,7 +407,20 @@ static void launch_pass(const PassArgs& a, uint32_t groups, hipStream_t st) {
   while (nbuf < NTT_MAX_BATCH && a.data[nbuf]) nbuf++;
   hipLaunchKernelGGL((k_ntt_pass<LOGK, LOGC>), dim3(groups, nbuf), dim3(pass_threads(LOGK, LOGC)), 0, st, a);
 }
-static int one_each_max() { static const int v = [] { const char* e = getenv("ZKHIP_NTT_ONE_EACH_MAX"); int x = e ? atoi(e) : 22; return x < 0 || x > 22 ? 22 : x; }(); return v; }
+// A test and measurement knob: which tile shape runs a size.  Results do not depend on it.  The override (ntt_set_one_each_max,
+// process-wide; -1: none) comes first, then the environment, read once.
+static std::atomic<int> g_one_each_override{-1};
+static int one_each_max() {
+  const int o = g_one_each_override.load(std::memory_order_relaxed);
+  if (o >= 0) return o;
+  static const int v = [] { const char* e = getenv("ZKHIP_NTT_ONE_EACH_MAX"); int x = e ? atoi(e) : 22; return x < 0 || x > 22 ? 22 : x; }();
+  return v;
+}
+int ntt_set_one_each_max(int log_d_max) {
+  if (log_d_max < -1 || log_d_max > 22) return ZKHIP_ERR_ARG;
+  g_one_each_override.store(log_d_max, std::memory_order_relaxed);
+  return ZKHIP_OK;
+}
 // One workgroup per sub-transform at every size (round 5; rounds 2-4: up to 2^18, beyond that 2048 elements per workgroup - adjacent
 // sub-transforms, C * 48 contiguous bytes per row of the strided pass).  A 2048-element tile is 112 KiB of LDS: ONE workgroup per CU,
 // whose load and store phases and seven barriers leave the CU's SIMDs idle (SQ_WAIT_ANY 35 % of the wave-cycles); two independent
@@ -583,6 +615,44 @@ int ntt_dev_abi(uint64_t* d_data, int log_d, int inverse, int coset, char* err, 
     if (e != hipSuccess) { snprintf(err, errlen, "ntt: %s", hipGetErrorString(e)); rc = ZKHIP_ERR_HIP; }
   }
   (void)hipFree(p);
+  return rc;
+}
+
+// Test hook (zkhip_internal_ntt_packed): ntt_dev_packed_batch once on nbuf host vectors given in device LOCATION order - element i of
+// a host vector goes to location i of its device buffer and comes back from location i, nothing is permuted here.  form 0: ABI limbs
+// through k_fr_abi_to_dev / k_fr_dev_to_abi (log_k = 0); form 1: the packed device words, copied in and out untouched.  The caller
+// has checked the arguments; `data` is written only after the transform has run and synchronised without an error.
+int ntt_packed_hook(void* data, int form, int nbuf, int log_d, int inverse, int coset, int in_transposed, char* err, size_t errlen) {
+  const size_t d = (size_t)1 << log_d, bytes = d * 48;           // (6 x u64 and 12 x u32: 48 bytes either way)
+  uint8_t* const host = (uint8_t*)data;
+  uint32_t* bufs[NTT_MAX_BATCH] = {nullptr, nullptr, nullptr};
+  uint64_t* abi = nullptr;                                       // form 0: staging for one vector of ABI limbs
+  int rc = ZKHIP_OK;
+  hipError_t e = form == 0 ? hipMalloc(&abi, bytes) : hipSuccess;
+  for (int b = 0; b < nbuf && e == hipSuccess; b++) {
+    if ((e = hipMalloc(&bufs[b], bytes)) != hipSuccess) break;
+    if (form == 0) {
+      if ((e = hipMemcpy(abi, host + b * bytes, bytes, hipMemcpyHostToDevice)) != hipSuccess) break;
+      fr_abi_to_dev(abi, bufs[b], d, 0);                         // (the next copy into `abi` is ordered behind it: both on the null stream)
+    } else {
+      e = hipMemcpy(bufs[b], host + b * bytes, bytes, hipMemcpyHostToDevice);
+    }
+  }
+  if (e == hipSuccess) {
+    rc = ntt_dev_packed_batch(bufs, nbuf, log_d, inverse, coset, in_transposed, 0, err, errlen);
+    if (rc == ZKHIP_OK) e = hipStreamSynchronize(0);
+  }
+  for (int b = 0; b < nbuf && e == hipSuccess && rc == ZKHIP_OK; b++) {
+    if (form == 0) {
+      fr_dev_to_abi(bufs[b], abi, d, 0);
+      e = hipMemcpy(host + b * bytes, abi, bytes, hipMemcpyDeviceToHost);
+    } else {
+      e = hipMemcpy(host + b * bytes, bufs[b], bytes, hipMemcpyDeviceToHost);
+    }
+  }
+  if (e != hipSuccess) { snprintf(err, errlen, "ntt hook: %s", hipGetErrorString(e)); rc = ZKHIP_ERR_HIP; }
+  for (uint32_t* b : bufs) if (b) (void)hipFree(b);
+  if (abi) (void)hipFree(abi);
   return rc;
 }
 

@@ -43,6 +43,7 @@ EXPORTS = [
     "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
     "zkhip_nested_verifier_new", "zkhip_nested_verifier_num_inputs", "zkhip_nested_verifier_verify_batch", "zkhip_nested_verifier_last_fallbacks",
     "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
+    "zkhip_internal_ntt_packed", "zkhip_internal_ntt_set_one_each_max",
 ]
 
 
@@ -1607,6 +1608,26 @@ def measure_ntt(log_d, inverse=False, coset=False, batch=1, reps=10):
     lib.zkhip_measure_ntt.argtypes = [ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
     _check(lib.zkhip_measure_ntt(log_d, int(inverse), int(coset), batch, reps, ctypes.byref(out)))
     return out.value
+
+
+def ntt_packed(data, log_d, inverse=False, coset=False, in_transposed=False):
+    """Test hook: the engine's batched transform on 1 .. 3 vectors in device LOCATION order (zkhip_internal_ntt_packed; the hook
+    permutes nothing: natural order on one side of a transform of 2^12 elements or more, transposed order on the other).
+    data: uint64 [nbuf, 2^log_d, 6] = ABI limbs (form 0), or uint32 [nbuf, 2^log_d, 12] = the packed device words (form 1).
+    Returns a new array of the same shape and type."""
+    a = np.asarray(data)
+    assert a.dtype in (np.uint64, np.uint32) and a.ndim == 3 and a.shape[1:] == (1 << log_d, 6 if a.dtype == np.uint64 else 12), (a.dtype, a.shape)
+    out = np.ascontiguousarray(a).copy()
+    lib = load()
+    lib.zkhip_internal_ntt_packed.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    _check(lib.zkhip_internal_ntt_packed(out.ctypes.data, 0 if a.dtype == np.uint64 else 1, a.shape[0], int(log_d), int(inverse), int(coset), int(in_transposed)))
+    return out
+
+
+def ntt_set_one_each_max(log_d_max):
+    """Test / measurement knob (zkhip_internal_ntt_set_one_each_max): transforms above 2^log_d_max run the wide tiles; -1: the
+    environment (ZKHIP_NTT_ONE_EACH_MAX) or the default 22.  Process-wide; results do not depend on it."""
+    _check(load().zkhip_internal_ntt_set_one_each_max(int(log_d_max)))
 
 
 def reset_time_base():
