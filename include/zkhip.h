@@ -398,7 +398,8 @@ int zkhip_bls12_377_groth16_verify(const uint64_t vk_alpha_g1[12], const uint64_
  * function as gfx950 kernels (csrc/pairing_bls.cuh / pairing_bls.hip): sixteen lanes per verification, the lines of the key's -beta,
  * -delta and of the negated generator and the doubling chains 2^j ABC_i prepared once per handle on the host.
  * nested_vk, nested_proofs and nested_inputs are laid out as above; inputs_per_proof 0 .. 16.
- * PRECONDITION: every coordinate and input is FULLY REDUCED (below the modulus of Fr of BW6-761); the device does not look.
+ * PRECONDITION: every coordinate and input is FULLY REDUCED (below the modulus of Fr of BW6-761); the device does not look, and no
+ * point is tested for order r.  For proofs from anybody else use the CHECKED route below (zkhip_nested_verifier_new_checked).
  * zkhip_nested_verifier_new checks the key on the HOST before it touches a device: a point off its curve, or a key whose own
  * chains meet a degenerate chord-and-tangent step (an ABC_i, i >= 1, with a multiple 2^j ABC_i of y = 0 - (-1, 0) for one; a zero
  * slope denominator in the line schedule of beta, delta) is refused with ZKHIP_ERR_ARG, zkhip_last_error() naming the element.
@@ -417,6 +418,43 @@ int zkhip_nested_verifier_verify_batch(zkhip_nested_verifier* v, const uint64_t*
                                        uint8_t* ok);
 int zkhip_nested_verifier_last_fallbacks(const zkhip_nested_verifier* v, size_t* out);
 void zkhip_nested_verifier_free(zkhip_nested_verifier* v);
+
+/* ---- checked nested batches: the nested verifier for proofs somebody else made ------------------------------------------------
+ * The unchecked route above tests curve membership only, and the optimal-ate pairing is bilinear only on G1 x G2: BLS12-377's G1 has a
+ * 125-bit cofactor ((-1, 0), (0, 1) and (2, 3) are on y^2 = x^3 + 1 with orders 2, 3 and 6), its twist a 502-bit one, and an input
+ * travels as a 377-bit field element of which the accumulator reads 253 bits (x and x + r share a verdict).  The checked route gives
+ * one status byte per proof with the codes and masks of ZKHIP_VERIFY_* / ZKHIP_VERIFY_MASK_* above and the same rule: the FIRST of
+ * ENCODING, OFF_CURVE, NOT_ORDER_R that any element has, the high nibble naming exactly the elements with that code.
+ *   ENCODING     a coordinate's 6 limbs are >= the modulus of Fr of BW6-761 (A, C: 2 coordinates, B: 4); an input's 6 limbs are >= that
+ *                modulus, or its canonical value is >= r of BLS12-377 (r - 1 passes; r and 2^253 - 1 do not)
+ *   OFF_CURVE    the point is not on y^2 = x^3 + 1 (A, C) or y^2 = x^3 + 1/u (B).  The nested format has NO point at infinity: the
+ *                all-zero point fails its curve equation by itself and is OFF_CURVE - unlike the BW6-761 route above, where it passes
+ *   NOT_ORDER_R  [r] P != O, r = 0x12ab655e9a2ca55660b44d1e5c37b00159aa76fed00000010a11800000000001 (253 bits), by double-and-add over
+ *                r's bits (253 doublings, 88 additions; complete formulas, csrc/pairing_bls.cuh nested_point_has_order_r)
+ * zkhip_nested_verifier_new_checked: runs these point checks on alpha, beta, delta, ABC_0 .. ABC_k ON THE HOST before anything else
+ * reads the key (and so without a device too): a key that fails is refused with ZKHIP_ERR_ARG, zkhip_last_error() naming the first
+ * offending element (alpha:, beta:, delta:, ABC[i]:) and its code in brackets.  After that it does what zkhip_nested_verifier_new does.
+ * Only handles made here serve zkhip_nested_verifier_verify_batch_checked (ZKHIP_ERR_STATE otherwise); they serve
+ * zkhip_nested_verifier_verify_batch as well.
+ * zkhip_nested_verifier_verify_batch_checked: in front of the kernels of the unchecked route one lane per proof point (the B points
+ * first, so that a wave holds one kind of point) and one per proof's inputs run the checks; a lane stops at its first failure.  A
+ * refused proof gets its byte from the checks alone: it runs through the pairing kernels on stand-in values, is never handed to the
+ * host and never counted in zkhip_nested_verifier_last_fallbacks.  A proof nothing refuses gets ACCEPT or REJECT as the unchecked
+ * route decides it (status == 0 equals its ok); degenerate steps of the input accumulator still go to the host function and are
+ * counted.  A B of order r cannot have a degenerate line schedule - kQ = +-Q or 2kQ = O would need r | k -+ 1 or r | 2k for a k below
+ * 2^64 - so on the checked route fallbacks come from the input accumulator only.  count == 0 returns ZKHIP_OK.  status: count bytes. */
+int zkhip_nested_verifier_new_checked(const uint64_t* nested_vk, size_t inputs_per_proof, zkhip_nested_verifier** out);
+int zkhip_nested_verifier_verify_batch_checked(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs,
+                                               size_t count, uint8_t* status);
+/* The same checks on the host (no device, no zkhip_init; csrc/nested_point_check_host.hpp): the route the device's is pinned on.
+ * zkhip_bls12_377_point_check: *code = 0, ZKHIP_VERIFY_ENCODING, _OFF_CURVE or _NOT_ORDER_R for one point: 12 limbs (x | y) or, with
+ * g2 != 0, 24 (x.c0 | x.c1 | y.c0 | y.c1).  zkhip_bls12_377_groth16_verify_checked: the status byte
+ * zkhip_nested_verifier_verify_batch_checked gives for this proof (where nothing is refused, zkhip_bls12_377_groth16_verify's
+ * verdict); ZKHIP_ERR_ARG, with the element and code in zkhip_last_error(), for a key that fails the point checks. */
+int zkhip_bls12_377_point_check(const uint64_t* p, int g2, int* code);
+int zkhip_bls12_377_groth16_verify_checked(const uint64_t vk_alpha_g1[12], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                           const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_a[12],
+                                           const uint64_t proof_b[24], const uint64_t proof_c[12], uint8_t* status);
 
 /* replaces: libzecale::aggregator_circuit<wppT, wsnarkT, nverifierT, NumProofs>(inputs_per_nested_proof)
  * (libzecale/circuits/aggregator_circuit.hpp:32-114; constructor .tcc:17-98): builds the constraint system.

@@ -5,7 +5,12 @@ turns, the median of three at every count; and the wrapping stream's rate with a
 64 beside it.  Writes profiles/nested_verify_gpu.txt (or --out).  The first GPU call (work space) is not timed.
 GATE: at 1,024 proofs the GPU batch is no slower than the sixteen host threads on the same batch.  last_fallbacks must be zero
 everywhere: a batch that went through the host would make the comparison meaningless.
-Usage: python tools/nested_verify_ab.py [--out FILE] [--stream N] [--gpu-slots K]"""
+--checked measures the CHECKED route instead of the host comparison (profiles/nested_verify_checked.txt): at 64, 1,024 and 16,384 proofs
+per batch the unchecked and the checked call on ONE checked handle and the same batches taking turns, with --parent-lib the unchecked call
+of a library built from the parent commit in the same turns (nothing was added to that route: the two must agree within the spread of
+the repeats), and the wrapping stream without a screener, with an unchecked and with a checked one.  No gate: the ratio is the number on
+file.
+Usage: python tools/nested_verify_ab.py [--out FILE] [--stream N] [--gpu-slots K] [--checked [--parent-lib libzkhip.so]]"""
 import argparse
 import os
 import sys
@@ -18,18 +23,90 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HOST_THREADS = 16
+CHECKED_COUNTS = (64, 1024, 16384)
+CHECKED_ROUNDS = 5
 ROUNDS = 3
 COUNTS = (1, 64, 1024, 16384)
 EXTRA = (4, 16, 256)                # more points for the count at which the GPU overtakes the host
 SCREEN_BATCH = 64
 
 
+class ParentVerifier:
+    """zkhip_nested_verifier_* of ANOTHER build of the library (the parent commit's), loaded beside this one: its unchecked route"""
+
+    def __init__(self, path, vk, k):
+        import ctypes
+        self.ct, self.lib = ctypes, ctypes.CDLL(path)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkhip_nested_verifier_new.argtypes = [u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        self.lib.zkhip_nested_verifier_verify_batch.argtypes = [ctypes.c_void_p, u64p, u64p, ctypes.c_size_t, ctypes.c_void_p]
+        self.lib.zkhip_nested_verifier_free.argtypes = [ctypes.c_void_p]
+        self.p = lambda a: a.ctypes.data_as(u64p)
+        assert self.lib.zkhip_init(0) == 0
+        self.handle = ctypes.c_void_p()
+        self.vk = np.ascontiguousarray(vk, dtype=np.uint64)
+        assert self.lib.zkhip_nested_verifier_new(self.p(self.vk), k, ctypes.byref(self.handle)) == 0
+
+    def verify_batch(self, inp, prf):
+        ok = np.zeros(prf.shape[0], dtype=np.uint8)
+        assert self.lib.zkhip_nested_verifier_verify_batch(self.handle, self.p(inp), self.p(prf), prf.shape[0], ok.ctypes.data) == 0
+        return ok.astype(bool)
+
+    def free(self):
+        self.lib.zkhip_nested_verifier_free(self.handle)
+
+
+def checked_table(say, zkhip, vk, pool, pool_in, parent_lib):
+    """unchecked vs checked on one checked handle (and the parent build's unchecked route), the routes taking turns on the same batch"""
+    n_pool = len(pool)
+    ver = zkhip.NestedVerifier(vk, 1, checked=True)
+    parent = ParentVerifier(parent_lib, vk, 1) if parent_lib else None
+    routes = [("unchecked", lambda i, p: list(ver.verify_batch(i, p)))]
+    if parent:
+        routes.append(("parent", lambda i, p: list(parent.verify_batch(i, p))))
+    routes.append(("checked", lambda i, p: [int(c | m) == 0 for c, m in zip(*ver.verify_batch_checked(i, p))]))
+    for _, fn in routes:
+        fn(pool_in[:1], pool[:1])                            # work space
+    fallbacks = 0
+    say("%8s %-10s %10s %10s %10s %14s" % ("count", "route", "median ms", "min ms", "max ms", "verif./s"))
+    ratios = {}
+    for count in CHECKED_COUNTS:
+        idx = [i % n_pool for i in range(count)]
+        inp, prf = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
+        want = [i != n_pool - 1 for i in idx]
+        ms = {name: [] for name, _ in routes}
+        for _ in range(CHECKED_ROUNDS):
+            for name, fn in routes:
+                t = time.perf_counter()
+                ok = fn(inp, prf)
+                ms[name].append((time.perf_counter() - t) * 1e3)
+                assert ok == want, "%s verdicts at count %d" % (name, count)
+                if name != "parent":
+                    fallbacks += ver.last_fallbacks()
+        med = {name: sorted(v)[CHECKED_ROUNDS // 2] for name, v in ms.items()}
+        for name, _ in routes:
+            say("%8d %-10s %10.2f %10.2f %10.2f %14.1f" % (count, name, med[name], min(ms[name]), max(ms[name]), count / med[name] * 1e3))
+        ratios[count] = med["checked"] / med["unchecked"]
+        line = "%8d checked / unchecked = %.3f" % (count, ratios[count])
+        if parent:
+            spread = (max(ms["unchecked"]) - min(ms["unchecked"])) / med["unchecked"]
+            line += "; unchecked / parent's unchecked = %.3f (spread of the unchecked repeats: %.1f %% of their median)" % (med["unchecked"] / med["parent"], spread * 100)
+        say(line)
+    if parent:
+        parent.free()
+    return ver, fallbacks
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nested_verify_gpu.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--checked", action="store_true", help="measure the checked route against the unchecked one instead of the GPU against the host")
+    ap.add_argument("--parent-lib", default=None, help="with --checked: a libzkhip.so built from the parent commit, for its unchecked route in the same turns")
     ap.add_argument("--stream", type=int, default=1024, help="proofs per block of the stream measurement (0: skip)")
     ap.add_argument("--gpu-slots", type=int, default=24)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "nested_verify_checked.txt" if args.checked else "nested_verify_gpu.txt")
     import bench
     from tests.helpers import golden
     from zecale_amd import encoding as E
@@ -48,6 +125,24 @@ def main():
         pool.append(pr); pool_in.append(inp.reshape(1, 6))
     pool, pool_in = np.array(pool), np.array(pool_in)
     pool_in[-1] = pool_in[0]                                 # one invalid statement in the pool: proof 6 with proof 1's input
+    if args.checked:
+        say("# nested Groth16 verification, dummy-application key (1 input): the checked route (every point's encoding, curve and order, every input's range,"
+            " on the device) vs the unchecked one, %d alternating runs" % CHECKED_ROUNDS)
+        ver, fallbacks = checked_table(say, zkhip, vk, pool, pool_in, args.parent_lib)
+        gate = True
+    else:
+        ver, fallbacks, gate = host_table(say, zkhip, vk, pool, pool_in)
+    if args.stream:
+        fallbacks += stream_section(say, args, bench, zkhip, ver, pool, pool_in)
+    say("last_fallbacks summed over every GPU batch of this run: %d" % fallbacks)
+    ver.free()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0 if gate and fallbacks == 0 else 1
+
+
+def host_table(say, zkhip, vk, pool, pool_in):
     n_pool = len(pool)
     say("# nested Groth16 verification, dummy-application key (1 input): GPU kernels vs the host route on %d threads, medians of %d alternating runs"
         % (HOST_THREADS, ROUNDS))
@@ -83,68 +178,74 @@ def main():
     say("the GPU overtakes the %d host threads at count %s (smallest measured count at which its batch is no slower)" % (HOST_THREADS, over[0] if over else "none measured"))
     gate = gpu_ms[1024] <= host_ms[1024]
     say("GATE (GPU no slower than %d host threads at 1,024 proofs): %s  (%.1fx)" % (HOST_THREADS, "met" if gate else "MISSED", host_ms[1024] / gpu_ms[1024]))
+    return ver, fallbacks, gate
 
-    # ---- the wrapping stream with and without a NestedVerifier screening beside it (interleaved: without, with, without, with)
-    if args.stream:
-        nvk_l, npr, nin, trapdoor = bench.aggregator_inputs(1)
-        agg = zkhip.AggregatorCircuit(2, 1)
-        desc = zkhip.r1cs_desc_from_aggregator(agg)
-        kp = zkhip.Keypair(desc, *trapdoor)
-        crs = kp.upload_crs()
-        z = agg.witness(nvk_l, npr, nin)
-        rs = bench.random_fr_uniform(9, 2)
-        provers = [zkhip.Prover(crs, desc) for _ in range(args.gpu_slots)]
-        for p_ in provers:
-            p_.set_streaming(True)
-            p_.prove(z, rs[0], rs[1])
-        idx = [i % n_pool for i in range(SCREEN_BATCH)]
-        s_in, s_pr = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
-        s_want = [i != n_pool - 1 for i in idx]
-        screened = [0]
 
-        def block(with_screen):
-            counter, lock, stop = [args.stream], threading.Lock(), threading.Event()
-            n0 = screened[0]
+def stream_section(say, args, bench, zkhip, ver, pool, pool_in):
+    """The wrapping stream's rate without a screener and with a NestedVerifier screening batches of 64 back to back beside it, the
+    blocks interleaved, each kind twice; with --checked the handle screens through its unchecked and through its checked route.
+    Returns the fallbacks of the screening batches."""
+    n_pool, fallbacks = len(pool), [0]
+    nvk_l, npr, nin, trapdoor = bench.aggregator_inputs(1)
+    agg = zkhip.AggregatorCircuit(2, 1)
+    desc = zkhip.r1cs_desc_from_aggregator(agg)
+    kp = zkhip.Keypair(desc, *trapdoor)
+    crs = kp.upload_crs()
+    z = agg.witness(nvk_l, npr, nin)
+    rs = bench.random_fr_uniform(9, 2)
+    provers = [zkhip.Prover(crs, desc) for _ in range(args.gpu_slots)]
+    for p_ in provers:
+        p_.set_streaming(True)
+        p_.prove(z, rs[0], rs[1])
+    idx = [i % n_pool for i in range(SCREEN_BATCH)]
+    s_in, s_pr = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
+    s_want = [i != n_pool - 1 for i in idx]
+    screened = [0]
+    screen = {"unchecked": lambda: list(ver.verify_batch(s_in, s_pr)),
+              "checked": lambda: [int(c | m) == 0 for c, m in zip(*ver.verify_batch_checked(s_in, s_pr))]}
 
-            def worker(p_):
-                while True:
-                    with lock:
-                        if counter[0] <= 0:
-                            return
-                        counter[0] -= 1
-                    p_.prove(z, rs[0], rs[1])
+    def block(kind):
+        counter, lock, stop = [args.stream], threading.Lock(), threading.Event()
+        n0 = screened[0]
 
-            def screener():
-                nonlocal fallbacks
-                while not stop.is_set():
-                    assert list(ver.verify_batch(s_in, s_pr)) == s_want
-                    fallbacks += ver.last_fallbacks()
-                    screened[0] += 1
-            ths = [threading.Thread(target=worker, args=(p_,)) for p_ in provers]
-            sc = threading.Thread(target=screener) if with_screen else None
-            t = time.perf_counter()
-            if sc:
-                sc.start()
-            [x.start() for x in ths]; [x.join() for x in ths]
-            dt = time.perf_counter() - t
-            stop.set()
-            if sc:
-                sc.join()
-            return args.stream / dt, (screened[0] - n0) * SCREEN_BATCH / dt
-        rates = [(w, block(w)) for w in (False, True, False, True)]
-        say("wrapping stream, %d proofs per block on %d prover instances, proofs/s (a NestedVerifier screens batches of %d back to back beside it where it runs):"
-            % (args.stream, args.gpu_slots, SCREEN_BATCH))
-        for w, (r, s) in rates:
-            say("  %-24s %8.1f%s" % ("with NestedVerifier" if w else "without NestedVerifier", r, "   (%.0f nested verifications/s beside it)" % s if w else ""))
-        for p_ in provers:
-            p_.free()
-        crs.free(); kp.free(); agg.free()
-    say("last_fallbacks summed over every GPU batch of this run: %d" % fallbacks)
-    ver.free()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    return 0 if gate and fallbacks == 0 else 1
+        def worker(p_):
+            while True:
+                with lock:
+                    if counter[0] <= 0:
+                        return
+                    counter[0] -= 1
+                p_.prove(z, rs[0], rs[1])
+
+        def screener():
+            while not stop.is_set():
+                assert screen[kind]() == s_want
+                fallbacks[0] += ver.last_fallbacks()
+                screened[0] += 1
+        ths = [threading.Thread(target=worker, args=(p_,)) for p_ in provers]
+        sc = threading.Thread(target=screener) if kind else None
+        t = time.perf_counter()
+        if sc:
+            sc.start()
+        [x.start() for x in ths]; [x.join() for x in ths]
+        dt = time.perf_counter() - t
+        stop.set()
+        if sc:
+            sc.join()
+        return args.stream / dt, (screened[0] - n0) * SCREEN_BATCH / dt
+    kinds = (None, "unchecked", "checked") if args.checked else (None, "unchecked")
+    rates = [(k, block(k)) for k in kinds + kinds]
+    say("wrapping stream, %d proofs per block on %d prover instances, proofs/s (a NestedVerifier screens batches of %d back to back beside it where it runs):"
+        % (args.stream, args.gpu_slots, SCREEN_BATCH))
+    name = {None: "without NestedVerifier", "unchecked": "with NestedVerifier", "checked": "with NestedVerifier, checked"}
+    for k, (r, s_) in rates:
+        say("  %-30s %8.1f%s" % (name[k], r, "   (%.0f nested verifications/s beside it)" % s_ if k else ""))
+    mean = {k: sum(r for kk, (r, _) in rates if kk == k) / 2 for k in kinds}
+    for k in kinds[1:]:
+        say("  loss of the wrapping stream %s: %.1f %%" % (name[k], (1 - mean[k] / mean[None]) * 100))
+    for p_ in provers:
+        p_.free()
+    crs.free(); kp.free(); agg.free()
+    return fallbacks[0]
 
 
 if __name__ == "__main__":

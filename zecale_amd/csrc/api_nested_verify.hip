@@ -1,6 +1,8 @@
 // C ABI (include/zkhip.h): nested (BLS12-377) Groth16 verification in batches on the device (pairing_bls.hip).  The host side of a
 // handle lives here: what it derives from its key (nested_key.hpp: the curve checks, the lines of -beta, -delta and the negated
-// generator, the doubling chains 2^j ABC_i), the host route of the test hook and the fallback of proofs the device does not decide.
+// generator, the doubling chains 2^j ABC_i), the host route of the test hook and the fallback of proofs the device does not decide;
+// and the host route of the CHECKED batches (nested_point_check_host.hpp: encoding, curve and order of a point, range of an input),
+// which also checks a checked handle's key before anything else reads it.
 #include <string.h>
 #include <stdexcept>
 #include <string>
@@ -8,6 +10,9 @@
 #include "api_internal.hpp"
 #include "circuit/sections.hpp"
 #include "nested_key.hpp"
+#include "nested_point_check_host.hpp"
+#include "pairing.cuh"               // verify_refusal: one definition for both checked routes
+#include "pairing.h"                 // pairing_key_refusal
 #include "pairing_bls.h"
 
 using namespace zkhip::api;
@@ -22,6 +27,7 @@ struct zkhip_nested_verifier {
   std::vector<uint64_t> vk;              // the key as given: the fallback verifies under it
   size_t last_fallbacks;
   std::vector<uint8_t> status;
+  bool checked;                          // made by zkhip_nested_verifier_new_checked: the key's points passed the host point check
 };
 
 namespace {
@@ -51,15 +57,22 @@ NestedKeyData consts_only() {
   return kd;
 }
 
-}  // namespace
+// the host point check of a key's k + 4 points; a failure leaves pairing_key_refusal's message in t_err
+int nested_key_point_check(const uint64_t* nested_vk, size_t k) {
+  size_t element = 0;
+  const int code = zkhip::nested_key::key_check_host(nested_vk, k, &element);
+  if (!code) return ZKHIP_OK;
+  pairing_key_refusal(element, code, t_err, sizeof t_err);
+  return ZKHIP_ERR_ARG;
+}
 
-#pragma GCC visibility pop
-
-extern "C" {
-
-int zkhip_nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof, zkhip_nested_verifier** out) {
+int nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof, bool checked, zkhip_nested_verifier** out) {
   if (!nested_vk || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
   if (inputs_per_proof > 16) return fail(ZKHIP_ERR_ARG, "inputs_per_proof 0 .. 16");
+  if (checked) {                                                        // before anything else reads the key's limbs as field elements
+    const int rc = nested_key_point_check(nested_vk, inputs_per_proof);
+    if (rc != ZKHIP_OK) return rc;
+  }
   PreparedKey pk;
   try {
     std::string why;                                                    // on the host, before a device is touched
@@ -78,25 +91,22 @@ int zkhip_nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof
   NestedCtx* ctx = nullptr;
   const int rc = nested_ctx_new(&kd, &ctx, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
-  zkhip_nested_verifier* v = new zkhip_nested_verifier{ctx, cur_dev(), inputs_per_proof, {}, 0, {}};
+  zkhip_nested_verifier* v = new zkhip_nested_verifier{ctx, cur_dev(), inputs_per_proof, {}, 0, {}, checked};
   v->vk.assign(nested_vk, nested_vk + 60 + 12 * (inputs_per_proof + 1));
   *out = v;
   return ZKHIP_OK;
 }
 
-size_t zkhip_nested_verifier_num_inputs(const zkhip_nested_verifier* v) { return v ? v->n_inputs : 0; }
-
-int zkhip_nested_verifier_verify_batch(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
-                                       uint8_t* ok) {
-  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+// one batch on either route.  out: ok bytes (1 / 0), or on the checked route the status bytes of zkhip.h.  What the device marked
+// degenerate is decided by the host's verifier; a refused proof is never among them (nested_verify_batch clears its status).
+int nested_verifier_run(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count, bool checked, uint8_t* out) {
   v->last_fallbacks = 0;
   if (count == 0) return ZKHIP_OK;
-  if (!nested_proofs || !ok || (v->n_inputs && !nested_inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (!nested_proofs || !out || (v->n_inputs && !nested_inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
   BIND(v);
   v->status.resize(count);
-  const int rc = nested_verify_batch(v->ctx, nested_inputs, nested_proofs, count, ok, v->status.data(), t_err, sizeof t_err);
+  const int rc = nested_verify_batch(v->ctx, nested_inputs, nested_proofs, count, checked, out, v->status.data(), t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
-  // what the device marked degenerate is decided by the host's verifier
   const uint64_t* vk = v->vk.data();
   size_t fallbacks = 0;
   for (size_t i = 0; i < count; i++) {
@@ -107,10 +117,71 @@ int zkhip_nested_verifier_verify_batch(zkhip_nested_verifier* v, const uint64_t*
     const int rc2 = zkhip_bls12_377_groth16_verify(vk, vk + 12, vk + 36, vk + 60, v->n_inputs ? nested_inputs + i * v->n_inputs * 6 : nullptr, v->n_inputs,
                                                    pr, pr + 12, pr + 36, &one);
     if (rc2 != ZKHIP_OK) return fail(rc2, "the host verifier refused a proof the device handed back");
-    ok[i] = one ? 1 : 0;
+    out[i] = checked ? (uint8_t)(one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT) : (uint8_t)(one ? 1 : 0);
   }
   v->last_fallbacks = fallbacks;
   return ZKHIP_OK;
+}
+
+}  // namespace
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int zkhip_nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof, zkhip_nested_verifier** out) {
+  return nested_verifier_new(nested_vk, inputs_per_proof, false, out);
+}
+int zkhip_nested_verifier_new_checked(const uint64_t* nested_vk, size_t inputs_per_proof, zkhip_nested_verifier** out) {
+  return nested_verifier_new(nested_vk, inputs_per_proof, true, out);
+}
+
+// ---- the checks of the checked nested verifier on the host (nested_point_check_host.hpp): no device
+int zkhip_bls12_377_point_check(const uint64_t* p, int g2, int* code) {
+  if (!p || !code) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *code = zkhip::nested_key::point_check_host(p, g2 != 0);
+  return ZKHIP_OK;
+}
+
+int zkhip_bls12_377_groth16_verify_checked(const uint64_t vk_alpha_g1[12], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                           const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_a[12],
+                                           const uint64_t proof_b[24], const uint64_t proof_c[12], uint8_t* status) {
+  namespace K = zkhip::nested_key;
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !proof_a || !proof_b || !proof_c || !status || (n_inputs && !inputs))
+    return fail(ZKHIP_ERR_ARG, "null pointer");
+  const uint64_t* key[3] = {vk_alpha_g1, vk_beta_g2, vk_delta_g2};
+  for (size_t i = 0; i < n_inputs + 4; i++) {      // the order and the words of zkhip_nested_verifier_new_checked
+    const int code = K::point_check_host(i < 3 ? key[i] : vk_abc + (i - 3) * 12, i == 1 || i == 2);
+    if (!code) continue;
+    pairing_key_refusal(i, code, t_err, sizeof t_err);
+    return ZKHIP_ERR_ARG;
+  }
+  uint8_t e[4];
+  e[0] = (uint8_t)K::point_check_host(proof_a, false);
+  e[1] = (uint8_t)K::point_check_host(proof_b, true);
+  e[2] = (uint8_t)K::point_check_host(proof_c, false);
+  e[3] = (uint8_t)K::inputs_check_host(inputs, n_inputs);
+  if ((*status = verify_refusal(e)) != 0) return ZKHIP_OK;
+  int ok = 0;
+  const int rc = zkhip_bls12_377_groth16_verify(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, inputs, n_inputs, proof_a, proof_b, proof_c, &ok);
+  if (rc != ZKHIP_OK) return fail(rc, "zkhip_bls12_377_groth16_verify failed");
+  *status = ok ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT;
+  return ZKHIP_OK;
+}
+
+size_t zkhip_nested_verifier_num_inputs(const zkhip_nested_verifier* v) { return v ? v->n_inputs : 0; }
+
+int zkhip_nested_verifier_verify_batch(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
+                                       uint8_t* ok) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  return nested_verifier_run(v, nested_inputs, nested_proofs, count, false, ok);
+}
+
+int zkhip_nested_verifier_verify_batch_checked(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
+                                               uint8_t* status) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (!v->checked) return fail(ZKHIP_ERR_STATE, "checked batches need a handle of zkhip_nested_verifier_new_checked");
+  return nested_verifier_run(v, nested_inputs, nested_proofs, count, true, status);
 }
 
 int zkhip_nested_verifier_last_fallbacks(const zkhip_nested_verifier* v, size_t* out) {

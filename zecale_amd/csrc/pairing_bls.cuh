@@ -11,7 +11,8 @@
 // the Miller loop: the lines (lambda', b) of a G2 point depend on that point alone and come from g2_lines_lane (one lane per point,
 // the affine chain of g2_precompute) or from the host (the key's -beta, -delta and the negated generator).
 // Every body is a function of (lane index, operand arrays); none waits, spins or branches on data other than by selects - except
-// the one-lane-per-point bodies (g2_lines_lane, nested_acc_lane, the curve checks), which run in kernels without barriers.
+// the one-lane-per-point bodies (g2_lines_lane, nested_acc_lane, the curve checks, the checked route's nested_point_check and
+// nested_inputs_check at the end of this file), which run in kernels without barriers.
 //
 // LAZY BOUNDS ([k]: value < k p, limbs normalised).  fp29.cuh's contract: a b + c d < 2^10 R p; here R / p > 2^29, so any sum of
 // products of operands [k1] x [k2] with sum k1 k2 < 2^39 is inside it and its result is < p (1 + 2^-10): written [1+].
@@ -22,6 +23,7 @@
 #include "../../include/zkhip.h"
 #include "fp29.cuh"
 #include "fp_inv.cuh"
+#include "pairing.cuh"      // abi_geq_modulus, verify_refusal: shared with the BW6-761 checked route
 
 namespace zkhip {
 
@@ -272,6 +274,145 @@ ZK_HD ZK_INL bool nested_acc_lane(const Fr* abc0, const Fr* chain, const uint64_
   out[0] = fp_mul(acc.X, fp_mul(zi, acc.ZZZ));
   out[1] = fp_mul(acc.Y, fp_mul(zi, acc.ZZ));
   return fine;
+}
+
+// ---- checked batches: encoding, curve membership and order of one nested point, one lane per point (k_nested_point_check).
+// A G1 point is 12 ABI limbs (x | y), a G2 point 24 (x.c0 | x.c1 | y.c0 | y.c1).  The codes are zkhip.h's ZKHIP_VERIFY_*.  The nested
+// format has NO point at infinity: the all-zero point fails its curve equation by itself (0 != 1, 0 != 1/u) and is OFF_CURVE - unlike
+// pairing.cuh's point_check.  A lane stops at its first failure: an unreduced coordinate is never converted, a point off its curve
+// never enters the group law.
+ZK_HD ZK_INL bool nested_abi_geq_modulus(const uint64_t* x /* 6 raw ABI limbs */) { return abi_geq_modulus<FrParams>(x); }
+
+// One set of names over Fr and Fr2, so that the XYZZ formulas below are written once (they never use b: one body serves G1 and G2).
+// nf_mul(x, y): any x, y with [kx] x [ky], kx (ky + 128) < 2^39, and y [25] at most (fr2_mul forms 128 p - 5 y.b); result [1+].
+ZK_HD ZK_INL Fr nf_mul(const Fr& x, const Fr& y) { return fp_mul(x, y); }
+ZK_HD ZK_INL Fr2 nf_mul(const Fr2& x, const Fr2& y) { return fr2_mul(x, y); }
+ZK_HD ZK_INL Fr nf_add(const Fr& x, const Fr& y) { return fp_add(x, y); }
+ZK_HD ZK_INL Fr2 nf_add(const Fr2& x, const Fr2& y) { return fr2_add(x, y); }
+template <int K> ZK_HD ZK_INL Fr nf_sub(const Fr& x, const Fr& y) { return fp_sub_k<FrParams, K>(x, y); }          // x - y + K p, y [K] at most
+template <int K> ZK_HD ZK_INL Fr2 nf_sub(const Fr2& x, const Fr2& y) { return fr2_sub<K>(x, y); }
+// exact for a product's result ([1+] < 2 p) and for an exact zero; never applied to anything else
+ZK_HD ZK_INL bool nf_is_zero_2p(const Fr& x) { return fp_is_zero_2p(x); }
+ZK_HD ZK_INL bool nf_is_zero_2p(const Fr2& x) { return fp_is_zero_2p(x.a) && fp_is_zero_2p(x.b); }
+ZK_HD ZK_INL void nf_set(Fr& x, bool one) { x = one ? fp_one<FrParams>() : fp_zero<FrParams>(); }
+ZK_HD ZK_INL void nf_set(Fr2& x, bool one) { x.a = one ? fp_one<FrParams>() : fp_zero<FrParams>(); x.b = fp_zero<FrParams>(); }
+
+// Extended Jacobian coordinates (x = X / ZZ, y = Y / ZZZ), infinity <=> ZZ = 0.  Stored: X [10], Y [4]; ZZ, ZZZ products [1+] or exact zeros.
+template <class E> struct NestedXYZZ { E X, Y, ZZ, ZZZ; };
+
+// 2 P (dbl-2008-s-1, ec.cuh xyzz_dbl).  P.X [10], P.Y [4] -> X [6], Y [4].  A point of order 2 (Y = 0, so U = 0 mod p) gives V = W = 0
+// and with them ZZ = ZZZ = 0: infinity.  Infinity stays infinity (ZZ3 = V ZZ).
+template <class E> ZK_HD ZK_INL NestedXYZZ<E> nested_xyzz_dbl(const NestedXYZZ<E>& p) {
+  NestedXYZZ<E> r;
+  const E U = nf_add(p.Y, p.Y);                           // [8]
+  const E V = nf_mul(U, U);                               // [1+]
+  const E W = nf_mul(U, V);                               // [1+]
+  const E S = nf_mul(p.X, V);                             // [1+]
+  const E xx = nf_mul(p.X, p.X);                          // [1+]   ([10] x [10])
+  const E M = nf_add(nf_add(xx, xx), xx);                 // [6]
+  const E MM = nf_mul(M, M);                              // [1+]
+  r.X = nf_sub<4>(MM, nf_add(S, S));                      // [6]    (2 S is [4])
+  const E t = nf_sub<8>(S, r.X);                          // [10]   (X3 is [6] <= 8)
+  const E Wy = nf_mul(W, p.Y);                            // [1+]
+  r.Y = nf_sub<2>(nf_mul(M, t), Wy);                      // [4]
+  r.ZZ = nf_mul(V, p.ZZ);                                 // [1+]
+  r.ZZZ = nf_mul(W, p.ZZZ);                               // [1+]
+  return r;
+}
+// 2 (x, y) for an affine point, x, y [2] (mdbl-2008-s-1): the doubling above with ZZ = ZZZ = 1
+template <class E> ZK_HD ZK_INL NestedXYZZ<E> nested_xyzz_dbl_affine(const E& x, const E& y) {
+  NestedXYZZ<E> p;
+  p.X = x; p.Y = y; nf_set(p.ZZ, true); nf_set(p.ZZZ, true);
+  return nested_xyzz_dbl(p);
+}
+// acc += (x2, y2), a finite affine point with coordinates [2] (madd-2008-s, ec.cuh xyzz_madd), COMPLETE - unlike nested_acc_step it
+// takes its same-x branches: it opens from infinity, doubles when acc = (x2, y2) and goes to infinity when acc = -(x2, y2).  The two
+// comparisons are made on PP and RR, results of products ([1+]; a square is zero exactly when its root is), never on P [18] or R [6].
+template <class E> ZK_HD ZK_INL void nested_xyzz_madd(NestedXYZZ<E>& acc, const E& x2, const E& y2) {
+  if (nf_is_zero_2p(acc.ZZ)) {
+    acc.X = x2; acc.Y = y2; nf_set(acc.ZZ, true); nf_set(acc.ZZZ, true);
+    return;
+  }
+  const E U2 = nf_mul(x2, acc.ZZ);                        // [1+]
+  const E S2 = nf_mul(y2, acc.ZZZ);                       // [1+]
+  const E P = nf_sub<16>(U2, acc.X);                      // [18]   (acc.X is [10] <= 16)
+  const E R = nf_sub<4>(S2, acc.Y);                       // [6]    (acc.Y is [4])
+  const E PP = nf_mul(P, P);                              // [1+]   ([18] x [18], second operand <= [25])
+  const E RR = nf_mul(R, R);                              // [1+]
+  if (nf_is_zero_2p(PP)) {                                // same x: acc = +-(x2, y2)
+    if (nf_is_zero_2p(RR)) acc = nested_xyzz_dbl_affine(x2, y2);
+    else { nf_set(acc.X, false); nf_set(acc.Y, false); nf_set(acc.ZZ, false); nf_set(acc.ZZZ, false); }
+    return;
+  }
+  const E PPP = nf_mul(P, PP);                            // [1+]
+  const E Q = nf_mul(acc.X, PP);                          // [1+]
+  const E X3 = nf_sub<4>(nf_sub<4>(RR, PPP), nf_add(Q, Q));   // [2 + 4 + 4 = 10]
+  const E t = nf_sub<16>(Q, X3);                          // [18]   (X3 is [10] <= 16)
+  const E Y3a = nf_mul(t, R);                             // [1+]   (the [18] factor first: the second operand stays <= [25])
+  const E Y3b = nf_mul(acc.Y, PPP);                       // [1+]
+  acc.X = X3;
+  acc.Y = nf_sub<2>(Y3a, Y3b);                            // [4]
+  acc.ZZ = nf_mul(acc.ZZ, PP);                            // [1+]
+  acc.ZZZ = nf_mul(acc.ZZZ, PPP);                         // [1+]
+}
+
+// bit i (0 .. 252) of r = 0x12ab655e9a2ca55660b44d1e5c37b00159aa76fed00000010a11800000000001, the order of the nested groups
+ZK_HD ZK_INL bool nested_r_bit(int i) {
+  const uint64_t w = i >= 192 ? 0x12ab655e9a2ca556ull : i >= 128 ? 0x60b44d1e5c37b001ull : i >= 64 ? 0x59aa76fed0000001ull : 0x0a11800000000001ull;
+  return ((w >> (i & 63)) & 1) != 0;
+}
+constexpr int NESTED_R_BITS = 253;
+
+// [r] (x, y) = O by double-and-add over r's 253 bits, most significant first: the definition.  x, y [2].  The bit is the same for every
+// lane.  Every valid point ends with (r - 1) P + P = O in the same-x branch of the addition; a point of order 3 reaches that branch in
+// the second iteration (2 P + P); a point of order 2 sends the doubling to ZZ = 0.
+// Bounds: acc leaves the doubling with X [6], Y [4] and the addition with X [10], Y [4] ([2], [2] opened from the point): always
+// within the X [10], Y [4] both formulas take.
+template <class E> ZK_HD ZK_INL bool nested_point_has_order_r(const E& x, const E& y) {
+  NestedXYZZ<E> acc;
+  nf_set(acc.X, false); nf_set(acc.Y, false); nf_set(acc.ZZ, false); nf_set(acc.ZZZ, false);
+#pragma unroll 1
+  for (int i = NESTED_R_BITS - 1; i >= 0; i--) {
+    acc = nested_xyzz_dbl(acc);                            // X [6], Y [4]
+    if (nested_r_bit(i)) nested_xyzz_madd(acc, x, y);     // X [10], Y [4]
+  }
+  return nf_is_zero_2p(acc.ZZ);
+}
+
+// p: 12 ABI limbs (G1) or 24 (G2).  fifth_neg: -1/5 in device form [2] (read for G2 only).
+ZK_HD ZK_INL int nested_point_check(const uint64_t* p, bool g2, const Fr& fifth_neg) {
+  bool unreduced = nested_abi_geq_modulus(p) || nested_abi_geq_modulus(p + 6);
+  if (g2) unreduced = unreduced || nested_abi_geq_modulus(p + 12) || nested_abi_geq_modulus(p + 18);
+  if (unreduced) return ZKHIP_VERIFY_ENCODING;
+  if (g2) {
+    const Fr2 x{fp_from_abi<FrParams>(p), fp_from_abi<FrParams>(p + 6)}, y{fp_from_abi<FrParams>(p + 12), fp_from_abi<FrParams>(p + 18)};   // [2]
+    if (!nested_g2_on_curve(x, y, fifth_neg)) return ZKHIP_VERIFY_OFF_CURVE;
+    return nested_point_has_order_r(x, y) ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_NOT_ORDER_R;
+  }
+  const Fr x = fp_from_abi<FrParams>(p), y = fp_from_abi<FrParams>(p + 6);                 // [2]
+  if (!nested_g1_on_curve(x, y)) return ZKHIP_VERIFY_OFF_CURVE;
+  return nested_point_has_order_r(x, y) ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_NOT_ORDER_R;
+}
+
+// any of `n` inputs (6 raw ABI limbs each) is not an element of the nested scalar field: its limbs are >= the modulus of the field that
+// carries it (Fr of BW6-761), or its canonical value is >= r (the accumulator reads 253 bits: x and x + r would share a verdict)
+ZK_HD ZK_INL int nested_inputs_check(const uint64_t* inputs, size_t n) {
+  constexpr uint32_t r32[12] = {0x00000001u, 0x0a118000u, 0xd0000001u, 0x59aa76feu, 0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu, 0, 0, 0, 0};
+  bool bad = false;
+#pragma unroll 1
+  for (size_t i = 0; i < n; i++) {
+    if (nested_abi_geq_modulus(inputs + i * 6)) { bad = true; continue; }
+    uint32_t w[12];
+    fp_abi_to_canonical_words<FrParams>(inputs + i * 6, w);
+    uint32_t borrow = 0;                                    // of w - r: clear when w >= r
+#pragma unroll
+    for (int t = 0; t < 12; t++) {
+      const uint32_t a = w[t], m = r32[t], d = a - m;
+      borrow = (uint32_t)(a < m) | (uint32_t)(d < borrow);
+    }
+    bad = bad || borrow == 0;
+  }
+  return bad ? ZKHIP_VERIFY_ENCODING : ZKHIP_VERIFY_ACCEPT;
 }
 
 }  // namespace zkhip

@@ -36,8 +36,10 @@ int nested_products(NestedCtx* c, const uint64_t* g1, const uint64_t* g2, int pa
                     size_t errlen);
 // ok[i] = e(A_i, B_i) e(acc_i, -g2) e(alpha, -beta) e(C_i, -delta) == 1 where status[i] is 0; 0 where it is NESTED_OFF_CURVE; undecided
 // where it has NESTED_DEGENERATE.  proofs: count x 48 limbs, inputs: count x n_inputs x 6.
-int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, uint8_t* ok, uint8_t* status, char* errbuf,
-                        size_t errlen);
+// checked: every proof point and input is validated on the device first and ok[i] is the status byte of zkhip.h (ZKHIP_VERIFY_*); where
+// it names a refusal status[i] is 0, where status[i] has NESTED_DEGENERATE ok[i] is undecided as before.
+int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, uint8_t* status,
+                        char* errbuf, size_t errlen);
 // op 0: a b, 1: a^2, 2: a (b0 + b1 w + b3 w^3 + b7 w^7 + b9 w^9) through the lane bodies of pairing_bls.cuh; a, b, out: n x 72 ABI limbs
 int nested_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen);
 

@@ -11,6 +11,11 @@
 // In front run the one-lane-per-proof kernels without LDS or barriers: k_nested_prep (curve checks of A, B, C - a lane leaves at its
 // first failure - and the 69 lines of B) and k_nested_acc (acc = ABC_0 + sum x_i ABC_i along the host's chain).  They write one status
 // byte each per proof; a proof with a status continues on stand-in values and the host ignores its product.
+//
+// Checked batches put k_nested_point_check in front: one lane per proof point (encoding, curve, [r] P = O) and per proof's inputs, no
+// LDS and no barrier, so a lane leaves at its first failure.  It writes one code per element; a proof with any code set is REFUSED:
+// k_nested_prep_checked (in k_nested_prep's place) converts none of its limbs and gives it the stand-ins of an off-curve proof, and its
+// status byte comes from the codes alone.  The unchecked route launches what it always launched.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -68,6 +73,48 @@ __global__ void __launch_bounds__(64) k_nested_prep(const uint64_t* __restrict__
   const Fr2 bx{fp_from_abi<FrParams>(pr + 12), fp_from_abi<FrParams>(pr + 18)}, by{fp_from_abi<FrParams>(pr + 24), fp_from_abi<FrParams>(pr + 30)};
   if (!nested_g2_on_curve(bx, by, consts[12])) { status[i] = NESTED_OFF_CURVE; return; }
   if (!nested_g1_on_curve(cx, cy)) { status[i] = NESTED_OFF_CURVE; return; }
+  status[i] = g2_lines_lane(bx, by, lines + i * NESTED_LINES) ? 0 : NESTED_DEGENERATE;
+}
+
+// ---- checked batches: encoding, curve and order of every proof point, one lane per point (pairing_bls.cuh nested_point_check), and
+// the inputs, one lane per proof.  No LDS, no barrier, no atomics; a lane leaves at its first failure.  Lanes [0, count) take the B
+// points, [count, 3 count) the A and C points (proof (t - count) / 2), [3 count, 4 count) the inputs: a wave holds one kind of point
+// but for the two at the seams, so it runs the Fr2 body or the Fr body and not both in turn.  codes: four bytes per proof (A, B, C,
+// inputs).  consts[12] is -1/5.
+__global__ void __launch_bounds__(64) k_nested_point_check(const uint64_t* __restrict__ proofs, const uint64_t* __restrict__ inputs, size_t n_inputs,
+                                                           size_t count, const Fr* __restrict__ consts, uint8_t* __restrict__ codes) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 4 * count) return;
+  if (t < count) {
+    codes[t * 4 + 1] = (uint8_t)nested_point_check(proofs + t * 48 + 12, true, consts[12]);
+  } else if (t < 3 * count) {
+    const size_t j = (t - count) >> 1;
+    const bool c = ((t - count) & 1) != 0;
+    codes[j * 4 + (c ? 2 : 0)] = (uint8_t)nested_point_check(proofs + j * 48 + (c ? 36 : 0), false, consts[12]);
+  } else {
+    const size_t j = t - 3 * count;
+    codes[j * 4 + 3] = (uint8_t)nested_inputs_check(inputs + j * n_inputs * 6, n_inputs);
+  }
+}
+
+// ---- k_nested_prep behind k_nested_point_check: a proof with a code set is REFUSED - none of its limbs is converted, its G1 slots get
+// the key's alpha (a valid point) and its status NESTED_OFF_CURVE, which makes the Miller loop read the stand-in lines for its B.  The
+// others passed the curve checks already: device form and the lines of B.
+__global__ void __launch_bounds__(64) k_nested_prep_checked(const uint64_t* __restrict__ proofs, size_t count, const uint32_t* __restrict__ codes,
+                                                            const Fr* __restrict__ standin /* x, y */, Fr* __restrict__ g1, NestedLine* __restrict__ lines,
+                                                            uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  if (codes[i] != 0) {
+    g1[i * 6 + 0] = standin[0]; g1[i * 6 + 1] = standin[1];
+    g1[i * 6 + 4] = standin[0]; g1[i * 6 + 5] = standin[1];
+    status[i] = NESTED_OFF_CURVE;
+    return;
+  }
+  const uint64_t* pr = proofs + i * 48;
+  g1[i * 6 + 0] = fp_from_abi<FrParams>(pr); g1[i * 6 + 1] = fp_from_abi<FrParams>(pr + 6);
+  g1[i * 6 + 4] = fp_from_abi<FrParams>(pr + 36); g1[i * 6 + 5] = fp_from_abi<FrParams>(pr + 42);
+  const Fr2 bx{fp_from_abi<FrParams>(pr + 12), fp_from_abi<FrParams>(pr + 18)}, by{fp_from_abi<FrParams>(pr + 24), fp_from_abi<FrParams>(pr + 30)};
   status[i] = g2_lines_lane(bx, by, lines + i * NESTED_LINES) ? 0 : NESTED_DEGENERATE;
 }
 
@@ -195,13 +242,16 @@ struct NestedCtx {
   Fr *d_g1 = nullptr, *d_f = nullptr;
   NestedLine* d_lines = nullptr;
   uint8_t* d_status = nullptr;      // cap x 4: per proof of a chunk of m at [0, m) and [m, 2 m) (prep, accumulator); per G2 point (products)
+  uint8_t* d_codes = nullptr;       // checked batches: four codes per proof (k_nested_point_check), read as one word per proof behind it
+  size_t codes_cap = 0;
   std::vector<uint64_t> h_gt;
-  std::vector<uint8_t> h_status;
+  std::vector<uint8_t> h_status, h_codes;
 };
 
 static void nctx_release_work(NestedCtx* c) {
-  for (void* p : {(void*)c->d_in1, (void*)c->d_in2, (void*)c->d_gt, (void*)c->d_g1, (void*)c->d_f, (void*)c->d_lines, (void*)c->d_status}) if (p) (void)hipFree(p);
-  c->d_in1 = c->d_in2 = c->d_gt = nullptr; c->d_g1 = c->d_f = nullptr; c->d_lines = nullptr; c->d_status = nullptr; c->cap = 0;
+  for (void* p : {(void*)c->d_in1, (void*)c->d_in2, (void*)c->d_gt, (void*)c->d_g1, (void*)c->d_f, (void*)c->d_lines, (void*)c->d_status, (void*)c->d_codes})
+    if (p) (void)hipFree(p);
+  c->d_in1 = c->d_in2 = c->d_gt = nullptr; c->d_g1 = c->d_f = nullptr; c->d_lines = nullptr; c->d_status = c->d_codes = nullptr; c->cap = c->codes_cap = 0;
 }
 
 // work space for `count` products of four pairs (a proof is one): 4 G2 points of 24 limbs or a proof's 48; 16 inputs of 6 limbs at most
@@ -216,6 +266,16 @@ static int nctx_reserve(NestedCtx* c, size_t count, char* errbuf, size_t errlen)
   NEST_HIP(hipMalloc(&c->d_lines, count * 4 * NESTED_LINES * sizeof(NestedLine)));
   NEST_HIP(hipMalloc(&c->d_status, count * 4));
   c->cap = count;
+  return ZKHIP_OK;
+}
+
+// the codes of `count` proofs: only a checked batch asks for them
+static int nctx_reserve_codes(NestedCtx* c, size_t count, char* errbuf, size_t errlen) {
+  if (count <= c->codes_cap) return ZKHIP_OK;
+  if (c->d_codes) (void)hipFree(c->d_codes);
+  c->d_codes = nullptr; c->codes_cap = 0;
+  NEST_HIP(hipMalloc(&c->d_codes, count * 4));
+  c->codes_cap = count;
   return ZKHIP_OK;
 }
 
@@ -309,8 +369,11 @@ int nested_products(NestedCtx* c, const uint64_t* g1, const uint64_t* g2, int pa
   return ZKHIP_OK;
 }
 
-int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, uint8_t* ok, uint8_t* status, char* errbuf,
-                        size_t errlen) {
+// checked: k_nested_point_check runs on the staged chunk in front, k_nested_prep_checked takes k_nested_prep's place, and ok[i] is the
+// status byte of zkhip.h; a refused proof has status[i] = 0 (it is decided: nothing of it goes to the host).  Unchecked: the launches
+// and results of before.
+int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, uint8_t* status,
+                        char* errbuf, size_t errlen) {
   if (!c->has_key) {
     if (errbuf) snprintf(errbuf, errlen, "nested pairing: a context without a key");
     return ZKHIP_ERR_STATE;
@@ -325,7 +388,17 @@ int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* pr
     if (rc != ZKHIP_OK) return rc;
     NEST_HIP(hipMemcpyAsync(c->d_in1, proofs + lo * 48, m * 48 * 8, hipMemcpyHostToDevice, c->st));
     if (ni) NEST_HIP(hipMemcpyAsync(c->d_in2, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
-    hipLaunchKernelGGL(k_nested_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1, m, c->d_fr, c->d_g1, c->d_lines, c->d_status);
+    if (checked) {
+      const int rc1 = nctx_reserve_codes(c, m, errbuf, errlen);
+      if (rc1 != ZKHIP_OK) return rc1;
+      hipLaunchKernelGGL(k_nested_point_check, dim3(blocks_for(4 * m, 64)), dim3(64), 0, c->st, c->d_in1, c->d_in2, ni, m, c->d_fr, c->d_codes);
+      hipLaunchKernelGGL(k_nested_prep_checked, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1, m, reinterpret_cast<const uint32_t*>(c->d_codes),
+                         c->d_fr + NK_ALPHA, c->d_g1, c->d_lines, c->d_status);
+      c->h_codes.resize(m * 4);
+      NEST_HIP(hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));     // (nested_run synchronises)
+    } else {
+      hipLaunchKernelGGL(k_nested_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1, m, c->d_fr, c->d_g1, c->d_lines, c->d_status);
+    }
     hipLaunchKernelGGL(k_nested_acc, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in2, ni, m, c->d_fr + NK_ABC0, c->d_fr + NK_CHAIN, c->d_g1,
                        c->d_status + m);
     NestedMillerArgs args = {};
@@ -341,8 +414,15 @@ int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* pr
     for (size_t j = 0; j < m; j++) {
       const uint8_t prep = c->h_status[j];
       const uint8_t s = (prep & NESTED_OFF_CURVE) ? NESTED_OFF_CURVE : (uint8_t)(prep | c->h_status[m + j]);
-      status[lo + j] = s;
-      ok[lo + j] = (s == 0 && memcmp(&c->h_gt[j * 72], one, sizeof one) == 0) ? 1 : 0;
+      const bool is_one = memcmp(&c->h_gt[j * 72], one, sizeof one) == 0;
+      if (!checked) {
+        status[lo + j] = s;
+        ok[lo + j] = (s == 0 && is_one) ? 1 : 0;
+        continue;
+      }
+      const uint8_t refused = verify_refusal(&c->h_codes[j * 4]);
+      status[lo + j] = refused ? 0 : s;
+      ok[lo + j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
     }
   }
   return ZKHIP_OK;

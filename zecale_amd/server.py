@@ -272,8 +272,9 @@ class GpuProver:
 
     def __init__(self, keypair_file=None, device=0, gpu_slots=32, witness_workers=10, gpu_witness=False, devices=None, hybrid_witness=False,
                  screen_nested=False):
-        """screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier) before a batch is popped, so
-        that an invalid one costs no slot of a wrapping proof (`screen`; off: the service never asks).
+        """screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier, the CHECKED route: every point's
+        encoding, curve and order, every input's range) before a batch is popped, so that an invalid or malformed one costs no slot of
+        a wrapping proof (`screen_status` / `screen`; off: the service never asks).
         devices: the GPUs of the node this ONE server process drives (the reference server is one process that owns its prover:
         aggregator_server.cpp:106-118, 390-416) - a resident copy of the key and a streaming pipeline on each, behind a dispatcher
         (zkhip_dispatcher_*); an index may repeat (two contexts on one GPU).  None / one entry: that GPU alone (`device`)."""
@@ -320,9 +321,15 @@ class GpuProver:
     def register_application(self, nested_vk_limbs):
         """RegisterApplication's part in the prover (aggregator_server.cpp:170-235 stores the key): the streaming prover computes the
         key's constants now (zkhip_aggregator_app: the key's share of every assignment and of four of the five MSMs), so that the
-        application's first batch does not pay for them.  A degenerate key gets no handle and is proved by the plain path."""
+        application's first batch does not pay for them.  A degenerate key gets no handle and is proved by the plain path.  With
+        screen_nested, a key that fails the point checks (encoding, curve, order r) is not registered: False, as for a key off its curve."""
         if self.screen_nested:
-            self._screen_handle(nested_vk_limbs)
+            try:
+                self._screen_handle(nested_vk_limbs)
+            except self.zk.ZkhipError as e:
+                if e.code != -1:
+                    raise
+                return False
         try:
             self.pipe.register_app(nested_vk_limbs)
             return True
@@ -330,27 +337,34 @@ class GpuProver:
             return False
 
     def _screen_handle(self, nested_vk_limbs):
-        """The application's NestedVerifier and the lock that keeps one batch in flight on it; (None, lock) for a key the handle
-        refuses (its own chains are degenerate): such a key keeps the host route."""
+        """The application's checked NestedVerifier and the lock that keeps one batch in flight on it; (None, lock) for a key the
+        handle refuses because its own chains or line schedules are degenerate: such a key keeps the host route.  A key that fails
+        the point checks raises (ZKHIP_ERR_ARG, "verification key refused: <element>: <code>")."""
         key = np.ascontiguousarray(nested_vk_limbs, dtype=np.uint64).tobytes()
         with self._screen_mu:
             if key not in self._screens:
                 try:
-                    v = self.zk.NestedVerifier(nested_vk_limbs, NUM_INPUTS_PER_NESTED_PROOF)
+                    v = self.zk.NestedVerifier(nested_vk_limbs, NUM_INPUTS_PER_NESTED_PROOF, checked=True)
                 except self.zk.ZkhipError as e:
-                    if e.code != -1:                                             # only ZKHIP_ERR_ARG is a property of the key
+                    if e.code != -1 or "verification key refused" in str(e):     # only ZKHIP_ERR_ARG is a property of the key
                         raise
                     v = None
                 self._screens[key] = (v, threading.Lock())
             return self._screens[key]
 
-    def screen(self, nested_vk_limbs, proofs, inputs):
-        """One verdict per nested proof (proofs: n x 48 limbs, inputs: n x k x 6), all of them in ONE batch on the GPU."""
+    def screen_status(self, nested_vk_limbs, proofs, inputs):
+        """One status byte per nested proof (proofs: n x 48 limbs, inputs: n x k x 6; include/zkhip.h ZKHIP_VERIFY_*: 0 accepted, 1 the
+        pairing rejects it, else the refusal code with the mask of the failing elements), all of them in ONE checked batch on the GPU."""
         v, lock = self._screen_handle(nested_vk_limbs)
         if v is None:
-            return [bool(self.zk.bls12_377_groth16_verify(nested_vk_limbs, i, p)) for p, i in zip(proofs, inputs)]
+            return [int(self.zk.bls12_377_groth16_verify_checked(nested_vk_limbs, i, p)) for p, i in zip(proofs, inputs)]
         with lock:
-            return [bool(b) for b in v.verify_batch(np.array(inputs), np.array(proofs))]
+            codes, masks = v.verify_batch_checked(np.array(inputs), np.array(proofs))
+        return [int(c | m) for c, m in zip(codes, masks)]
+
+    def screen(self, nested_vk_limbs, proofs, inputs):
+        """One verdict per nested proof: screen_status's byte is zero."""
+        return [s == 0 for s in self.screen_status(nested_vk_limbs, proofs, inputs)]
 
     def check_nested_proof(self, nested_vk_limbs, proof_limbs):
         """Well-formedness of ONE nested proof at submission time (libsnark's proof.is_well_formed(): every point on its curve).
@@ -385,6 +399,7 @@ class AggregatorService:
         self.pools = {}
         self.mu = threading.Lock()
         self.screen_dropped = 0          # nested transactions a prover's `screen` refused (never proved, kept in the pool's `screen_refused`)
+        self.screen_malformed = 0        # ... of them, those a prover's `screen_status` gave a code >= 2: not a wrong statement but a malformed proof
 
     # --- RPCs (aggregator_server.cpp:130-348) ---
     def GetConfiguration(self, request, context):
@@ -446,7 +461,7 @@ class AggregatorService:
     def GenerateAggregatedTransaction(self, request, context):
         def run():
             name = request.application_name
-            screen = getattr(self.prover, "screen", None) if getattr(self.prover, "screen_nested", True) else None
+            screen = (getattr(self.prover, "screen_status", None) or getattr(self.prover, "screen", None)) if getattr(self.prover, "screen_nested", True) else None
             def pop():
                 with self.mu:
                     pool = self._pool(name)
@@ -488,9 +503,10 @@ class AggregatorService:
 
     # --- helpers ---
     def _screen(self, name, screen):
-        """Every queued transaction of the application that no screening has passed yet goes through the prover's `screen` in ONE
-        call, outside the lock (submissions go on meanwhile).  What passes goes back with its fee and arrival order and is never
-        screened again; what fails is set aside and counted.  If the screening itself fails, all of them go back unmarked."""
+        """Every queued transaction of the application that no screening has passed yet goes through the prover's `screen_status`
+        (status bytes; where the prover has none, `screen`: verdicts) in ONE call, outside the lock (submissions go on meanwhile).
+        What passes goes back with its fee and arrival order and is never screened again; what fails is set aside - with its status
+        byte where there is one - and counted.  If the screening itself fails, all of them go back unmarked."""
         with self.mu:
             pool = self._pool(name)
             taken = pool.take_unscreened()
@@ -498,7 +514,13 @@ class AggregatorService:
         if not taken:
             return
         try:
-            verdicts = list(screen(vk_limbs, [e[2]["proof"] for e in taken], [e[2]["inputs"] for e in taken]))
+            status_of = getattr(self.prover, "screen_status", None)
+            statuses = None
+            if status_of is not None:
+                statuses = [int(s) for s in status_of(vk_limbs, [e[2]["proof"] for e in taken], [e[2]["inputs"] for e in taken])]
+                verdicts = [s == 0 for s in statuses]
+            else:
+                verdicts = list(screen(vk_limbs, [e[2]["proof"] for e in taken], [e[2]["inputs"] for e in taken]))
             if len(verdicts) != len(taken):
                 raise RuntimeError("screen returned %d verdicts for %d proofs" % (len(verdicts), len(taken)))
         except Exception:
@@ -511,6 +533,11 @@ class AggregatorService:
                 e[2]["screened"] = True
             pool.restore(good)
             bad = [e[2] for e, ok in zip(taken, verdicts) if not ok]
+            if statuses is not None:
+                for e, st in zip(taken, statuses):
+                    if st:
+                        e[2]["screen_status"] = st
+                self.screen_malformed += sum(1 for st in statuses if (st & 0x0F) >= 2)
             pool.screen_refused = getattr(pool, "screen_refused", []) + bad
             self.screen_dropped += len(bad)
 

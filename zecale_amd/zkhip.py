@@ -43,6 +43,7 @@ EXPORTS = [
     "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
     "zkhip_nested_verifier_new", "zkhip_nested_verifier_num_inputs", "zkhip_nested_verifier_verify_batch", "zkhip_nested_verifier_last_fallbacks",
     "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
+    "zkhip_nested_verifier_new_checked", "zkhip_nested_verifier_verify_batch_checked", "zkhip_bls12_377_point_check", "zkhip_bls12_377_groth16_verify_checked",
     "zkhip_internal_ntt_packed", "zkhip_internal_ntt_set_one_each_max",
 ]
 
@@ -218,6 +219,10 @@ def load():
     lib.zkhip_nested_verifier_verify_batch.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
     lib.zkhip_nested_verifier_last_fallbacks.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
     lib.zkhip_nested_verifier_free.argtypes = [ctypes.c_void_p]
+    lib.zkhip_nested_verifier_new_checked.argtypes = [c_u64p, ctypes.c_size_t, vpp]
+    lib.zkhip_nested_verifier_verify_batch_checked.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.zkhip_bls12_377_point_check.argtypes = [c_u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.zkhip_bls12_377_groth16_verify_checked.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p, c_u64p, ctypes.c_void_p]
     lib.zkhip_internal_fq12_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
     lib.zkhip_internal_nested_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
     _lib = lib
@@ -804,6 +809,28 @@ def bls12_377_groth16_verify(nested_vk, inputs, proof):
     return bool(ok.value)
 
 
+def bls12_377_point_check(point, g2):
+    """Host code: 0, VERIFY_ENCODING, VERIFY_OFF_CURVE or VERIFY_NOT_ORDER_R for one nested point: 12 limbs (x | y), or with g2 24
+    (x.c0 | x.c1 | y.c0 | y.c1).  The nested format has no point at infinity: all zero is VERIFY_OFF_CURVE."""
+    pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(24 if g2 else 12)
+    code = ctypes.c_int(-1)
+    _check(load().zkhip_bls12_377_point_check(_p(pt), 1 if g2 else 0, ctypes.byref(code)))
+    return code.value
+
+
+def bls12_377_groth16_verify_checked(nested_vk, inputs, proof):
+    """bls12_377_groth16_verify behind the checks of the checked nested batch verifier, on the host: returns the proof's status byte
+    (code in the low nibble, mask of the failing elements in the high one), the byte NestedVerifier.verify_batch_checked gives.  A key
+    that fails the point checks raises (ZKHIP_ERR_ARG, the message names the element and the code)."""
+    c = lambda a: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+    vk, pr, inp = c(nested_vk), c(proof), c(inputs).reshape(-1, 6)
+    assert vk.size == 60 + 12 * (inp.shape[0] + 1) and pr.size == 48
+    st = np.zeros(1, dtype=np.uint8)
+    _check(load().zkhip_bls12_377_groth16_verify_checked(_p(vk[:12]), _p(vk[12:36]), _p(vk[36:60]), _p(vk[60:]), _p(inp), inp.shape[0],
+                                                         _p(pr[:12]), _p(pr[12:36]), _p(pr[36:]), st.ctypes.data))
+    return int(st[0])
+
+
 # the nested batch verifier's kernels (zecale_amd/csrc/pairing_bls.cuh / pairing_bls.hip): a verification owns sixteen lanes, so one
 # wave holds NESTED_VERIFIER_GROUP of them and one 128-thread workgroup NESTED_VERIFIER_WORKGROUP
 NESTED_VERIFIER_GROUP = 4
@@ -813,14 +840,21 @@ NESTED_VERIFIER_WORKGROUP = 8
 class NestedVerifier:
     """Nested (BLS12-377) Groth16 verification in batches on the GPU (zkhip_nested_verifier): the verdicts of bls12_377_groth16_verify
     from gfx950 kernels.  nested_vk: 60 + 12 (k + 1) limbs (alpha | beta | delta | ABC), k = inputs_per_proof.  The key is checked on
-    the host when the handle is made (a refused key raises, the message names the element).  Every coordinate and input must be fully
-    reduced.  One batch in flight per handle; handles run side by side, one host thread each."""
+    the host when the handle is made (a refused key raises, the message names the element).  One batch in flight per handle; handles
+    run side by side, one host thread each.
+    verify_batch tests curve membership only: every coordinate and input must be fully reduced, and no point is tested for order r -
+    it is for proofs the caller made.  For anybody else's proofs make the handle with checked=True: the key's points are validated on
+    the host first (encoding, curve, order; a key that fails raises, the message names the element and the code), and
+    verify_batch_checked validates every proof point and input on the device before the pairing and says per proof why it was
+    refused."""
 
-    def __init__(self, nested_vk, inputs_per_proof):
+    def __init__(self, nested_vk, inputs_per_proof, checked=False):
         vk = np.ascontiguousarray(nested_vk, dtype=np.uint64).reshape(-1)
         assert vk.size == 60 + 12 * (inputs_per_proof + 1)
         self.handle = ctypes.c_void_p()
-        _check(load().zkhip_nested_verifier_new(_p(vk), inputs_per_proof, ctypes.byref(self.handle)))
+        self.checked = bool(checked)
+        new = load().zkhip_nested_verifier_new_checked if checked else load().zkhip_nested_verifier_new
+        _check(new(_p(vk), inputs_per_proof, ctypes.byref(self.handle)))
         self.n_inputs = int(load().zkhip_nested_verifier_num_inputs(self.handle))
 
     def verify_batch(self, inputs, proofs):
@@ -830,6 +864,16 @@ class NestedVerifier:
         ok = np.zeros(pr.shape[0], dtype=np.uint8)
         _check(load().zkhip_nested_verifier_verify_batch(self.handle, _p(inp), _p(pr), pr.shape[0], ok.ctypes.data))
         return ok.astype(bool)
+
+    def verify_batch_checked(self, inputs, proofs):
+        """As verify_batch on a handle made with checked=True, every proof point and input validated first.  Returns (codes, masks),
+        uint8 arrays: codes[i] is VERIFY_ACCEPT, VERIFY_REJECT, or the first of VERIFY_ENCODING, VERIFY_OFF_CURVE, VERIFY_NOT_ORDER_R
+        that an element of proof i has; masks[i] the elements that have it (VERIFY_MASK_A | _B | _C | _INPUT, zero for ACCEPT and REJECT)."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 48)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        st = np.zeros(pr.shape[0], dtype=np.uint8)
+        _check(load().zkhip_nested_verifier_verify_batch_checked(self.handle, _p(inp), _p(pr), pr.shape[0], st.ctypes.data))
+        return st & np.uint8(0x0F), st & np.uint8(0xF0)
 
     def last_fallbacks(self):
         """How many proofs of the last batch the device handed to the host verifier (a degenerate chord-and-tangent step)."""
