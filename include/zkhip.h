@@ -380,6 +380,35 @@ int zkhip_groth16_verify_checked(const uint64_t vk_alpha_g1[24], const uint64_t 
                                  const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_affine[72],
                                  uint8_t* status);
 
+/* ---- combined batches: ONE random-combination check for a whole batch ------------------------------------------------------------
+ * zkhip_verifier_verify_batch answers "which of these proofs are valid?" and pays a full pairing product per proof.  The callers
+ * that verify in bulk mostly ask "are these ALL valid?".  For proofs (A_i, B_i, C_i) with inputs x_i under one key and independent
+ * non-zero 128-bit scalars rho_i the batch is accepted iff
+ *     prod_i t(rho_i A_i, B_i) * t(S_acc, -g2) * t(sigma alpha, -beta) * t(S_C, -delta) == 1,
+ *     sigma = sum_i rho_i (mod r),  S_acc = sigma ABC_0 + sum_j (sum_i rho_i x_ij mod r) ABC_j,  S_C = sum_i rho_i C_i:
+ * ONE Miller pair, two 128-bit scalar multiplications and a share of two reduction trees per proof on the device, the three shared
+ * pairs and the single final exponentiation once per batch on the host.  GT has prime order r, so WHEN EVERY POINT HAS ORDER r a batch
+ * with an invalid proof passes with probability about 2^-128 over the choice of the rho_i.
+ * PRECONDITIONS on an unchecked handle: those of zkhip_verifier_verify_batch - and they matter MORE here.  There a point outside the
+ * group of order r spoils the verdict of its own proof; here the argument for the whole batch rests on GT elements of order r: with a
+ * point of small order somebody can make an invalid proof whose error term has small order and is cancelled by the random scalar with
+ * noticeable probability, or by a second proof.  Proofs somebody else made go through a handle of zkhip_verifier_new_checked with
+ * `status` set.
+ * all_ok = 1 iff the check passes.  rho: count x 2 words (little endian, 128 bits each, none zero: ZKHIP_ERR_ARG), or NULL to draw
+ * them from the OS (getrandom; ZKHIP_ERR_STATE if that fails, there is no weaker generator behind it) - a caller-supplied rho is for
+ * tests and reproducible measurements only: scalars an adversary knows or can predict prove nothing.
+ * status: NULL, or count bytes on a handle of zkhip_verifier_new_checked: the point checks of zkhip_verifier_verify_batch_checked run
+ * in front, status[i] is that route's refusal byte (ENCODING / OFF_CURVE / NOT_ORDER_R with its mask) or 0; a refused proof is left
+ * out of the product and the sums and makes all_ok 0.  status != NULL on an unchecked handle: ZKHIP_ERR_STATE.
+ * count == 0: all_ok = 1.  A failed batch does not say which proof is at fault: zkhip_verifier_verify_batch does.
+ * zkhip_groth16_verify_all: the same check on the host alone (no device, no zkhip_init; the per-proof work on up to 16 threads), the
+ * route the device one is pinned on; like zkhip_groth16_verify it first fails a batch with a point off its curve. */
+int zkhip_verifier_verify_all(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                              const uint64_t* rho, int* all_ok, uint8_t* status);
+int zkhip_groth16_verify_all(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                             const uint64_t* vk_abc, size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs_affine,
+                             size_t count, const uint64_t* rho, int* all_ok);
+
 /* ---- the wrapping (aggregator) circuit: host code, no device needed ------------------------------- */
 /* Nested objects are over BLS12-377, whose base field is Fr of BW6-761: coordinates are 6-limb Montgomery
  * elements.  G1 affine = x | y (12 limbs); G2 affine = x.c0 | x.c1 | y.c0 | y.c1 (24 limbs), Fq2 = Fq[u]/(u^2+5).
@@ -700,6 +729,14 @@ int zkhip_internal_last_acc_path(int* out);
  * zkhip_groth16_verify (needs no device); route 1: the kernels of zkhip_verifier_verify_batch. */
 int zkhip_internal_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
 int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out);
+/* verify_all_value: the REDUCED GT value of zkhip_verifier_verify_all's combined product (6 x 12 ABI limbs; one iff the check passes)
+ * for the handle's key; rho is required.  route 0: the host code of zkhip_groth16_verify_all without its curve check; route 1: the
+ * device route.  On a handle of zkhip_verifier_new_checked both routes run the point checks first and leave a refused proof out.
+ * verify_all_finish_ms: the host's time in the last device-route call on this handle behind the last chunk's synchronisation (the
+ * shared pairs and the final exponentiation). */
+int zkhip_internal_verify_all_value(int route, zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                                    const uint64_t* rho, uint64_t out[72]);
+int zkhip_internal_verify_all_finish_ms(const zkhip_verifier* v, double* ms);
 /* Test hooks of the nested pairing kernels (no counterpart).
  * fq12_selftest: n independent operand sets through the per-lane bodies of pairing_bls.cuh inside a real kernel, sixteen lanes per
  * set: op 0 = a b, 1 = a^2, 2 = a (b_0 + b_1 w + b_3 w^3 + b_7 w^7 + b_9 w^9) (the sparse line product; b's other coefficients are

@@ -6,7 +6,13 @@ The checked route (Verifier(vk, checked=True).verify_batch_checked: every proof 
 the unchecked one on the same batches, no proof refused so that every point walks all 377 bits of r: unchecked, checked, three
 times over at every count, the median of each.  GATE 2: checked <= 1.25 x unchecked at 1,024 proofs.
 profiles/verify_checked.txt is a run with --out profiles/verify_checked.txt (profiles/verify_gpu.txt is the run before this column).
-Usage: python tools/verify_ab.py [--out FILE] [--stream N] [--gpu-slots K]"""
+--combined writes profiles/verify_combined.txt instead: ONE random-combination check per batch (Verifier.verify_all, scalars drawn from
+the OS) against the per-proof route (verify_batch) of this build and - with --parent-lib - of a library built from the parent commit,
+on all-valid batches of 1 .. 65,536 proofs, the routes taking turns in one run, medians of five; the host finish's share of the
+combined time; and the host route (groth16_verify_all, 16 threads) once per batch.  CONDITIONS: the per-proof route equals the parent's
+within the spread of its own repeats (no kernel of it changed); the combined batch at 16,384 proofs takes at most half the per-proof
+batch's time.
+Usage: python tools/verify_ab.py [--out FILE] [--stream N] [--gpu-slots K] [--combined [--parent-lib libzkhip.so]]"""
 import argparse
 import os
 import sys
@@ -23,6 +29,96 @@ ROUNDS = 3
 COUNTS = (1, 64, 1024, 16384)
 EXTRA = (16, 32, 128, 256)          # more points for the count at which the GPU overtakes the host
 BATCH = 256
+COMBINED_COUNTS = (1, 64, 1024, 16384, 65536)
+COMBINED_ROUNDS = 5
+COMBINED_GATE = 0.5                 # combined ms / per-proof ms at 16,384 proofs
+
+
+class ParentVerifier:
+    """zkhip_verifier_* of ANOTHER build of the library (the parent commit's), loaded beside this one: its per-proof route"""
+
+    def __init__(self, path, vk):
+        import ctypes
+        self.lib = ctypes.CDLL(path)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self.lib.zkhip_verifier_new.argtypes = [u64p, u64p, u64p, u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        self.lib.zkhip_verifier_verify_batch.argtypes = [ctypes.c_void_p, u64p, u64p, ctypes.c_size_t, ctypes.c_void_p]
+        self.lib.zkhip_verifier_free.argtypes = [ctypes.c_void_p]
+        self.p = lambda a: np.ascontiguousarray(a, dtype=np.uint64).ctypes.data_as(u64p)
+        assert self.lib.zkhip_init(0) == 0
+        self.handle = ctypes.c_void_p()
+        abc = np.ascontiguousarray(vk["ABC"], dtype=np.uint64).reshape(-1, 24)
+        assert self.lib.zkhip_verifier_new(self.p(vk["alpha"]), self.p(vk["beta"]), self.p(vk["delta"]), self.p(abc), abc.shape[0] - 1,
+                                           ctypes.byref(self.handle)) == 0
+
+    def verify_batch(self, inp, prf):
+        ok = np.zeros(prf.shape[0], dtype=np.uint8)
+        assert self.lib.zkhip_verifier_verify_batch(self.handle, self.p(inp), self.p(prf), prf.shape[0], ok.ctypes.data) == 0
+        return ok.astype(bool)
+
+    def free(self):
+        self.lib.zkhip_verifier_free(self.handle)
+
+
+def combined_table(say, zkhip, vk, pool, pool_in, parent_lib):
+    """the combined check against the per-proof route (and the parent build's), taking turns on the same all-valid batches"""
+    n_pool = len(pool)
+    ver = zkhip.Verifier(vk)
+    parent = ParentVerifier(parent_lib, vk) if parent_lib else None
+    finish = []
+
+    def combined(i, p):
+        ok = ver.verify_all(i, p)
+        finish.append(ver.last_finish_ms())
+        return [ok] * len(p)
+    routes = [("combined", combined), ("per-proof", lambda i, p: list(ver.verify_batch(i, p)))]
+    if parent:
+        routes.append(("parent", lambda i, p: list(parent.verify_batch(i, p))))
+    for _, fn in routes:
+        fn(pool_in[:1], pool[:1])                            # work space
+    say("%8s %-10s %10s %10s %10s %14s" % ("count", "route", "median ms", "min ms", "max ms", "verif./s"))
+    med_all, same = {}, True
+    for count in COMBINED_COUNTS:
+        idx = np.arange(count) % n_pool
+        inp, prf = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
+        for _, fn in routes:
+            fn(inp, prf)                                      # the work space of this size
+        ms = {name: [] for name, _ in routes}
+        del finish[:]
+        for _ in range(COMBINED_ROUNDS):
+            for name, fn in routes:
+                t = time.perf_counter()
+                ok = fn(inp, prf)
+                ms[name].append((time.perf_counter() - t) * 1e3)
+                assert all(ok) and len(ok) == count, "%s verdicts at count %d" % (name, count)
+        med = {name: sorted(v)[COMBINED_ROUNDS // 2] for name, v in ms.items()}
+        med_all[count] = med
+        for name, _ in routes:
+            say("%8d %-10s %10.2f %10.2f %10.2f %14.1f" % (count, name, med[name], min(ms[name]), max(ms[name]), count / med[name] * 1e3))
+        fin = sorted(finish)[len(finish) // 2]
+        t = time.perf_counter()
+        assert zkhip.groth16_verify_all(vk, inp, prf)
+        host_ms = (time.perf_counter() - t) * 1e3
+        line = "%8d combined / per-proof = %.3f; host finish %.1f ms = %.0f %% of the combined batch; host route on %d threads (one run): %.0f ms" % (
+            count, med["combined"] / med["per-proof"], fin, 100 * fin / med["combined"], HOST_THREADS, host_ms)
+        if parent:
+            spread = max(ms["per-proof"]) - min(ms["per-proof"])
+            agree = abs(med["per-proof"] - med["parent"]) <= spread
+            same = same and agree
+            line += "; per-proof - parent's = %+.2f ms, spread of the per-proof repeats %.2f ms: %s" % (med["per-proof"] - med["parent"], spread,
+                                                                                                       "within" if agree else "OUTSIDE")
+        say(line)
+    pays = [c for c in COMBINED_COUNTS if med_all[c]["combined"] < med_all[c]["per-proof"]]
+    say("the combined check is the cheaper one from count %s on (smallest measured count at which its batch is faster)" % (pays[0] if pays else "none measured"))
+    ratio = med_all[16384]["combined"] / med_all[16384]["per-proof"]
+    gate = ratio <= COMBINED_GATE
+    say("CONDITION speed (combined <= %.1f x per-proof at 16,384 proofs, medians of %d alternating runs): %s  (%.3f, %.1fx faster)"
+        % (COMBINED_GATE, COMBINED_ROUNDS, "met" if gate else "MISSED", ratio, 1 / ratio))
+    if parent:
+        say("CONDITION no regression (per-proof route within the spread of its own repeats of the parent build's, at every count): %s" % ("met" if same else "MISSED"))
+        parent.free()
+    ver.free()
+    return gate and same
 
 
 def main():
@@ -31,7 +127,11 @@ def main():
     ap.add_argument("--stream", type=int, default=2048, help="proofs per block of the stream measurement (0: skip)")
     ap.add_argument("--gpu-slots", type=int, default=24)
     ap.add_argument("--pool", type=int, default=16, help="distinct proofs (the batches repeat them; the last one gets a bumped input)")
+    ap.add_argument("--combined", action="store_true", help="the combined check against the per-proof route; writes profiles/verify_combined.txt")
+    ap.add_argument("--parent-lib", default=None, help="with --combined: a libzkhip.so built from the parent commit, for its per-proof route in the same turns")
     args = ap.parse_args()
+    if args.combined and args.out.endswith("verify_gpu.txt"):
+        args.out = os.path.join(os.path.dirname(args.out), "verify_combined.txt")
     import bench
     from zecale_amd import zkhip
     zkhip.init(0)
@@ -55,6 +155,14 @@ def main():
     prover.free()
     pool_in = np.tile(prim, (args.pool, 1, 1))
     pool_in[-1, 0, 0] ^= np.uint64(1)                       # one invalid statement in the pool
+    if args.combined:
+        say("# Groth16 verification, batch-2 wrapping key (%d primary inputs): one combined check per batch vs the per-proof route, all-valid batches" % n_in)
+        ok = combined_table(say, zkhip, vk, pool[:-1], pool_in[:-1], args.parent_lib)
+        crs.free(); kp.free(); agg.free()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return 0 if ok else 1
     say("# Groth16 verification, batch-2 wrapping key (%d primary inputs): GPU pairing kernels vs the host route on %d threads" % (n_in, HOST_THREADS))
 
     # ---- host route, 16 threads (ctypes releases the GIL)

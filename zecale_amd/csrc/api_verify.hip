@@ -29,6 +29,54 @@ static int verifier_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2,
   return ZKHIP_OK;
 }
 
+// y^2 = x^3 - 1 (G1) or x^3 + 4 (G2), both over Fq; the all-zero encoding of the point at infinity passes
+static bool on_curve_abi(const uint64_t* p, bool g2) {
+  using host::HFq;
+  const HFq x = HFq::from_limbs(p), y = HFq::from_limbs(p + 12);
+  if (x.is_zero() && y.is_zero()) return true;
+  const HFq rhs = x.sqr() * x + (g2 ? HFq::one().dbl().dbl() : HFq::one().neg());
+  return y.sqr() == rhs;
+}
+
+static void neg_point_abi(const uint64_t* p, uint64_t* o) {
+  using host::HFq;
+  memcpy(o, p, 96);
+  const HFq y = HFq::from_limbs(p + 12);
+  const bool inf = HFq::from_limbs(p).is_zero() && y.is_zero();
+  (inf ? y : y.neg()).to_limbs(o + 12);
+}
+
+// the scalars of a combined batch: the caller's (none zero), or count x 16 bytes from the OS into `own`
+static int combine_scalars(const uint64_t* rho, size_t count, std::vector<uint64_t>& own, const uint64_t** out) {
+  if (rho) {
+    for (size_t i = 0; i < count; i++) if ((rho[i * 2] | rho[i * 2 + 1]) == 0) return fail(ZKHIP_ERR_ARG, "a combination scalar is zero");
+    *out = rho;
+    return ZKHIP_OK;
+  }
+  own.resize(count * 2);
+  if (!host::draw_rho(own.data(), count)) return fail(ZKHIP_ERR_STATE, "getrandom failed: no scalars for the combination, and no weaker generator stands in");
+  *out = own.data();
+  return ZKHIP_OK;
+}
+
+// the combined check on the host alone: the reduced value.  skip: null, or the proofs left out.
+static void verify_all_host(const host::CombineKey& key, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho,
+                            const uint8_t* skip, uint64_t* value) {
+  using namespace host;
+  const unsigned hw = std::thread::hardware_concurrency();
+  CombineSums sums(key.n_inputs);
+  Fq6 product = Fq6::one();
+  HJac s_c = HJac::infinity();
+  combined_proofs_host(key.n_inputs, inputs, proofs, count, rho, skip, hw > 16 ? 16 : hw, product, s_c, sums);
+  fq6_to_limbs(combined_value(key, sums, s_c, product), value);
+}
+
+static bool value_is_one(const uint64_t* value) {
+  uint64_t one[72] = {0};
+  host::HFq::one().to_limbs(one);
+  return memcmp(value, one, sizeof one) == 0;
+}
+
 #pragma GCC visibility pop
 
 extern "C" {
@@ -42,13 +90,7 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
   auto aff = [](const uint64_t* p) { return HJac::from_affine(HFq::from_limbs(p), HFq::from_limbs(p + 12)); };
   // well-formedness first (libsnark: proof.is_well_formed()): G1 is y^2 = x^3 - 1, G2 is y^2 = x^3 + 4, both over Fq;
   // the all-zero encoding of the point at infinity passes.  An off-curve point would put the pairing in an invalid-curve setting.
-  auto on_curve = [](const uint64_t* p, bool g2) {
-    HFq x = HFq::from_limbs(p), y = HFq::from_limbs(p + 12);
-    if (x.is_zero() && y.is_zero()) return true;
-    HFq four = HFq::one().dbl().dbl();
-    HFq rhs = x.sqr() * x + (g2 ? four : HFq::one().neg());
-    return y.sqr() == rhs;
-  };
+  auto on_curve = on_curve_abi;
   bool wf = on_curve(proof_affine, false) && on_curve(proof_affine + 24, true) && on_curve(proof_affine + 48, false) &&
             on_curve(vk_alpha_g1, false) && on_curve(vk_beta_g2, true) && on_curve(vk_delta_g2, true);
   for (size_t i = 0; i <= n_inputs && wf; i++) wf = on_curve(vk_abc + i * 24, false);
@@ -63,18 +105,37 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
   uint64_t acc_aff[24], neg_g2[24], neg_beta[24], neg_delta[24];
   HFq x, y;
   acc.to_affine(x, y); x.to_limbs(acc_aff); y.to_limbs(acc_aff + 12);
-  auto neg_pt = [](const uint64_t* p, uint64_t* o) {
-    memcpy(o, p, 96);
-    HFq yy = HFq::from_limbs(p + 12);
-    bool inf = HFq::from_limbs(p).is_zero() && yy.is_zero();
-    (inf ? yy : yy.neg()).to_limbs(o + 12);
-  };
+  auto neg_pt = neg_point_abi;
   uint64_t g2[24];
   memcpy(g2, FqParams::G2_GEN_X64, 96); memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
   neg_pt(g2, neg_g2); neg_pt(vk_beta_g2, neg_beta); neg_pt(vk_delta_g2, neg_delta);
   std::vector<const uint64_t*> p1 = {proof_affine, acc_aff, vk_alpha_g1, proof_affine + 48};
   std::vector<const uint64_t*> p2 = {proof_affine + 24, neg_g2, neg_beta, neg_delta};
   *ok = pairing_product_is_one(p1, p2) ? 1 : 0;
+  return ZKHIP_OK;
+}
+
+// ---- the combined check on the host alone (pairing_host.hpp): the route zkhip_verifier_verify_all is pinned on
+int zkhip_groth16_verify_all(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                             size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, const uint64_t* rho, int* all_ok) {
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !all_ok) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (count == 0) { *all_ok = 1; return ZKHIP_OK; }
+  if (!proofs_affine || (n_inputs && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  const int rc = combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  // well-formedness first, as zkhip_groth16_verify: a point off its curve fails the batch before any pairing arithmetic
+  bool wf = on_curve_abi(vk_alpha_g1, false) && on_curve_abi(vk_beta_g2, true) && on_curve_abi(vk_delta_g2, true);
+  for (size_t i = 0; i <= n_inputs && wf; i++) wf = on_curve_abi(vk_abc + i * 24, false);
+  for (size_t i = 0; i < count && wf; i++)
+    wf = on_curve_abi(proofs_affine + i * 72, false) && on_curve_abi(proofs_affine + i * 72 + 24, true) && on_curve_abi(proofs_affine + i * 72 + 48, false);
+  if (!wf) { *all_ok = 0; return ZKHIP_OK; }
+  uint64_t g2[24], neg_g2[24], neg_beta[24], neg_delta[24], value[72];
+  memcpy(g2, FqParams::G2_GEN_X64, 96); memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
+  neg_point_abi(g2, neg_g2); neg_point_abi(vk_beta_g2, neg_beta); neg_point_abi(vk_delta_g2, neg_delta);
+  const host::CombineKey key = {vk_alpha_g1, neg_g2, neg_beta, neg_delta, vk_abc, n_inputs};
+  verify_all_host(key, inputs, proofs_affine, count, rho, nullptr, value);
+  *all_ok = value_is_one(value) ? 1 : 0;
   return ZKHIP_OK;
 }
 
@@ -135,6 +196,24 @@ int zkhip_verifier_verify_batch_checked(zkhip_verifier* v, const uint64_t* input
   BIND(v);
   return pairing_verify_batch(v->ctx, inputs, proofs_affine, count, true, status, t_err, sizeof t_err);
 }
+int zkhip_verifier_verify_all(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, const uint64_t* rho,
+                              int* all_ok, uint8_t* status) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (!all_ok) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (status && !pairing_ctx_checked(v->ctx)) return fail(ZKHIP_ERR_STATE, "a per-proof status needs a handle of zkhip_verifier_new_checked");
+  if (count == 0) { *all_ok = 1; return ZKHIP_OK; }
+  if (!proofs_affine || (pairing_ctx_num_inputs(v->ctx) && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  int rc = combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  BIND(v);
+  uint64_t value[72];
+  if ((rc = pairing_verify_all(v->ctx, inputs, proofs_affine, count, rho, status != nullptr, status, value, t_err, sizeof t_err)) != ZKHIP_OK) return rc;
+  bool ok = value_is_one(value);
+  for (size_t i = 0; status && ok && i < count; i++) ok = status[i] == 0;      // a refused proof is left out of the product and fails the batch
+  *all_ok = ok ? 1 : 0;
+  return ZKHIP_OK;
+}
 void zkhip_verifier_free(zkhip_verifier* v) {
   if (!v) return;
   if (bind_dev(v->device) == ZKHIP_OK) pairing_ctx_free(v->ctx);
@@ -170,6 +249,41 @@ int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t
   rc = pairing_products(ctx, g1, g2, (int)pairs_per_product, count, out, t_err, sizeof t_err);
   pairing_ctx_free(ctx);
   return rc;
+}
+
+int zkhip_internal_verify_all_value(int route, zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                                    const uint64_t* rho, uint64_t out[72]) {
+  if (route != 0 && route != 1) return fail(ZKHIP_ERR_ARG, "route 0 (host) or 1 (GPU)");
+  if (!v || !out || (count && (!proofs_affine || !rho || (pairing_ctx_num_inputs(v->ctx) && !inputs)))) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  int rc = combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  const bool checked = pairing_ctx_checked(v->ctx);
+  if (route == 1 && count) {
+    BIND(v);
+    return pairing_verify_all(v->ctx, inputs, proofs_affine, count, rho, checked, nullptr, out, t_err, sizeof t_err);
+  }
+  host::CombineKey key;
+  key.n_inputs = pairing_ctx_num_inputs(v->ctx);
+  pairing_ctx_key(v->ctx, &key.alpha, &key.neg_g2, &key.neg_beta, &key.neg_delta, &key.abc);
+  std::vector<uint8_t> skip;
+  if (checked) {                                   // the checked route's refusals, on the host: such a proof is left out
+    skip.resize(count);
+    for (size_t i = 0; i < count; i++) {
+      const uint64_t* pr = proofs_affine + i * 72;
+      uint8_t e[4] = {(uint8_t)host::point_check_host(pr, false), (uint8_t)host::point_check_host(pr + 24, true),
+                      (uint8_t)host::point_check_host(pr + 48, false), ZKHIP_VERIFY_ACCEPT};
+      for (size_t j = 0; j < key.n_inputs; j++) if (host::HFr::geq_p(inputs + (i * key.n_inputs + j) * 6)) e[3] = ZKHIP_VERIFY_ENCODING;
+      skip[i] = verify_refusal(e);
+    }
+  }
+  verify_all_host(key, inputs, proofs_affine, count, rho, checked ? skip.data() : nullptr, out);
+  return ZKHIP_OK;
+}
+int zkhip_internal_verify_all_finish_ms(const zkhip_verifier* v, double* ms) {
+  if (!v || !ms) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *ms = pairing_ctx_last_finish_ms(v->ctx);
+  return ZKHIP_OK;
 }
 
 }  // extern "C"

@@ -20,12 +20,17 @@
 #include "../../include/zkhip.h"
 #include "ec.cuh"
 #include "fp29.cuh"
+#include "fp_inv.cuh"
 
 namespace zkhip {
 
 constexpr int PAIRING_GROUP = 8;        // lanes per verification (six coefficient lanes + two idle)
 constexpr int PAIRING_MAX_PAIRS = 4;    // pairs per product (one point step per lane, lanes 0 .. 3)
 constexpr int PAIRING_MILLER_STEPS = 376;   // bit length of r minus one
+// combined batches: values one strip of the reduction trees multiplies (k_gt_product) or adds (k_g1_sum).  Eight keeps a launch's
+// dependent chain at seven products, and a chunk of 16,384 values is down to one in five launches of microseconds each.
+constexpr int PAIRING_STRIP = 8;
+constexpr int PAIRING_RHO_BITS = 128;       // bit length of a combination scalar
 
 ZK_HD ZK_INL Fq fq_select(bool c, const Fq& a, const Fq& b) {
   Fq r;
@@ -203,6 +208,68 @@ ZK_HD ZK_INL uint8_t verify_refusal(const uint8_t e[4]) {
     if (mask) return (uint8_t)(code | mask);
   }
   return 0;
+}
+
+// ---- combined batches: prod_i t(rho_i A_i, B_i) and S_C = sum_i rho_i C_i for one random-combination check of a whole batch.
+
+// rho P by double-and-add over the 128 bits of rho (two 64-bit words, little endian), most significant first; the scalar is shifted
+// through its four 32-bit words as in k_acc_terms, so no word is picked by a run-time index.  p: 24 reduced ABI limbs (x | y), all zero
+// is the point at infinity and stays there.  The formulas never use the curve's b; the caller hands in points of G1.
+// Bounds: those of point_has_order_r - acc leaves xyzz_dbl with X [6], Y [4] and xyzz_madd with X [10], Y [4], within what both accept.
+ZK_HD ZK_INL XYZZ rho_scale(const uint64_t* p, const uint64_t* rho) {
+  uint64_t nz = 0;
+#pragma unroll
+  for (int k = 0; k < 24; k++) nz |= p[k];
+  const bool inf = nz == 0;
+  const Fq x = fp_from_abi<FqParams>(p), y = fp_from_abi<FqParams>(p + 12);     // [2]
+  uint32_t w[4] = {(uint32_t)rho[0], (uint32_t)(rho[0] >> 32), (uint32_t)rho[1], (uint32_t)(rho[1] >> 32)};
+  XYZZ acc = xyzz_infinity();
+#pragma unroll 1
+  for (int b = 0; b < PAIRING_RHO_BITS; b++) {
+    acc = xyzz_dbl(acc);                                                        // X [6], Y [4]
+    const bool bit = (w[3] >> 31) != 0;
+#pragma unroll
+    for (int j = 3; j >= 0; j--) w[j] = (w[j] << 1) | (j ? w[j - 1] >> 31 : 0u);
+    if (bit && !inf) xyzz_madd(acc, x, y);                                      // X [10], Y [4]
+  }
+  return acc;
+}
+
+// p (X [10], Y [4], ZZ and ZZZ [2]) as affine ABI limbs (x | y), all zero for the point at infinity: one inversion, as k_acc_sum.
+// Every operand of a product is [10] at most and every result [2], which fp_to_abi reduces.
+ZK_HD ZK_INL void xyzz_to_affine_abi(const XYZZ& p, uint64_t* o) {
+  if (xyzz_is_inf(p)) {
+    for (int k = 0; k < 24; k++) o[k] = 0;
+    return;
+  }
+  const Fq zi = fp_inv<FqParams>(fp_mul(p.ZZ, p.ZZZ));      // 1 / (ZZ ZZZ)
+  const Fq x = fp_mul(p.X, fp_mul(zi, p.ZZZ));              // X / ZZ
+  const Fq y = fp_mul(p.Y, fp_mul(zi, p.ZZ));               // Y / ZZZ
+  fp_to_abi<FqParams>(x, o);
+  fp_to_abi<FqParams>(y, o + 12);
+}
+
+// coefficient k of value i of the strip that starts at `first`: in[first + i] while that lies inside the `count` values, else of one
+// (a select on the clamped index: nothing past the array is read).  in: six coefficients [4] per value; one is [1].
+ZK_HD ZK_INL Fq gt_strip_operand(int k, const Fq* in, size_t first, int i, size_t count) {
+  const size_t idx = first + (size_t)i;
+  const bool inside = idx < count;
+  const Fq v = in[(inside ? idx : count - 1) * 6 + k];
+  return fq_select(inside, v, k == 0 ? fp_one<FqParams>() : fp_zero<FqParams>());
+}
+
+// the sum of the strip that starts at `first` (< count), at most PAIRING_STRIP values.  xyzz_add is complete - equal summands double,
+// P and -P give infinity, infinity on either side is skipped - and keeps X [10], Y [4] (xyzz_dbl: X [6], Y [4]) for summands within
+// the same bounds, which rho_scale's results and earlier sums are.
+ZK_HD ZK_INL XYZZ g1_strip_sum(const XYZZ* in, size_t first, size_t count) {
+  XYZZ acc = in[first];
+#pragma unroll 1
+  for (int i = 1; i < PAIRING_STRIP; i++) {
+    if (first + (size_t)i >= count) break;
+    const XYZZ t = in[first + (size_t)i];
+    xyzz_add(acc, t);                                       // X [10], Y [4]
+  }
+  return acc;
 }
 
 }  // namespace zkhip

@@ -27,6 +27,17 @@ int pairing_products(PairingCtx* c, const uint64_t* g1, const uint64_t* g2, int 
 // ZKHIP_ERR_STATE): every proof point is validated on the device first and ok[i] is the status byte of zkhip.h (ZKHIP_VERIFY_*).
 int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, char* errbuf,
                          size_t errlen);
+// ONE random-combination check of the whole batch (pairing_host.hpp states the equation): value = its reduced GT value, 72 ABI limbs,
+// one iff the batch passes.  rho: count x 2 words, none zero.  checked (a context whose key was checked, else ZKHIP_ERR_STATE):
+// k_point_check runs in front, a refused proof is left out of the product and the sums, and status (count bytes, or null) gets its
+// refusal byte, 0 for a proof nothing refuses.  status without checked: ZKHIP_ERR_STATE.
+int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                       uint8_t* status, uint64_t* value, char* errbuf, size_t errlen);
+// the host's time behind the last chunk of the last pairing_verify_all: the shared pairs and the final exponentiation
+double pairing_ctx_last_finish_ms(const PairingCtx* c);
+// the key of a verifier context in the form of pairing_host.hpp's CombineKey (G2 points negated), for the host route on a handle
+void pairing_ctx_key(const PairingCtx* c, const uint64_t** alpha, const uint64_t** neg_g2, const uint64_t** neg_beta, const uint64_t** neg_delta,
+                     const uint64_t** abc);
 // op 0: a b, 1: a^2, 2: a (b0 + b3 w^3 + b4 w^4) through the lane bodies of pairing.cuh; a, b, out: n x 72 ABI limbs
 int pairing_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen);
 

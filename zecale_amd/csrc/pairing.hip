@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
+#include <chrono>
 #include <vector>
 
 #include "ec.cuh"
@@ -21,11 +22,13 @@
 #include "host_field.hpp"
 #include "pairing.cuh"
 #include "pairing.h"
+#include "pairing_host.hpp"
 
 namespace zkhip {
 
 constexpr int PAIRING_BLOCK = 128;
 constexpr int PAIRING_WG = PAIRING_BLOCK / PAIRING_GROUP;      // verifications per workgroup
+// (PAIRING_STRIP, the strip of the combined batches' reduction trees, is pairing.cuh's: the lane bodies and the host shim read it too)
 constexpr size_t PAIRING_CHUNK = 16384;                        // verifications per launch sequence (bounds the work space)
 
 // ---- ABI points -> the constants of a Miller loop.  One lane per pair.
@@ -243,7 +246,76 @@ __global__ void __launch_bounds__(64) k_acc_sum(const XYZZ* __restrict__ terms, 
   fp_to_abi<FqParams>(y, o + 12);
 }
 
-#define PAIR_HIP(x)                                                                                   \
+// ---- combined batches (pairing_host.hpp states the equation): rho_i A_i and rho_i C_i, then two reduction trees.
+// One lane per (proof, element): lanes 0 .. count - 1 scale A, the next count scale C, so a wave does one kind of work.  A's lane
+// writes rho A as affine ABI limbs into pair i's G1 slot (all zero for a result at infinity: k_pair_prep then marks the pair as
+// contributing 1); C's lane keeps XYZZ for k_g1_sum.  g1: the staged chunk of pairing_verify_batch, A in the first and C in the fourth
+// of a proof's four slots.  A flagged proof (checked route) is the point at infinity in both places.
+__global__ void __launch_bounds__(64) k_rho_scale(const uint64_t* __restrict__ g1, const uint64_t* __restrict__ rho, size_t count,
+                                                  uint64_t* __restrict__ ra /* count x 24 */, XYZZ* __restrict__ rc,
+                                                  const uint32_t* __restrict__ flags /* per proof, or null */) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * count) return;
+  const size_t j = t < count ? t : t - count;
+  const bool is_c = t >= count;
+  if (flags && flags[j]) {
+    if (is_c) rc[j] = xyzz_infinity();
+    else for (int k = 0; k < 24; k++) ra[j * 24 + k] = 0;
+    return;
+  }
+  const XYZZ v = rho_scale(g1 + (j * 4 + (is_c ? 3 : 0)) * 24, rho + j * 2);
+  if (is_c) rc[j] = v;
+  else xyzz_to_affine_abi(v, ra + j * 24);
+}
+
+// `count` unreduced Miller values -> ceil(count / PAIRING_STRIP) products.  A group of eight lanes owns a strip: six coefficient lanes,
+// the running product and the next operand twice in LDS (a product reads one copy of each and writes the other), ONE barrier per
+// product - the cut of k_miller.  Groups past the last strip recompute it and store nothing, so every thread reaches every barrier; a
+// strip that runs past the end of the values multiplies by one.  abi (the launch that is left with one strip): the product as ABI
+// limbs.  in and out are different buffers.
+__global__ void __launch_bounds__(PAIRING_BLOCK) k_gt_product(const Fq* __restrict__ in, size_t count, Fq* __restrict__ out,
+                                                              uint64_t* __restrict__ abi) {
+  __shared__ Fq sF[PAIRING_WG][2][6];
+  __shared__ Fq sB[PAIRING_WG][2][6];
+  const int g = threadIdx.x / PAIRING_GROUP, k = threadIdx.x % PAIRING_GROUP;
+  const size_t strips = (count + PAIRING_STRIP - 1) / PAIRING_STRIP;
+  size_t strip = (size_t)blockIdx.x * PAIRING_WG + g;
+  const bool live = strip < strips;
+  if (!live) strip = strips - 1;
+  const size_t first = strip * PAIRING_STRIP;
+  if (k < 6) {
+    sF[g][0][k] = gt_strip_operand(k, in, first, 0, count);
+    sB[g][0][k] = gt_strip_operand(k, in, first, 1, count);
+  }
+  __syncthreads();
+  int cur = 0;
+#pragma unroll 1
+  for (int i = 1; i < PAIRING_STRIP; i++) {
+    if (k < 6) {
+      sF[g][cur ^ 1][k] = fq6_mul_coeff(k, sF[g][cur], sB[g][cur]);       // [4] x [4] -> [4]
+      if (i + 1 < PAIRING_STRIP) sB[g][cur ^ 1][k] = gt_strip_operand(k, in, first, i + 1, count);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (live && k < 6) {
+    if (abi) fp_to_abi<FqParams>(sF[g][cur][k], abi + k * 12);            // [4] -> canonical
+    else out[strip * 6 + k] = sF[g][cur][k];
+  }
+}
+
+// `count` XYZZ values -> ceil(count / PAIRING_STRIP) sums, one lane per strip (pairing.cuh g1_strip_sum).  abi (the launch that is left
+// with one strip): the sum as affine ABI limbs, all zero for infinity.  in and out are different buffers.
+__global__ void __launch_bounds__(64) k_g1_sum(const XYZZ* __restrict__ in, size_t count, XYZZ* __restrict__ out, uint64_t* __restrict__ abi) {
+  const size_t strips = (count + PAIRING_STRIP - 1) / PAIRING_STRIP;
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= strips) return;
+  const XYZZ acc = g1_strip_sum(in, s * PAIRING_STRIP, count);
+  if (abi) xyzz_to_affine_abi(acc, abi);
+  else out[s] = acc;
+}
+
+#define PAIR_HIP(x)                                                                                  \
   do {                                                                                                \
     hipError_t e_ = (x);                                                                              \
     if (e_ != hipSuccess) {                                                                           \
@@ -290,8 +362,16 @@ struct PairingCtx {
   XYZZ* d_terms = nullptr;
   size_t in_cap = 0;
   uint64_t alpha[24], neg_g2[24], neg_beta[24], neg_delta[24];
+  std::vector<uint64_t> abc;        // the key's ABC points, ABI limbs (the host finish of a combined batch)
   std::vector<uint64_t> h_g1, h_g2, h_gt;
   std::vector<uint8_t> h_codes;
+  // combined batches (pairing_verify_all)
+  size_t comb_cap = 0;
+  uint64_t *d_rho = nullptr, *d_ra = nullptr, *d_b = nullptr, *d_res = nullptr;   // scalars, rho A and B per pair, the chunk's product | sum
+  XYZZ *d_rc = nullptr, *d_rc2 = nullptr;                                         // rho C, and the other buffer of the sum tree
+  Fq* d_f2 = nullptr;                                                             // the other buffer of the product tree
+  std::vector<uint64_t> h_b;
+  double finish_ms = 0;
 };
 
 static void ctx_release_work(PairingCtx* c) {
@@ -313,15 +393,41 @@ static int ctx_reserve(PairingCtx* c, size_t count, char* errbuf, size_t errlen)
   return ZKHIP_OK;
 }
 
+static void ctx_release_comb(PairingCtx* c) {
+  for (void* p : {(void*)c->d_rho, (void*)c->d_ra, (void*)c->d_b, (void*)c->d_res, (void*)c->d_rc, (void*)c->d_rc2, (void*)c->d_f2}) if (p) (void)hipFree(p);
+  c->d_rho = c->d_ra = c->d_b = c->d_res = nullptr; c->d_rc = c->d_rc2 = nullptr; c->d_f2 = nullptr; c->comb_cap = 0;
+}
+
+static int ctx_reserve_comb(PairingCtx* c, size_t count, char* errbuf, size_t errlen) {
+  if (count <= c->comb_cap) return ZKHIP_OK;
+  ctx_release_comb(c);
+  const size_t strips = (count + PAIRING_STRIP - 1) / PAIRING_STRIP;
+  PAIR_HIP(hipMalloc(&c->d_rho, count * 16));
+  PAIR_HIP(hipMalloc(&c->d_ra, count * 192));
+  PAIR_HIP(hipMalloc(&c->d_b, count * 192));
+  PAIR_HIP(hipMalloc(&c->d_res, (72 + 24) * 8));
+  PAIR_HIP(hipMalloc(&c->d_rc, count * sizeof(XYZZ)));
+  PAIR_HIP(hipMalloc(&c->d_rc2, strips * sizeof(XYZZ)));
+  PAIR_HIP(hipMalloc(&c->d_f2, strips * 6 * sizeof(Fq)));
+  c->comb_cap = count;
+  return ZKHIP_OK;
+}
+
 void pairing_ctx_free(PairingCtx* c) {
   if (!c) return;
   ctx_release_work(c);
+  ctx_release_comb(c);
   for (void* p : {(void*)c->d_const, (void*)c->d_abc, (void*)c->d_inputs, (void*)c->d_terms}) if (p) (void)hipFree(p);
   if (c->st) (void)hipStreamDestroy(c->st);
   delete c;
 }
 
 size_t pairing_ctx_num_inputs(const PairingCtx* c) { return c ? c->n_inputs : 0; }
+double pairing_ctx_last_finish_ms(const PairingCtx* c) { return c ? c->finish_ms : 0; }
+void pairing_ctx_key(const PairingCtx* c, const uint64_t** alpha, const uint64_t** neg_g2, const uint64_t** neg_beta, const uint64_t** neg_delta,
+                     const uint64_t** abc) {
+  *alpha = c->alpha; *neg_g2 = c->neg_g2; *neg_beta = c->neg_beta; *neg_delta = c->neg_delta; *abc = c->abc.data();
+}
 bool pairing_ctx_checked(const PairingCtx* c) { return c && c->checked; }
 
 void pairing_key_refusal(size_t element, int code, char* buf, size_t len) {
@@ -388,6 +494,7 @@ static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* 
   c->has_key = true;
   c->n_inputs = n_inputs;
   memcpy(c->alpha, vk_alpha_g1, 192);
+  c->abc.assign(vk_abc, vk_abc + (n_inputs + 1) * 24);
   uint64_t g2[24];
   memcpy(g2, FqParams::G2_GEN_X64, 96);
   memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
@@ -504,6 +611,107 @@ int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* 
       ok[lo + j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
     }
   }
+  return ZKHIP_OK;
+}
+
+// One random-combination check of the whole batch.  Per chunk the device scales A and C by rho (k_rho_scale), runs the existing
+// Miller loop with ONE pair per proof on (rho_i A_i, B_i) and reduces the unreduced values to one product (k_gt_product) and the
+// rho_i C_i to one sum (k_g1_sum), relaunched until one value is left; the host multiplies and adds the chunks' results, forms the
+// sums in Fr while the device works (checked route: once the codes are back, over the proofs nothing refuses), and finishes with the
+// three shared pairs and ONE final exponentiation (pairing_host.hpp combined_value).
+int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                       uint8_t* status, uint64_t* value, char* errbuf, size_t errlen) {
+  using namespace host;
+  if ((checked || status) && !c->checked) {
+    if (errbuf) snprintf(errbuf, errlen, "a per-proof status needs a handle of zkhip_verifier_new_checked");
+    return ZKHIP_ERR_STATE;
+  }
+  const size_t ni = c->n_inputs;
+  CombineSums sums(ni);
+  Fq6 product = Fq6::one();
+  HJac s_c = HJac::infinity();
+  auto add_sums = [&](size_t lo, size_t m, const uint8_t* codes) {
+    for (size_t j = 0; j < m; j++)
+      if (!codes || !verify_refusal(codes + j * 4)) sums.add(rho + (lo + j) * 2, inputs + (lo + j) * ni * 6);
+  };
+  for (size_t lo = 0; lo < count; lo += PAIRING_CHUNK) {
+    const size_t m = count - lo < PAIRING_CHUNK ? count - lo : PAIRING_CHUNK;
+    int rc = ctx_reserve(c, m, errbuf, errlen);
+    if (rc == ZKHIP_OK) rc = ctx_reserve_comb(c, m, errbuf, errlen);
+    if (rc != ZKHIP_OK) return rc;
+    // the staged chunk has the layout of pairing_verify_batch (k_point_check reads it): A and C in the first and the fourth G1 slot
+    c->h_g1.resize(m * 96); c->h_b.resize(m * 24);
+    if (checked) c->h_g2.resize(m * 96);
+    for (size_t j = 0; j < m; j++) {
+      const uint64_t* pr = proofs + (lo + j) * 72;
+      memcpy(&c->h_g1[j * 96], pr, 192);
+      memcpy(&c->h_g1[j * 96 + 72], pr + 48, 192);
+      memcpy(&c->h_b[j * 24], pr + 24, 192);
+      if (checked) memcpy(&c->h_g2[j * 96], pr + 24, 192);
+    }
+    PAIR_HIP(hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
+    PAIR_HIP(hipMemcpyAsync(c->d_b, c->h_b.data(), m * 192, hipMemcpyHostToDevice, c->st));
+    PAIR_HIP(hipMemcpyAsync(c->d_rho, rho + lo * 2, m * 16, hipMemcpyHostToDevice, c->st));
+    const uint32_t* flags = nullptr;
+    if (checked) {
+      if (ni && m * ni > c->in_cap) {
+        if (c->d_inputs) (void)hipFree(c->d_inputs);
+        if (c->d_terms) (void)hipFree(c->d_terms);
+        c->d_inputs = nullptr; c->d_terms = nullptr; c->in_cap = 0;
+        PAIR_HIP(hipMalloc(&c->d_inputs, m * ni * 48));
+        PAIR_HIP(hipMalloc(&c->d_terms, m * ni * sizeof(XYZZ)));
+        c->in_cap = m * ni;
+      }
+      PAIR_HIP(hipMemcpyAsync(c->d_g2, c->h_g2.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
+      if (ni) PAIR_HIP(hipMemcpyAsync(c->d_inputs, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
+      c->h_codes.resize(m * 4);
+      hipLaunchKernelGGL(k_point_check, dim3(blocks_for(m * 3, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_inputs, ni, m * 3, 0, c->d_const,
+                         c->d_codes);
+      flags = reinterpret_cast<const uint32_t*>(c->d_codes);
+    }
+    hipLaunchKernelGGL(k_rho_scale, dim3(blocks_for(2 * m, 64)), dim3(64), 0, c->st, c->d_g1, c->d_rho, m, c->d_ra, c->d_rc, flags);
+    hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_ra, c->d_b, c->d_const + 72, m, c->d_pairs, c->d_inf, flags, 1);
+    hipLaunchKernelGGL(k_miller, dim3(blocks_for(m, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs, c->d_inf, 1, m, c->d_const, c->d_f);
+    {
+      const Fq* in = c->d_f;
+      Fq* out = c->d_f2;
+      for (size_t n = m;;) {
+        const size_t strips = (n + PAIRING_STRIP - 1) / PAIRING_STRIP;
+        hipLaunchKernelGGL(k_gt_product, dim3(blocks_for(strips, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, in, n, out,
+                           strips == 1 ? c->d_res : nullptr);
+        if (strips == 1) break;
+        n = strips;
+        Fq* t = const_cast<Fq*>(in); in = out; out = t;      // the values of the level before are dead: their buffer takes the next level
+      }
+    }
+    {
+      const XYZZ* in = c->d_rc;
+      XYZZ* out = c->d_rc2;
+      for (size_t n = m;;) {
+        const size_t strips = (n + PAIRING_STRIP - 1) / PAIRING_STRIP;
+        hipLaunchKernelGGL(k_g1_sum, dim3(blocks_for(strips, 64)), dim3(64), 0, c->st, in, n, out, strips == 1 ? c->d_res + 72 : nullptr);
+        if (strips == 1) break;
+        n = strips;
+        XYZZ* t = const_cast<XYZZ*>(in); in = out; out = t;
+      }
+    }
+    PAIR_HIP(hipGetLastError());
+    uint64_t res[72 + 24];
+    PAIR_HIP(hipMemcpyAsync(res, c->d_res, sizeof res, hipMemcpyDeviceToHost, c->st));
+    if (checked) PAIR_HIP(hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));
+    if (!checked) add_sums(lo, m, nullptr);
+    PAIR_HIP(hipStreamSynchronize(c->st));
+    if (checked) {
+      add_sums(lo, m, c->h_codes.data());
+      if (status) for (size_t j = 0; j < m; j++) status[lo + j] = verify_refusal(&c->h_codes[j * 4]);
+    }
+    product = product * fq6_from_limbs(res);
+    s_c = s_c.add(jac_from_limbs(res + 72));
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const CombineKey key = {c->alpha, c->neg_g2, c->neg_beta, c->neg_delta, c->abc.data(), ni};
+  fq6_to_limbs(combined_value(key, sums, s_c, product), value);
+  c->finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return ZKHIP_OK;
 }
 

@@ -8,6 +8,10 @@
 // Miller lines are scaled by Fq factors and vertical lines dropped (both die in the final exponentiation);
 // the four Miller loops share one accumulator (one Fq6 squaring per bit for the whole product).
 #pragma once
+#include <errno.h>
+#include <sys/random.h>
+
+#include <thread>
 #include <vector>
 
 #include "../../include/zkhip.h"
@@ -104,8 +108,8 @@ inline void miller_add(MillerPair& m, Fq6& f) {
   m.X = X3; m.Y = Y3; m.Z = D;
 }
 
-// prod_i t(P_i, Q_i), the reduced value.   points affine (x, y) in ABI limbs; infinity (all zero) contributes 1.
-inline Fq6 pairing_product_value(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
+// prod_i f_{r,P_i}(psi(Q_i)), the UNREDUCED Miller value.   points affine (x, y) in ABI limbs; infinity (all zero) contributes 1.
+inline Fq6 miller_product(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
   std::vector<MillerPair> ms;
   HFq quarter_neg = HFq::from_u64(4).inv().neg();    // -1/4
   for (size_t i = 0; i < g1.size(); i++) {
@@ -127,7 +131,107 @@ inline Fq6 pairing_product_value(const std::vector<const uint64_t*>& g1, const s
     if ((r[i / 64] >> (i % 64)) & 1)
       for (auto& m : ms) if (!m.done) miller_add(m, f);
   }
-  return f.pow_limbs(FqParams::FINAL_EXP, FqParams::FINAL_EXP_LIMBS);
+  return f;
+}
+
+// f^((q^6-1)/r)
+inline Fq6 final_exponentiation(const Fq6& f) { return f.pow_limbs(FqParams::FINAL_EXP, FqParams::FINAL_EXP_LIMBS); }
+
+// prod_i t(P_i, Q_i), the reduced value
+inline Fq6 pairing_product_value(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
+  return final_exponentiation(miller_product(g1, g2));
+}
+
+// ---- combined batches: ONE check for a whole batch of proofs (A_i, B_i, C_i), inputs x_i, under one key, with independent non-zero
+// 128-bit scalars rho_i:
+//     prod_i t(rho_i A_i, B_i) * t(S_acc, -g2) * t(sigma alpha, -beta) * t(S_C, -delta) == 1,
+//     sigma = sum rho_i,  S_acc = sigma ABC_0 + sum_j (sum_i rho_i x_ij) ABC_j,  S_C = sum rho_i C_i.
+// GT has prime order r: when every point has order r, a batch with an invalid proof passes with probability about 2^-128.
+// The per-proof pairs' Miller values come from the device (pairing.hip) or from combined_proofs_host below; the three shared pairs and
+// the single final exponentiation are combined_value, the same code behind both routes.
+
+struct CombineKey {      // ABI limbs; the G2 points already negated
+  const uint64_t *alpha, *neg_g2, *neg_beta, *neg_delta, *abc;
+  size_t n_inputs;
+};
+
+// sigma and the n_inputs sums of rho_i x_ij in Fr, proof after proof
+struct CombineSums {
+  HFr sigma;
+  std::vector<HFr> s;
+  explicit CombineSums(size_t n_inputs) : sigma(HFr::zero()), s(n_inputs, HFr::zero()) {}
+  void add(const uint64_t* rho /* 2 words */, const uint64_t* inputs /* n_inputs x 6 ABI limbs */) {
+    const uint64_t k[6] = {rho[0], rho[1], 0, 0, 0, 0};
+    const HFr r = HFr::from_canonical(k);
+    sigma = sigma + r;
+    for (size_t j = 0; j < s.size(); j++) s[j] = s[j] + r * HFr::from_limbs(inputs + j * 6);
+  }
+};
+
+// count x 16 bytes from the OS, each scalar redrawn while zero.  false: getrandom failed - there is no weaker generator behind it.
+inline bool draw_rho(uint64_t* rho, size_t count) {
+  for (size_t i = 0; i < count; i++) {
+    do {
+      size_t got = 0;
+      while (got < 16) {
+        const ssize_t n = getrandom(reinterpret_cast<char*>(rho + i * 2) + got, 16 - got, 0);
+        if (n < 0 && errno == EINTR) continue;
+        if (n <= 0) return false;
+        got += (size_t)n;
+      }
+    } while ((rho[i * 2] | rho[i * 2 + 1]) == 0);
+  }
+  return true;
+}
+
+inline Fq6 fq6_from_limbs(const uint64_t* p) { Fq6 r; for (int k = 0; k < 6; k++) r.c[k] = HFq::from_limbs(p + k * 12); return r; }
+inline void fq6_to_limbs(const Fq6& f, uint64_t* p) { for (int k = 0; k < 6; k++) f.c[k].to_limbs(p + k * 12); }
+inline HJac jac_from_limbs(const uint64_t* p) { return HJac::from_affine(HFq::from_limbs(p), HFq::from_limbs(p + 12)); }
+inline void jac_to_limbs(const HJac& P, uint64_t* o) { HFq x, y; P.to_affine(x, y); x.to_limbs(o); y.to_limbs(o + 12); }
+
+// the reduced value of the combined product: the three shared pairs' Miller value times `proofs_product` (the unreduced
+// prod_i f(rho_i A_i, B_i)), then ONE final exponentiation
+inline Fq6 combined_value(const CombineKey& key, const CombineSums& sums, const HJac& s_c, const Fq6& proofs_product) {
+  uint64_t k[6], pts[3][24];
+  sums.sigma.to_canonical(k);
+  HJac s_acc = jac_from_limbs(key.abc).mul_canonical(k, 6);
+  jac_to_limbs(jac_from_limbs(key.alpha).mul_canonical(k, 6), pts[1]);
+  for (size_t j = 0; j < key.n_inputs; j++) {
+    sums.s[j].to_canonical(k);
+    s_acc = s_acc.add(jac_from_limbs(key.abc + (j + 1) * 24).mul_canonical(k, 6));
+  }
+  jac_to_limbs(s_acc, pts[0]);
+  jac_to_limbs(s_c, pts[2]);
+  const Fq6 shared = miller_product({pts[0], pts[1], pts[2]}, {key.neg_g2, key.neg_beta, key.neg_delta});
+  return final_exponentiation(shared * proofs_product);
+}
+
+// the host route's share of the per-proof work: prod_i f(rho_i A_i, B_i) (unreduced), S_C, and the sums, over the proofs that `skip`
+// (null, or one byte per proof) does not leave out; the proofs are dealt to `threads` threads, each with its own partial results.
+inline void combined_proofs_host(size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho,
+                                 const uint8_t* skip, unsigned threads, Fq6& product, HJac& s_c, CombineSums& sums) {
+  if (threads < 1) threads = 1;
+  if (threads > count) threads = count ? (unsigned)count : 1;
+  std::vector<Fq6> part_f(threads, Fq6::one());
+  std::vector<HJac> part_c(threads, HJac::infinity());
+  auto work = [&](unsigned t) {
+    for (size_t i = t; i < count; i += threads) {
+      if (skip && skip[i]) continue;
+      const uint64_t* pr = proofs + i * 72;
+      uint64_t ra[24];
+      jac_to_limbs(jac_from_limbs(pr).mul_canonical(rho + i * 2, 2), ra);
+      part_f[t] = part_f[t] * miller_product({ra}, {pr + 24});
+      part_c[t] = part_c[t].add(jac_from_limbs(pr + 48).mul_canonical(rho + i * 2, 2));
+    }
+  };
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < threads; t++) pool.emplace_back(work, t);
+  work(0);
+  for (auto& th : pool) th.join();
+  product = Fq6::one();
+  s_c = HJac::infinity();
+  for (unsigned t = 0; t < threads; t++) { product = product * part_f[t]; s_c = s_c.add(part_c[t]); }
+  for (size_t i = 0; i < count; i++) if (!skip || !skip[i]) sums.add(rho + i * 2, inputs + i * n_inputs * 6);
 }
 
 // The checks of the checked verifier for one point (x | y, 24 ABI limbs), in their order: 0, or ZKHIP_VERIFY_ENCODING (a

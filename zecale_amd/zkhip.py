@@ -45,6 +45,7 @@ EXPORTS = [
     "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
     "zkhip_nested_verifier_new_checked", "zkhip_nested_verifier_verify_batch_checked", "zkhip_bls12_377_point_check", "zkhip_bls12_377_groth16_verify_checked",
     "zkhip_internal_ntt_packed", "zkhip_internal_ntt_set_one_each_max",
+    "zkhip_verifier_verify_all", "zkhip_groth16_verify_all", "zkhip_internal_verify_all_value", "zkhip_internal_verify_all_finish_ms",
 ]
 
 
@@ -211,6 +212,11 @@ def load():
     lib.zkhip_verifier_verify_batch_checked.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_void_p]
     lib.zkhip_bw6_761_point_check.argtypes = [c_u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.zkhip_groth16_verify_checked.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.c_void_p]
+    lib.zkhip_verifier_verify_all.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+    lib.zkhip_groth16_verify_all.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p, ctypes.c_size_t, c_u64p,
+                                             ctypes.POINTER(ctypes.c_int)]
+    lib.zkhip_internal_verify_all_value.argtypes = [ctypes.c_int, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p]
+    lib.zkhip_internal_verify_all_finish_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
     lib.zkhip_internal_fq6_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
     lib.zkhip_internal_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
     lib.zkhip_nested_verifier_new.argtypes = [c_u64p, ctypes.c_size_t, vpp]
@@ -726,10 +732,38 @@ def groth16_verify_checked(vk, inputs, proof):
     return int(st[0])
 
 
+def _rho_limbs(rho, count):
+    """None, or count combination scalars (ints below 2^128, or count x 2 words) -> count x 2 words, little endian"""
+    if rho is None:
+        return None
+    if len(rho) and isinstance(rho[0], int):
+        rho = [[r & (2 ** 64 - 1), r >> 64] for r in rho]
+    return np.ascontiguousarray(rho, dtype=np.uint64).reshape(count, 2)
+
+
+def groth16_verify_all(vk, inputs, proofs, rho=None):
+    """ONE random-combination check of a whole batch on the host (zkhip_groth16_verify_all; works without a GPU): True iff
+    prod_i t(rho_i A_i, B_i) t(S_acc, -g2) t(sigma alpha, -beta) t(S_C, -delta) is one.  vk as for groth16_verify; inputs:
+    count x n x 6 limbs; proofs: count x 72 limbs; rho: None (drawn from the OS) or count non-zero scalars below 2^128 - supplied
+    scalars are for tests and reproducible measurements only."""
+    c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+    abc = c(vk["ABC"]).reshape(-1, 24)
+    pr = c(proofs).reshape(-1, 72)
+    inp = c(inputs).reshape(pr.shape[0], abc.shape[0] - 1, 6)
+    rl = _rho_limbs(rho, pr.shape[0])
+    ok = ctypes.c_int(0)
+    _check(load().zkhip_groth16_verify_all(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), abc.shape[0] - 1, _p(inp), _p(pr),
+                                           pr.shape[0], None if rl is None else _p(rl), ctypes.byref(ok)))
+    return bool(ok.value)
+
+
 # the batch verifier's kernels (zecale_amd/csrc/pairing.cuh / pairing.hip): a verification owns eight lanes, so one wave holds
-# VERIFIER_GROUP of them and one 128-thread workgroup VERIFIER_WORKGROUP (tests size their batches around both)
+# VERIFIER_GROUP of them and one 128-thread workgroup VERIFIER_WORKGROUP (tests size their batches around both); the reduction trees
+# of a combined batch take VERIFIER_STRIP values per strip, and a batch runs in chunks of VERIFIER_CHUNK proofs
 VERIFIER_GROUP = 8
 VERIFIER_WORKGROUP = 16
+VERIFIER_STRIP = 8
+VERIFIER_CHUNK = 16384
 
 
 class Verifier:
@@ -769,10 +803,58 @@ class Verifier:
         _check(load().zkhip_verifier_verify_batch_checked(self.handle, _p(inp), _p(pr), pr.shape[0], st.ctypes.data))
         return st & np.uint8(0x0F), st & np.uint8(0xF0)
 
+    def verify_all(self, inputs, proofs, rho=None, status=False):
+        """ONE random-combination check of the whole batch (zkhip_verifier_verify_all): True iff every proof is valid, up to a
+        chance of about 2^-128 - PROVIDED every point has order r, which an unchecked handle does not check: it is for proofs the
+        caller made.  rho: None (drawn from the OS) or count non-zero scalars below 2^128, for tests and reproducible measurements
+        only.  status=True (a handle made with checked=True): every proof point is validated first, a refused proof is left out
+        and fails the batch; returns (verdict, status bytes: the refusal byte of verify_batch_checked per proof, or 0)."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        rl = _rho_limbs(rho, pr.shape[0])
+        st = np.zeros(max(pr.shape[0], 1), dtype=np.uint8) if status else None       # (never zero-length: its address says "status wanted")
+        ok = ctypes.c_int(0)
+        _check(load().zkhip_verifier_verify_all(self.handle, _p(inp), _p(pr), pr.shape[0], None if rl is None else _p(rl), ctypes.byref(ok),
+                                                None if st is None else st.ctypes.data))
+        return (bool(ok.value), st[:pr.shape[0]].tobytes()) if status else bool(ok.value)
+
+    def verify_batch_combined(self, inputs, proofs):
+        """Per-proof verdicts by way of the combined check: all ones when verify_all passes, and only otherwise the per-proof
+        route - verify_batch's bool array, or on a handle made with checked=True verify_batch_checked's (codes, masks), in front
+        of which verify_all runs with the point checks.  Measured (profiles/verify_combined.txt) an all-valid batch is
+        cheaper this way at EVERY size from one proof on (0.57 of the per-proof batch at 1 proof, 0.54 at 1,024, 0.39 at 16,384): there
+        is no batch size below which it does not pay; a batch with an invalid proof costs both routes (1.4 to 1.5 x the per-proof
+        one), so it pays where batches are mostly valid."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+        if self.checked:
+            if self.verify_all(inputs, pr, status=True)[0]:
+                return np.zeros(pr.shape[0], dtype=np.uint8), np.zeros(pr.shape[0], dtype=np.uint8)
+            return self.verify_batch_checked(inputs, pr)
+        if self.verify_all(inputs, pr):
+            return np.ones(pr.shape[0], dtype=bool)
+        return self.verify_batch(inputs, pr)
+
+    def last_finish_ms(self):
+        """Host time of the last verify_all behind the device's work: the three shared pairs and the final exponentiation."""
+        ms = ctypes.c_double(0)
+        _check(load().zkhip_internal_verify_all_finish_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     def free(self):
         if self.handle:
             load().zkhip_verifier_free(self.handle)
             self.handle = None
+
+
+def verify_all_value(route, verifier, inputs, proofs, rho):
+    """Test hook: the reduced GT value of the combined product of Verifier.verify_all, 6 x 12 ABI limbs.  route "host" or "gpu"; on a
+    checked handle both routes leave the proofs out that the point checks refuse."""
+    pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+    inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], verifier.n_inputs, 6)
+    rl = _rho_limbs(rho, pr.shape[0])
+    out = np.zeros((6, 12), dtype=np.uint64)
+    _check(load().zkhip_internal_verify_all_value({"host": 0, "gpu": 1}[route], verifier.handle, _p(inp), _p(pr), pr.shape[0], _p(rl), _p(out)))
+    return out
 
 
 def fq6_selftest(op, a, b):
