@@ -19,6 +19,15 @@ static XYZZ from_abi_point(const uint64_t* p) {
 extern "C" {
 int pairing_strip() { return PAIRING_STRIP; }
 
+// the integer rules of the host driver: proofs per chunk of the per-proof route, and the levels of a reduction tree over n values as
+// the driver walks them - reads[k] values go into level k, which writes pairing_strips of them.  Returns the number of levels.
+size_t batch_chunk(size_t n_inputs) { return pairing_batch_chunk(n_inputs); }
+int tree_levels(size_t n, size_t* reads, size_t* writes) {
+  const int levels = pairing_tree_levels(n);
+  for (int k = 0; k < levels; k++, n = pairing_strips(n)) { reads[k] = n; writes[k] = pairing_strips(n); }
+  return levels;
+}
+
 // k_rho_scale's A lane: rho P as affine ABI limbs, all zero for infinity
 void rho_scale_lane(const uint64_t* p, const uint64_t* rho, uint64_t* out) { xyzz_to_affine_abi(rho_scale(p, rho), out); }
 
@@ -59,14 +68,8 @@ void g1_sum_level(const uint64_t* pts, size_t n, uint64_t* out) {
 void verify_all_value_host(const uint64_t* alpha, const uint64_t* beta, const uint64_t* delta, const uint64_t* abc, size_t n_inputs,
                            const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, unsigned threads, uint64_t* out) {
   using namespace host;
-  auto neg = [](const uint64_t* p, uint64_t* o) {
-    memcpy(o, p, 96);
-    const HFq y = HFq::from_limbs(p + 12);
-    (HFq::from_limbs(p).is_zero() && y.is_zero() ? y : y.neg()).to_limbs(o + 12);
-  };
-  uint64_t g2[24], neg_g2[24], neg_beta[24], neg_delta[24];
-  memcpy(g2, FqParams::G2_GEN_X64, 96); memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
-  neg(g2, neg_g2); neg(beta, neg_beta); neg(delta, neg_delta);
+  uint64_t neg_g2[24], neg_beta[24], neg_delta[24];
+  neg_g2_generator(neg_g2); neg_point_abi(beta, neg_beta); neg_point_abi(delta, neg_delta);
   const CombineKey key = {alpha, neg_g2, neg_beta, neg_delta, abc, n_inputs};
   CombineSums sums(n_inputs);
   Fq6 product = Fq6::one();

@@ -104,6 +104,28 @@ def test_mixed_batches(zk, handles, count, group):
         assert list(ok) == [st == F.ACCEPT for _, st in passed]
 
 
+def test_chunk_boundary_of_the_checked_route(zk, handles):
+    """NESTED_VERIFIER_CHUNK + 1 proofs under the three-input key, the ten statements repeated by indexing their limb arrays: a proof
+    the pairing rejects is the last of the first chunk, a refused one (an input >= r) the only proof of the second, whose codes and
+    status bytes are read at the chunk's offset.  REJECT and the refusal byte at exactly those positions, ACCEPT elsewhere, and
+    nothing went to the host."""
+    chunk = zk.NESTED_VERIFIER_CHUNK
+    checked = handles[1][3][0]
+    base_in, base_pr = _arrays(checked, [F.make_case(3, j) for j in range(10)])
+    idx = np.arange(chunk + 1) % 10
+    inp, prl = base_in[idx], base_pr[idx]
+    rejected, refused = F.make_case(3, (chunk - 1) % 10, bump=True), F.refused_cases(3)["inputs"][0]
+    inp[chunk - 1], prl[chunk - 1] = rejected.inputs, rejected.proof
+    inp[chunk], prl[chunk] = refused.inputs, refused.proof
+    codes, masks = checked.verify_batch_checked(inp, prl)
+    assert checked.last_fallbacks() == 0
+    want = np.full(chunk + 1, F.ACCEPT, dtype=np.uint8)
+    want[chunk - 1], want[chunk] = F.REJECT, refused.want
+    assert (rejected.want, refused.want) == (F.REJECT, F.ENCODING | F.MASK["inputs"])
+    got = codes | masks
+    assert got.shape == want.shape and np.flatnonzero(got != want).tolist() == []
+
+
 def test_inputs_at_the_edge_of_the_scalar_field(zk, handles):
     """r - 1 and 0 are inputs like any other (the pairing rejects the statement); r, 2^253 - 1 and x + q on the limbs are refused"""
     keys, h = handles

@@ -15,12 +15,12 @@ from tests.helpers import aff_limbs, aff_point, csr_from_rows, fr_array, fr_int,
 
 pytestmark = pytest.mark.gpu
 
-G, WG = 4, 8
+G, WG, CHUNK = 4, 8, 8192
 OPS = ["mul", "sqr", "mul_line"]
 
 
 def test_group_sizes(zk):
-    assert (zk.NESTED_VERIFIER_GROUP, zk.NESTED_VERIFIER_WORKGROUP) == (G, WG)
+    assert (zk.NESTED_VERIFIER_GROUP, zk.NESTED_VERIFIER_WORKGROUP, zk.NESTED_VERIFIER_CHUNK) == (G, WG, CHUNK)
 
 
 # ---------------------------------------------------------------- 1. the lane bodies in a kernel
@@ -162,6 +162,26 @@ def test_mixed_batches_twice_and_on_two_handles(zk, k):
                     assert v.last_fallbacks() == 0                   # a batch that silently went through the host would pass the rest
     finally:
         v1.free(); v2.free()
+
+
+def test_chunk_boundary(zk):
+    """CHUNK + 1 proofs under the three-input key (a second chunk of one proof: its proof, inputs and both status bytes sit at the chunk's
+    offset), the ten statements repeated by indexing their limb arrays; an input bumped at the first position and on both sides of the
+    boundary.  False at exactly those three, and nothing went to the host."""
+    vk, proofs = N.statements(3)
+    base_in, base_pr = _arrays(proofs)
+    bad_in, _ = _arrays([(pr, _bumped(xs)) for pr, xs in proofs])
+    idx = np.arange(CHUNK + 1) % len(proofs)
+    inp, prl = base_in[idx], base_pr[idx]
+    invalid = [0, CHUNK - 1, CHUNK]
+    inp[invalid] = bad_in[idx[invalid]]
+    v = zk.NestedVerifier(N.vk_limbs(vk), 3)
+    try:
+        got = np.asarray(v.verify_batch(inp, prl))
+        assert v.last_fallbacks() == 0
+    finally:
+        v.free()
+    assert got.shape == (CHUNK + 1,) and np.flatnonzero(~got).tolist() == invalid
 
 
 # ---------------------------------------------------------------- 5. nine inputs

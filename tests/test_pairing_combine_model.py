@@ -33,6 +33,8 @@ def shim():
     lib.g1_sum_level.argtypes = [vp, sz, vp]
     lib.verify_all_value_host.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, vp, ctypes.c_uint, vp]
     lib.draw_scalars.argtypes = [vp, sz]
+    lib.batch_chunk.argtypes, lib.batch_chunk.restype = [sz], sz
+    lib.tree_levels.argtypes = [sz, vp, vp]
     return lib
 
 
@@ -43,6 +45,39 @@ def rho_words(rhos):
 def test_strip_constant(shim):
     from zecale_amd import zkhip
     assert shim.pairing_strip() == zkhip.VERIFIER_STRIP
+
+
+def test_chunk_of_the_per_proof_route(shim):
+    """VERIFIER_CHUNK proofs while the chunk's terms (proofs x inputs) stay within 2^21, which is up to 128 inputs per proof; beyond
+    that floor(2^21 / n_inputs), and never below one proof.  The right-hand side restates the rule the driver had inline."""
+    from zecale_amd import zkhip
+    chunk, terms = zkhip.VERIFIER_CHUNK, 1 << 21
+    assert chunk == 16384 and chunk * 128 == terms
+    for n in (0, 1, 127, 128, 129, 1000, terms, terms + 1):
+        want = chunk if n == 0 or chunk * n <= terms else max(terms // n, 1)
+        assert shim.batch_chunk(n) == want, n
+    assert [shim.batch_chunk(n) for n in (0, 1, 127, 128)] == [16384] * 4
+    assert [shim.batch_chunk(n) for n in (129, 1000, terms, terms + 1)] == [terms // 129, 2097, 1, 1]
+
+
+def test_levels_of_a_reduction_tree(shim):
+    """For every n up to one past three full levels, and for a whole chunk: level k reads what level k - 1 wrote and writes
+    ceil(n_k / STRIP) values, the levels before the last are left with more than one strip and the last with exactly one, and every
+    level's output fits the buffer it goes to - the first, third, ... level writes the second buffer of ceil(n / STRIP) values, the
+    second, fourth, ... writes back into the first of n."""
+    from zecale_amd import zkhip
+    strip = shim.pairing_strip()
+    reads, writes = np.zeros(64, dtype=np.uint64), np.zeros(64, dtype=np.uint64)
+    for n in list(range(1, strip ** 3 + 2)) + [zkhip.VERIFIER_CHUNK]:
+        levels = shim.tree_levels(n, reads.ctypes.data, writes.ctypes.data)
+        r, w = [int(x) for x in reads[:levels]], [int(x) for x in writes[:levels]]
+        assert levels >= 1 and r[0] == n and r[1:] == w[:-1], n
+        assert w == [-(-x // strip) for x in r], n
+        assert w[-1] == 1 and all(x > 1 for x in w[:-1]), n
+        second = -(-n // strip)
+        assert all(x <= (second if k % 2 == 0 else n) for k, x in enumerate(w)), n
+    assert shim.tree_levels(zkhip.VERIFIER_CHUNK, reads.ctypes.data, writes.ctypes.data) == 5
+    assert [shim.tree_levels(n, reads.ctypes.data, writes.ctypes.data) for n in (1, strip, strip + 1, strip ** 2, strip ** 2 + 1, strip ** 3 + 1)] == [1, 1, 2, 2, 3, 4]
 
 
 def test_rho_scale_lane_against_ec_mul(shim):

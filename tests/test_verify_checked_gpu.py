@@ -104,6 +104,23 @@ def test_a_point_at_infinity_passes_the_checks(zk, handles):
         assert got == [_host_byte(zk, keys[n], n, c) for c in cases] == [F.REJECT, F.ACCEPT, F.REJECT]
 
 
+def test_chunk_boundary_of_the_checked_route(zk, handles):
+    """VERIFIER_CHUNK + 1 proofs on the checked five-input handle: a tampered but well-formed proof is the last of the first chunk, a
+    refused one (an input >= r) the only proof of the second - its inputs and its codes are read at the chunk's offset.  REJECT and
+    the refusal byte at exactly those positions, ACCEPT for every other proof."""
+    from tests import combine_fixtures as C
+    chunk = zk.VERIFIER_CHUNK
+    refused = F.refused_cases(5)["inputs"][0]
+    inp, prf, _ = C.batch(5, chunk + 1, {chunk - 1: 1})
+    inp[chunk], prf[chunk] = refused.inputs, refused.proof
+    codes, masks = handles[1][5][0].verify_batch_checked(inp, prf)
+    got = codes | masks
+    want = np.full(chunk + 1, F.ACCEPT, dtype=np.uint8)
+    want[chunk - 1], want[chunk] = F.REJECT, refused.want
+    assert refused.want == F.ENCODING | F.MASK["inputs"]
+    assert got.shape == want.shape and np.flatnonzero(got != want).tolist() == []
+
+
 def test_two_checked_handles_of_two_keys_interleaved(zk):
     """each batch twice on its handle, the handles taking turns: nothing of a flagged batch stays behind in a handle's work space"""
     keys = {n: V.vk_limbs(V.statements(n)[0]) for n in (0, 5)}

@@ -185,6 +185,52 @@ def test_status_needs_a_checked_handle_and_scalars_must_not_be_zero(zk, handles)
         assert e.value.code == -1
 
 
+def test_work_space_grows_and_is_reused_across_routes_on_one_handle(zk):
+    """ONE fresh checked handle takes, in this order: verify_all with status at STRIP + 1 (the handle's first call: the combined route
+    reserves the input buffer), verify_batch_checked at WG + 1, verify_all at 1, verify_batch at 2 WG + 1, verify_all with status at
+    STRIP^2 + 1, verify_batch_checked at 1 - growing, shrinking, and changing the route that sizes the work space.  Every batch has a
+    tampered proof in the middle and, from two proofs on, a refused one (an input >= r) at the end.  Every result equals that of the
+    same call on a fresh handle of its own, and the bytes the checked calls give are the construction's."""
+    key = V.vk_limbs(V.statements(5)[0])
+    refused = F.refused_cases(5)["inputs"][0]
+    calls = [("verify_all", STRIP + 1, True), ("verify_batch_checked", WG + 1, False), ("verify_all", 1, False), ("verify_batch", 2 * WG + 1, False),
+             ("verify_all", STRIP * STRIP + 1, True), ("verify_batch_checked", 1, False)]
+
+    def call(v, name, count, status):
+        inp, prf, _ = C.batch(5, count, {count // 2: 1})
+        if count > 1:
+            inp[count - 1], prf[count - 1] = refused.inputs, refused.proof
+        if name == "verify_all":
+            out = v.verify_all(inp, prf, rho=C.scalars(count, seed=count), status=status)
+            return (out[0], list(out[1])) if status else out
+        if name == "verify_batch":
+            return [bool(b) for b in v.verify_batch(inp, prf)]
+        codes, masks = v.verify_batch_checked(inp, prf)
+        return [int(c | m) for c, m in zip(codes, masks)]
+
+    def bytes_wanted(count, tampered):
+        want = [0] * count
+        want[count // 2] = tampered
+        if count > 1:
+            want[count - 1] = refused.want
+        return want
+
+    shared = zk.Verifier(key, checked=True)
+    try:
+        got = [call(shared, *c) for c in calls]
+    finally:
+        shared.free()
+    for c, g in zip(calls, got):
+        fresh = zk.Verifier(key, checked=True)
+        try:
+            assert call(fresh, *c) == g, c
+        finally:
+            fresh.free()
+    assert got[0] == (False, bytes_wanted(STRIP + 1, 0)) and got[4] == (False, bytes_wanted(STRIP * STRIP + 1, 0))
+    assert got[1] == bytes_wanted(WG + 1, F.REJECT) and got[5] == [F.REJECT]
+    assert got[2] is False and got[3][:2 * WG] == [j != WG for j in range(2 * WG)]
+
+
 # ---------------------------------------------------------------- 7: per-proof verdicts by way of the combined check
 def test_verify_batch_combined(zk, handles):
     v, count = handles[N], WG + 1

@@ -190,6 +190,21 @@ def test_mixed_batches_on_two_handles(zk, count):
         h.free()
 
 
+def test_chunk_boundary_of_the_per_proof_route(zk):
+    """VERIFIER_CHUNK + 1 proofs (a second chunk of one proof: its staging, inputs and verdict start at an offset), tampered at the
+    first position and on both sides of the boundary: False at exactly those three, True everywhere else."""
+    from tests import combine_fixtures as C
+    n, chunk = 4, zk.VERIFIER_CHUNK
+    inp, prf, ks = C.batch(n, chunk + 1, {0: 1, chunk - 1: 1, chunk: 1})
+    v = zk.Verifier(V.vk_limbs(V.statements(n)[0]))
+    try:
+        got = np.asarray(v.verify_batch(inp, prf))
+    finally:
+        v.free()
+    assert got.shape == (chunk + 1,) and got.dtype == np.bool_
+    assert np.flatnonzero(~got).tolist() == [0, chunk - 1, chunk] == [j for j, k in enumerate(ks) if k]
+
+
 def test_two_verifier_threads_beside_a_prover(zk):
     g = golden("groth16_small.json")
     pts = lambda L: np.array([aff_limbs(pt_from_json(p)) for p in L]).reshape(-1, 24)

@@ -29,23 +29,6 @@ static int verifier_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2,
   return ZKHIP_OK;
 }
 
-// y^2 = x^3 - 1 (G1) or x^3 + 4 (G2), both over Fq; the all-zero encoding of the point at infinity passes
-static bool on_curve_abi(const uint64_t* p, bool g2) {
-  using host::HFq;
-  const HFq x = HFq::from_limbs(p), y = HFq::from_limbs(p + 12);
-  if (x.is_zero() && y.is_zero()) return true;
-  const HFq rhs = x.sqr() * x + (g2 ? HFq::one().dbl().dbl() : HFq::one().neg());
-  return y.sqr() == rhs;
-}
-
-static void neg_point_abi(const uint64_t* p, uint64_t* o) {
-  using host::HFq;
-  memcpy(o, p, 96);
-  const HFq y = HFq::from_limbs(p + 12);
-  const bool inf = HFq::from_limbs(p).is_zero() && y.is_zero();
-  (inf ? y : y.neg()).to_limbs(o + 12);
-}
-
 // the scalars of a combined batch: the caller's (none zero), or count x 16 bytes from the OS into `own`
 static int combine_scalars(const uint64_t* rho, size_t count, std::vector<uint64_t>& own, const uint64_t** out) {
   if (rho) {
@@ -71,12 +54,6 @@ static void verify_all_host(const host::CombineKey& key, const uint64_t* inputs,
   fq6_to_limbs(combined_value(key, sums, s_c, product), value);
 }
 
-static bool value_is_one(const uint64_t* value) {
-  uint64_t one[72] = {0};
-  host::HFq::one().to_limbs(one);
-  return memcmp(value, one, sizeof one) == 0;
-}
-
 #pragma GCC visibility pop
 
 extern "C" {
@@ -88,13 +65,8 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
   if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !proof_affine || !ok || (n_inputs && !inputs))
     return fail(ZKHIP_ERR_ARG, "null pointer");
   auto aff = [](const uint64_t* p) { return HJac::from_affine(HFq::from_limbs(p), HFq::from_limbs(p + 12)); };
-  // well-formedness first (libsnark: proof.is_well_formed()): G1 is y^2 = x^3 - 1, G2 is y^2 = x^3 + 4, both over Fq;
-  // the all-zero encoding of the point at infinity passes.  An off-curve point would put the pairing in an invalid-curve setting.
-  auto on_curve = on_curve_abi;
-  bool wf = on_curve(proof_affine, false) && on_curve(proof_affine + 24, true) && on_curve(proof_affine + 48, false) &&
-            on_curve(vk_alpha_g1, false) && on_curve(vk_beta_g2, true) && on_curve(vk_delta_g2, true);
-  for (size_t i = 0; i <= n_inputs && wf; i++) wf = on_curve(vk_abc + i * 24, false);
-  if (!wf) { *ok = 0; return ZKHIP_OK; }
+  // well-formedness first: a proof or a key with a point off its curve is rejected before any pairing arithmetic
+  if (!proof_on_curve(proof_affine) || !key_on_curve(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs)) { *ok = 0; return ZKHIP_OK; }
   // acc = ABC_0 + sum x_i ABC_i
   HJac acc = aff(vk_abc);
   for (size_t i = 0; i < n_inputs; i++) {
@@ -105,10 +77,7 @@ int zkhip_groth16_verify(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_
   uint64_t acc_aff[24], neg_g2[24], neg_beta[24], neg_delta[24];
   HFq x, y;
   acc.to_affine(x, y); x.to_limbs(acc_aff); y.to_limbs(acc_aff + 12);
-  auto neg_pt = neg_point_abi;
-  uint64_t g2[24];
-  memcpy(g2, FqParams::G2_GEN_X64, 96); memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
-  neg_pt(g2, neg_g2); neg_pt(vk_beta_g2, neg_beta); neg_pt(vk_delta_g2, neg_delta);
+  neg_g2_generator(neg_g2); neg_point_abi(vk_beta_g2, neg_beta); neg_point_abi(vk_delta_g2, neg_delta);
   std::vector<const uint64_t*> p1 = {proof_affine, acc_aff, vk_alpha_g1, proof_affine + 48};
   std::vector<const uint64_t*> p2 = {proof_affine + 24, neg_g2, neg_beta, neg_delta};
   *ok = pairing_product_is_one(p1, p2) ? 1 : 0;
@@ -125,17 +94,14 @@ int zkhip_groth16_verify_all(const uint64_t vk_alpha_g1[24], const uint64_t vk_b
   const int rc = combine_scalars(rho, count, own, &rho);
   if (rc != ZKHIP_OK) return rc;
   // well-formedness first, as zkhip_groth16_verify: a point off its curve fails the batch before any pairing arithmetic
-  bool wf = on_curve_abi(vk_alpha_g1, false) && on_curve_abi(vk_beta_g2, true) && on_curve_abi(vk_delta_g2, true);
-  for (size_t i = 0; i <= n_inputs && wf; i++) wf = on_curve_abi(vk_abc + i * 24, false);
-  for (size_t i = 0; i < count && wf; i++)
-    wf = on_curve_abi(proofs_affine + i * 72, false) && on_curve_abi(proofs_affine + i * 72 + 24, true) && on_curve_abi(proofs_affine + i * 72 + 48, false);
+  bool wf = host::key_on_curve(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs);
+  for (size_t i = 0; i < count && wf; i++) wf = host::proof_on_curve(proofs_affine + i * 72);
   if (!wf) { *all_ok = 0; return ZKHIP_OK; }
-  uint64_t g2[24], neg_g2[24], neg_beta[24], neg_delta[24], value[72];
-  memcpy(g2, FqParams::G2_GEN_X64, 96); memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
-  neg_point_abi(g2, neg_g2); neg_point_abi(vk_beta_g2, neg_beta); neg_point_abi(vk_delta_g2, neg_delta);
+  uint64_t neg_g2[24], neg_beta[24], neg_delta[24], value[72];
+  host::neg_g2_generator(neg_g2); host::neg_point_abi(vk_beta_g2, neg_beta); host::neg_point_abi(vk_delta_g2, neg_delta);
   const host::CombineKey key = {vk_alpha_g1, neg_g2, neg_beta, neg_delta, vk_abc, n_inputs};
   verify_all_host(key, inputs, proofs_affine, count, rho, nullptr, value);
-  *all_ok = value_is_one(value) ? 1 : 0;
+  *all_ok = host::gt_is_one(value) ? 1 : 0;
   return ZKHIP_OK;
 }
 
@@ -159,11 +125,7 @@ int zkhip_groth16_verify_checked(const uint64_t vk_alpha_g1[24], const uint64_t 
     return ZKHIP_ERR_ARG;
   }
   uint8_t e[4];
-  e[0] = (uint8_t)host::point_check_host(proof_affine, false);
-  e[1] = (uint8_t)host::point_check_host(proof_affine + 24, true);
-  e[2] = (uint8_t)host::point_check_host(proof_affine + 48, false);
-  e[3] = ZKHIP_VERIFY_ACCEPT;
-  for (size_t i = 0; i < n_inputs; i++) if (host::HFr::geq_p(inputs + i * 6)) e[3] = ZKHIP_VERIFY_ENCODING;
+  host::proof_check_codes_host(proof_affine, inputs, n_inputs, e);
   if ((*status = verify_refusal(e)) != 0) return ZKHIP_OK;
   int ok = 0;
   const int rc = zkhip_groth16_verify(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, inputs, n_inputs, proof_affine, &ok);
@@ -209,7 +171,7 @@ int zkhip_verifier_verify_all(zkhip_verifier* v, const uint64_t* inputs, const u
   BIND(v);
   uint64_t value[72];
   if ((rc = pairing_verify_all(v->ctx, inputs, proofs_affine, count, rho, status != nullptr, status, value, t_err, sizeof t_err)) != ZKHIP_OK) return rc;
-  bool ok = value_is_one(value);
+  bool ok = host::gt_is_one(value);
   for (size_t i = 0; status && ok && i < count; i++) ok = status[i] == 0;      // a refused proof is left out of the product and fails the batch
   *all_ok = ok ? 1 : 0;
   return ZKHIP_OK;
@@ -270,10 +232,8 @@ int zkhip_internal_verify_all_value(int route, zkhip_verifier* v, const uint64_t
   if (checked) {                                   // the checked route's refusals, on the host: such a proof is left out
     skip.resize(count);
     for (size_t i = 0; i < count; i++) {
-      const uint64_t* pr = proofs_affine + i * 72;
-      uint8_t e[4] = {(uint8_t)host::point_check_host(pr, false), (uint8_t)host::point_check_host(pr + 24, true),
-                      (uint8_t)host::point_check_host(pr + 48, false), ZKHIP_VERIFY_ACCEPT};
-      for (size_t j = 0; j < key.n_inputs; j++) if (host::HFr::geq_p(inputs + (i * key.n_inputs + j) * 6)) e[3] = ZKHIP_VERIFY_ENCODING;
+      uint8_t e[4];
+      host::proof_check_codes_host(proofs_affine + i * 72, inputs + i * key.n_inputs * 6, key.n_inputs, e);
       skip[i] = verify_refusal(e);
     }
   }

@@ -30,7 +30,25 @@ constexpr int PAIRING_MILLER_STEPS = 376;   // bit length of r minus one
 // combined batches: values one strip of the reduction trees multiplies (k_gt_product) or adds (k_g1_sum).  Eight keeps a launch's
 // dependent chain at seven products, and a chunk of 16,384 values is down to one in five launches of microseconds each.
 constexpr int PAIRING_STRIP = 8;
+constexpr size_t PAIRING_CHUNK = 16384;     // verifications per launch sequence (bounds the work space)
+constexpr size_t PAIRING_MAX_TERMS = (size_t)1 << 21;   // terms x_i ABC_i per launch of the per-proof route: 0.9 GB of work space
 constexpr int PAIRING_RHO_BITS = 128;       // bit length of a combination scalar
+
+// ---- the integer rules of the host driver (pairing.hip), here so that g++ reads them too (tests/pairing_combine_host_shim.cpp)
+// proofs per chunk of the per-proof route: PAIRING_CHUNK while that keeps the chunk's terms within PAIRING_MAX_TERMS, never below one
+constexpr size_t pairing_batch_chunk(size_t n_inputs) {
+  if (n_inputs == 0 || PAIRING_CHUNK * n_inputs <= PAIRING_MAX_TERMS) return PAIRING_CHUNK;
+  return PAIRING_MAX_TERMS / n_inputs ? PAIRING_MAX_TERMS / n_inputs : 1;
+}
+// values one level of a reduction tree writes for the n it reads
+constexpr size_t pairing_strips(size_t n) { return (n + PAIRING_STRIP - 1) / PAIRING_STRIP; }
+// launches of a reduction tree over n >= 1 values: level k reads n_k values (n_0 = n) and writes n_{k+1} = pairing_strips(n_k); the last
+// level is the one that is left with one strip
+constexpr int pairing_tree_levels(size_t n) {
+  int levels = 1;
+  for (; pairing_strips(n) > 1; n = pairing_strips(n)) levels++;
+  return levels;
+}
 
 ZK_HD ZK_INL Fq fq_select(bool c, const Fq& a, const Fq& b) {
   Fq r;

@@ -15,8 +15,10 @@
 #include <stdio.h>
 #include <string.h>
 #include <chrono>
+#include <utility>
 #include <vector>
 
+#include "device_buffer.hpp"
 #include "ec.cuh"
 #include "fp_inv.cuh"
 #include "host_field.hpp"
@@ -28,8 +30,8 @@ namespace zkhip {
 
 constexpr int PAIRING_BLOCK = 128;
 constexpr int PAIRING_WG = PAIRING_BLOCK / PAIRING_GROUP;      // verifications per workgroup
-// (PAIRING_STRIP, the strip of the combined batches' reduction trees, is pairing.cuh's: the lane bodies and the host shim read it too)
-constexpr size_t PAIRING_CHUNK = 16384;                        // verifications per launch sequence (bounds the work space)
+// (PAIRING_STRIP, the strip of the combined batches' reduction trees, PAIRING_CHUNK and the rules of the chunk loops are pairing.cuh's:
+// the lane bodies and the host shim read them too)
 
 // ---- ABI points -> the constants of a Miller loop.  One lane per pair.
 __global__ void __launch_bounds__(64) k_pair_prep(const uint64_t* __restrict__ g1, const uint64_t* __restrict__ g2,
@@ -315,112 +317,44 @@ __global__ void __launch_bounds__(64) k_g1_sum(const XYZZ* __restrict__ in, size
   else out[s] = acc;
 }
 
-#define PAIR_HIP(x)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (x);                                                                              \
-    if (e_ != hipSuccess) {                                                                           \
-      if (errbuf) snprintf(errbuf, errlen, "pairing: %s: %s", #x, hipGetErrorString(e_));             \
-      return ZKHIP_ERR_HIP;                                                                           \
-    }                                                                                                 \
-  } while (0)
-
 namespace {
-unsigned blocks_for(size_t n, size_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
 int bit_length(const uint64_t* e, int limbs) {
   int top = limbs * 64 - 1;
   while (top > 0 && !((e[top / 64] >> (top % 64)) & 1)) top--;
   return top + 1;
 }
-
-// -Q for a point in ABI limbs (infinity stays infinity)
-void neg_point(const uint64_t* p, uint64_t* o) {
-  using host::HFq;
-  memcpy(o, p, 96);
-  const HFq y = HFq::from_limbs(p + 12);
-  const bool inf = HFq::from_limbs(p).is_zero() && y.is_zero();
-  (inf ? y : y.neg()).to_limbs(o + 12);
-}
 }  // namespace
 
 struct PairingCtx {
-  hipStream_t st = nullptr;
-  uint64_t* d_const = nullptr;      // r (6), the final exponent (66), 1/4 and -1/4 (24)
+  DeviceStream st;                            // in front of the buffers: destroyed behind them
+  DeviceBuffer<uint64_t> d_const;             // r (6), the final exponent (66), 1/4 and -1/4 (24)
   int fe_bits = 0;
-  size_t cap = 0;                   // products the work space holds
-  uint64_t *d_g1 = nullptr, *d_g2 = nullptr, *d_gt = nullptr;
-  MillerConst* d_pairs = nullptr;
-  uint32_t* d_inf = nullptr;
-  Fq* d_f = nullptr;
-  uint8_t* d_codes = nullptr;       // checked batches: four codes per proof (k_point_check), one word per proof as the flag array
+  // the work space of a chunk (reserve_chunk)
+  DeviceBuffer<uint64_t> d_g1, d_g2, d_gt;
+  DeviceBuffer<MillerConst> d_pairs;
+  DeviceBuffer<uint32_t> d_inf;
+  DeviceBuffer<Fq> d_f;
+  DeviceBuffer<uint8_t> d_codes;              // checked batches: four codes per proof (k_point_check), one word per proof as the flag array
   // verifier handles
   bool has_key = false;
-  bool checked = false;             // the key passed k_point_check (pairing_ctx_new with checked set)
+  bool checked = false;                       // the key passed k_point_check (pairing_ctx_new with checked set)
   size_t n_inputs = 0;
-  AbcDev* d_abc = nullptr;
-  uint64_t* d_inputs = nullptr;
-  XYZZ* d_terms = nullptr;
-  size_t in_cap = 0;
+  DeviceBuffer<AbcDev> d_abc;
+  DeviceBuffer<uint64_t> d_inputs;
+  DeviceBuffer<XYZZ> d_terms;
   uint64_t alpha[24], neg_g2[24], neg_beta[24], neg_delta[24];
-  std::vector<uint64_t> abc;        // the key's ABC points, ABI limbs (the host finish of a combined batch)
+  std::vector<uint64_t> abc;                  // the key's ABC points, ABI limbs (the host finish of a combined batch)
   std::vector<uint64_t> h_g1, h_g2, h_gt;
   std::vector<uint8_t> h_codes;
   // combined batches (pairing_verify_all)
-  size_t comb_cap = 0;
-  uint64_t *d_rho = nullptr, *d_ra = nullptr, *d_b = nullptr, *d_res = nullptr;   // scalars, rho A and B per pair, the chunk's product | sum
-  XYZZ *d_rc = nullptr, *d_rc2 = nullptr;                                         // rho C, and the other buffer of the sum tree
-  Fq* d_f2 = nullptr;                                                             // the other buffer of the product tree
+  DeviceBuffer<uint64_t> d_rho, d_ra, d_b, d_res;   // scalars, rho A and B per pair, the chunk's product | sum
+  DeviceBuffer<XYZZ> d_rc, d_rc2;                   // rho C, and the other buffer of the sum tree
+  DeviceBuffer<Fq> d_f2;                            // the other buffer of the product tree
   std::vector<uint64_t> h_b;
   double finish_ms = 0;
 };
 
-static void ctx_release_work(PairingCtx* c) {
-  for (void* p : {(void*)c->d_g1, (void*)c->d_g2, (void*)c->d_gt, (void*)c->d_pairs, (void*)c->d_inf, (void*)c->d_f, (void*)c->d_codes}) if (p) (void)hipFree(p);
-  c->d_g1 = c->d_g2 = c->d_gt = nullptr; c->d_pairs = nullptr; c->d_inf = nullptr; c->d_f = nullptr; c->d_codes = nullptr; c->cap = 0;
-}
-
-static int ctx_reserve(PairingCtx* c, size_t count, char* errbuf, size_t errlen) {
-  if (count <= c->cap) return ZKHIP_OK;
-  ctx_release_work(c);
-  PAIR_HIP(hipMalloc(&c->d_g1, count * 4 * 24 * 8));
-  PAIR_HIP(hipMalloc(&c->d_g2, count * 4 * 24 * 8));
-  PAIR_HIP(hipMalloc(&c->d_gt, count * 72 * 8));
-  PAIR_HIP(hipMalloc(&c->d_pairs, count * 4 * sizeof(MillerConst)));
-  PAIR_HIP(hipMalloc(&c->d_inf, count * 4 * sizeof(uint32_t)));
-  PAIR_HIP(hipMalloc(&c->d_f, count * 6 * sizeof(Fq)));
-  PAIR_HIP(hipMalloc(&c->d_codes, count * 4));
-  c->cap = count;
-  return ZKHIP_OK;
-}
-
-static void ctx_release_comb(PairingCtx* c) {
-  for (void* p : {(void*)c->d_rho, (void*)c->d_ra, (void*)c->d_b, (void*)c->d_res, (void*)c->d_rc, (void*)c->d_rc2, (void*)c->d_f2}) if (p) (void)hipFree(p);
-  c->d_rho = c->d_ra = c->d_b = c->d_res = nullptr; c->d_rc = c->d_rc2 = nullptr; c->d_f2 = nullptr; c->comb_cap = 0;
-}
-
-static int ctx_reserve_comb(PairingCtx* c, size_t count, char* errbuf, size_t errlen) {
-  if (count <= c->comb_cap) return ZKHIP_OK;
-  ctx_release_comb(c);
-  const size_t strips = (count + PAIRING_STRIP - 1) / PAIRING_STRIP;
-  PAIR_HIP(hipMalloc(&c->d_rho, count * 16));
-  PAIR_HIP(hipMalloc(&c->d_ra, count * 192));
-  PAIR_HIP(hipMalloc(&c->d_b, count * 192));
-  PAIR_HIP(hipMalloc(&c->d_res, (72 + 24) * 8));
-  PAIR_HIP(hipMalloc(&c->d_rc, count * sizeof(XYZZ)));
-  PAIR_HIP(hipMalloc(&c->d_rc2, strips * sizeof(XYZZ)));
-  PAIR_HIP(hipMalloc(&c->d_f2, strips * 6 * sizeof(Fq)));
-  c->comb_cap = count;
-  return ZKHIP_OK;
-}
-
-void pairing_ctx_free(PairingCtx* c) {
-  if (!c) return;
-  ctx_release_work(c);
-  ctx_release_comb(c);
-  for (void* p : {(void*)c->d_const, (void*)c->d_abc, (void*)c->d_inputs, (void*)c->d_terms}) if (p) (void)hipFree(p);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  delete c;
-}
+void pairing_ctx_free(PairingCtx* c) { delete c; }     // every buffer, then the stream
 
 size_t pairing_ctx_num_inputs(const PairingCtx* c) { return c ? c->n_inputs : 0; }
 double pairing_ctx_last_finish_ms(const PairingCtx* c) { return c ? c->finish_ms : 0; }
@@ -445,19 +379,18 @@ static int ctx_check_key(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint6
   memcpy(&pts[0], vk_alpha_g1, 192); memcpy(&pts[24], vk_beta_g2, 192); memcpy(&pts[48], vk_delta_g2, 192);
   memcpy(&pts[72], vk_abc, (n_inputs + 1) * 192);
   std::vector<uint8_t> codes(n);
-  uint64_t* d_pts = nullptr;
-  uint8_t* d_kc = nullptr;
-  hipError_t e = hipMalloc(&d_pts, n * 192);
-  if (e == hipSuccess) e = hipMalloc(&d_kc, n);
+  DeviceBuffer<uint64_t> d_pts;
+  DeviceBuffer<uint8_t> d_kc;
+  hipError_t e = d_pts.reserve(n * 24);
+  if (e == hipSuccess) e = d_kc.reserve(n);
   if (e == hipSuccess) e = hipMemcpyAsync(d_pts, pts.data(), n * 192, hipMemcpyHostToDevice, c->st);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_point_check, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, d_pts, nullptr, nullptr, 0, n, 1, c->d_const, d_kc);
+    hipLaunchKernelGGL(k_point_check, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, d_pts.get(), nullptr, nullptr, 0, n, 1, c->d_const.get(), d_kc.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(codes.data(), d_kc, n, hipMemcpyDeviceToHost, c->st);
   if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-  for (void* p : {(void*)d_pts, (void*)d_kc}) if (p) (void)hipFree(p);
-  PAIR_HIP(e);
+  ZK_HIP_TRY("pairing", e);
   for (size_t i = 0; i < n; i++) {
     if (!codes[i]) continue;
     if (errbuf) pairing_key_refusal(i, codes[i], errbuf, errlen);
@@ -470,7 +403,7 @@ static int ctx_check_key(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint6
 static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, const uint64_t* vk_delta_g2, const uint64_t* vk_abc,
                     size_t n_inputs, bool checked, char* errbuf, size_t errlen) {
   using host::HFq;
-  PAIR_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  ZK_HIP_TRY("pairing", c->st.create());
   uint64_t k[6 + 66 + 24];
   static_assert(FqParams::FINAL_EXP_LIMBS == 66, "");
   memcpy(k, FqParams::R_ORDER64, 48);
@@ -483,9 +416,9 @@ static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* 
     return ZKHIP_ERR_STATE;
   }
   c->fe_bits = bit_length(FqParams::FINAL_EXP, 66);
-  PAIR_HIP(hipMalloc(&c->d_const, sizeof k));
-  PAIR_HIP(hipMemcpyAsync(c->d_const, k, sizeof k, hipMemcpyHostToDevice, c->st));
-  PAIR_HIP(hipStreamSynchronize(c->st));
+  ZK_HIP_TRY("pairing", c->d_const.reserve(sizeof k / 8));
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_const, k, sizeof k, hipMemcpyHostToDevice, c->st));
+  ZK_HIP_TRY("pairing", hipStreamSynchronize(c->st));
   if (!vk_alpha_g1) return ZKHIP_OK;
   if (checked) {                                   // before any host or device arithmetic on the key's points
     const int rc = ctx_check_key(c, vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, errbuf, errlen);
@@ -495,24 +428,16 @@ static int ctx_init(PairingCtx* c, const uint64_t* vk_alpha_g1, const uint64_t* 
   c->n_inputs = n_inputs;
   memcpy(c->alpha, vk_alpha_g1, 192);
   c->abc.assign(vk_abc, vk_abc + (n_inputs + 1) * 24);
-  uint64_t g2[24];
-  memcpy(g2, FqParams::G2_GEN_X64, 96);
-  memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
-  neg_point(g2, c->neg_g2);
-  neg_point(vk_beta_g2, c->neg_beta);
-  neg_point(vk_delta_g2, c->neg_delta);
-  uint64_t* d_abi = nullptr;
-  const size_t bytes = (n_inputs + 1) * 192;
-  PAIR_HIP(hipMalloc(&c->d_abc, (n_inputs + 1) * sizeof(AbcDev)));
-  PAIR_HIP(hipMalloc(&d_abi, bytes));
-  hipError_t e = hipMemcpyAsync(d_abi, vk_abc, bytes, hipMemcpyHostToDevice, c->st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_abc_prep, dim3(blocks_for(n_inputs + 1, 64)), dim3(64), 0, c->st, d_abi, n_inputs + 1, c->d_abc);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->st);
-  (void)hipFree(d_abi);
-  PAIR_HIP(e);
+  host::neg_g2_generator(c->neg_g2);
+  host::neg_point_abi(vk_beta_g2, c->neg_beta);
+  host::neg_point_abi(vk_delta_g2, c->neg_delta);
+  DeviceBuffer<uint64_t> d_abi;
+  ZK_HIP_TRY("pairing", c->d_abc.reserve(n_inputs + 1));
+  ZK_HIP_TRY("pairing", d_abi.reserve((n_inputs + 1) * 24));
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(d_abi, vk_abc, (n_inputs + 1) * 192, hipMemcpyHostToDevice, c->st));
+  hipLaunchKernelGGL(k_abc_prep, dim3(blocks_for(n_inputs + 1, 64)), dim3(64), 0, c->st, d_abi.get(), n_inputs + 1, c->d_abc.get());
+  ZK_HIP_TRY("pairing", hipGetLastError());
+  ZK_HIP_TRY("pairing", hipStreamSynchronize(c->st));
   return ZKHIP_OK;
 }
 
@@ -525,93 +450,146 @@ int pairing_ctx_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, con
   return ZKHIP_OK;
 }
 
+// ---- the stages of a chunk.  `combined` is pairing_verify_all's route, `checked` the one with k_point_check in front.
+
+// The work space of a chunk of m products.  The inputs are on the device for k_acc_terms and for k_point_check; only the per-proof
+// route has terms, only the combined route its scalars, scaled points and the second buffers of its trees.
+static int reserve_chunk(PairingCtx* c, size_t m, bool combined, bool checked, char* errbuf, size_t errlen) {
+  ZK_HIP_TRY("pairing", c->d_g1.reserve(m * 4 * 24));
+  ZK_HIP_TRY("pairing", c->d_g2.reserve(m * 4 * 24));
+  ZK_HIP_TRY("pairing", c->d_gt.reserve(m * 72));
+  ZK_HIP_TRY("pairing", c->d_pairs.reserve(m * 4));
+  ZK_HIP_TRY("pairing", c->d_inf.reserve(m * 4));
+  ZK_HIP_TRY("pairing", c->d_f.reserve(m * 6));
+  ZK_HIP_TRY("pairing", c->d_codes.reserve(m * 4));
+  if (!combined || checked) ZK_HIP_TRY("pairing", c->d_inputs.reserve(m * c->n_inputs * 6));
+  if (!combined) {
+    ZK_HIP_TRY("pairing", c->d_terms.reserve(m * c->n_inputs));
+    return ZKHIP_OK;
+  }
+  ZK_HIP_TRY("pairing", c->d_rho.reserve(m * 2));
+  ZK_HIP_TRY("pairing", c->d_ra.reserve(m * 24));
+  ZK_HIP_TRY("pairing", c->d_b.reserve(m * 24));
+  ZK_HIP_TRY("pairing", c->d_res.reserve(72 + 24));
+  ZK_HIP_TRY("pairing", c->d_rc.reserve(m));
+  ZK_HIP_TRY("pairing", c->d_rc2.reserve(pairing_strips(m)));
+  ZK_HIP_TRY("pairing", c->d_f2.reserve(pairing_strips(m) * 6));
+  return ZKHIP_OK;
+}
+
+// m proofs into the four-slot layout that k_point_check and run_products read: A and C in the first and the fourth G1 slot, B in the
+// first G2 slot.  The per-proof route fills the other slots with its three shared pairs; the combined route keeps B apart, one point
+// per pair, and needs the G2 slots only for k_point_check (with_g2).
+static void stage_chunk(PairingCtx* c, const uint64_t* proofs, size_t m, bool combined, bool with_g2) {
+  c->h_g1.resize(m * 96);
+  if (with_g2) c->h_g2.resize(m * 96);
+  if (combined) c->h_b.resize(m * 24);
+  for (size_t j = 0; j < m; j++) {
+    const uint64_t* pr = proofs + j * 72;
+    uint64_t* p1 = &c->h_g1[j * 96];
+    memcpy(p1, pr, 192);                                                  // A
+    memcpy(p1 + 72, pr + 48, 192);                                        // C
+    if (with_g2) memcpy(&c->h_g2[j * 96], pr + 24, 192);                  // B
+    if (combined) {
+      memcpy(&c->h_b[j * 24], pr + 24, 192);
+      continue;
+    }
+    uint64_t* p2 = &c->h_g2[j * 96];                                      // e(A, B) and e(C, -delta) stand in slots 0 and 3
+    memset(p1 + 24, 0, 192);        memcpy(p2 + 24, c->neg_g2, 192);      // e(acc, -g2): k_acc_sum writes acc
+    memcpy(p1 + 48, c->alpha, 192); memcpy(p2 + 48, c->neg_beta, 192);    // e(alpha, -beta)
+    memcpy(p2 + 72, c->neg_delta, 192);
+  }
+}
+
+// the staged G2 slots and the chunk's inputs to the device: what k_point_check reads besides the G1 slots
+static int upload_g2_and_inputs(PairingCtx* c, const uint64_t* inputs, size_t m, char* errbuf, size_t errlen) {
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g2, c->h_g2.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
+  if (c->n_inputs) ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_inputs, inputs, m * c->n_inputs * 48, hipMemcpyHostToDevice, c->st));
+  return ZKHIP_OK;
+}
+
+// k_point_check on the staged chunk; its codes, read as one word per proof, are the flags of the kernels behind
+static const uint32_t* enqueue_point_check(PairingCtx* c, size_t m) {
+  c->h_codes.resize(m * 4);
+  hipLaunchKernelGGL(k_point_check, dim3(blocks_for(m * 3, 64)), dim3(64), 0, c->st, c->d_g1.get(), c->d_g2.get(), c->d_inputs.get(), c->n_inputs,
+                     m * 3, 0, c->d_const.get(), c->d_codes.get());
+  return reinterpret_cast<const uint32_t*>(c->d_codes.get());
+}
+
+// A reduction tree over the n values in `a`: launch(in, n_k, out, last) for level after level until one strip is left
+// (pairing_tree_levels).  The values of the level before are dead, so their buffer takes the next level: the first level writes b,
+// which holds pairing_strips(n) values, the second a, and so on.
+template <class T, class Launch>
+static void reduce_tree(T* a, T* b, size_t n, Launch launch) {
+  for (int k = 0, levels = pairing_tree_levels(n); k < levels; k++, n = pairing_strips(n)) {
+    launch(const_cast<const T*>(a), n, b, k + 1 == levels);
+    std::swap(a, b);
+  }
+}
+
+// what came back for a chunk -> ok[j].  Unchecked: 1 / 0.  Checked: the status byte of zkhip.h - what refuses the proof, or the
+// pairing's verdict.
+static void chunk_verdicts(const PairingCtx* c, size_t m, bool checked, uint8_t* ok) {
+  for (size_t j = 0; j < m; j++) {
+    const bool is_one = host::gt_is_one(&c->h_gt[j * 72]);
+    if (!checked) { ok[j] = is_one ? 1 : 0; continue; }
+    const uint8_t refused = verify_refusal(&c->h_codes[j * 4]);
+    ok[j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
+  }
+}
+
 // d_g1 / d_g2 hold `count` products of `pairs` pairs: Miller loop, final exponentiation, GT values to the host.
 // flags: null, or the checked route's word per product (non-zero: the product's pairs are read as points at infinity); codes_out: null,
 // or where the checked route's count x 4 codes go, in the same synchronisation as the GT values
 static int run_products(PairingCtx* c, int pairs, size_t count, uint64_t* out, const uint32_t* flags, uint8_t* codes_out, char* errbuf, size_t errlen) {
   const size_t n = count * (size_t)pairs;
-  hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_const + 72, n, c->d_pairs, c->d_inf, flags,
-                     pairs);
-  hipLaunchKernelGGL(k_miller, dim3(blocks_for(count, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs, c->d_inf, pairs, count,
-                     c->d_const, c->d_f);
-  hipLaunchKernelGGL(k_final_exp, dim3(blocks_for(count, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_f, c->d_const + 6, c->fe_bits, count,
-                     c->d_gt);
-  PAIR_HIP(hipGetLastError());
-  PAIR_HIP(hipMemcpyAsync(out, c->d_gt, count * 72 * 8, hipMemcpyDeviceToHost, c->st));
-  if (codes_out) PAIR_HIP(hipMemcpyAsync(codes_out, c->d_codes, count * 4, hipMemcpyDeviceToHost, c->st));
-  PAIR_HIP(hipStreamSynchronize(c->st));
+  hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_g1.get(), c->d_g2.get(), c->d_const + 72, n, c->d_pairs.get(),
+                     c->d_inf.get(), flags, pairs);
+  hipLaunchKernelGGL(k_miller, dim3(blocks_for(count, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs.get(), c->d_inf.get(), pairs, count,
+                     c->d_const.get(), c->d_f.get());
+  hipLaunchKernelGGL(k_final_exp, dim3(blocks_for(count, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_f.get(), c->d_const + 6, c->fe_bits, count,
+                     c->d_gt.get());
+  ZK_HIP_TRY("pairing", hipGetLastError());
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(out, c->d_gt, count * 72 * 8, hipMemcpyDeviceToHost, c->st));
+  if (codes_out) ZK_HIP_TRY("pairing", hipMemcpyAsync(codes_out, c->d_codes, count * 4, hipMemcpyDeviceToHost, c->st));
+  ZK_HIP_TRY("pairing", hipStreamSynchronize(c->st));
   return ZKHIP_OK;
 }
 
 int pairing_products(PairingCtx* c, const uint64_t* g1, const uint64_t* g2, int pairs, size_t count, uint64_t* out, char* errbuf, size_t errlen) {
-  for (size_t lo = 0; lo < count; lo += PAIRING_CHUNK) {
-    const size_t m = count - lo < PAIRING_CHUNK ? count - lo : PAIRING_CHUNK;
-    int rc = ctx_reserve(c, m, errbuf, errlen);
+  return for_each_chunk(count, PAIRING_CHUNK, [&](size_t lo, size_t m) -> int {
+    const int rc = reserve_chunk(c, m, false, false, errbuf, errlen);
     if (rc != ZKHIP_OK) return rc;
-    PAIR_HIP(hipMemcpyAsync(c->d_g1, g1 + lo * pairs * 24, m * pairs * 192, hipMemcpyHostToDevice, c->st));
-    PAIR_HIP(hipMemcpyAsync(c->d_g2, g2 + lo * pairs * 24, m * pairs * 192, hipMemcpyHostToDevice, c->st));
-    if ((rc = run_products(c, pairs, m, out + lo * 72, nullptr, nullptr, errbuf, errlen)) != ZKHIP_OK) return rc;
-  }
-  return ZKHIP_OK;
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g1, g1 + lo * pairs * 24, m * pairs * 192, hipMemcpyHostToDevice, c->st));
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g2, g2 + lo * pairs * 24, m * pairs * 192, hipMemcpyHostToDevice, c->st));
+    return run_products(c, pairs, m, out + lo * 72, nullptr, nullptr, errbuf, errlen);
+  });
 }
 
 // checked == false: ok[i] = 1 / 0.  checked == true: ok[i] is the status byte of zkhip.h (ZKHIP_VERIFY_*), k_point_check runs on the staged
 // chunk in front of k_acc_terms and its codes flag the refused proofs for the kernels behind.
 int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, char* errbuf,
                          size_t errlen) {
-  using host::HFq;
   if (checked && !c->checked) {
     if (errbuf) snprintf(errbuf, errlen, "checked batches need a handle of zkhip_verifier_new_checked");
     return ZKHIP_ERR_STATE;
   }
   const size_t ni = c->n_inputs;
-  // the chunk also bounds the terms of a launch: 2^21 of them are 0.9 GB of work space
-  size_t chunk = PAIRING_CHUNK;
-  if (ni && chunk * ni > ((size_t)1 << 21)) chunk = (((size_t)1 << 21) / ni) ? ((size_t)1 << 21) / ni : 1;
-  uint64_t one[72] = {0};
-  HFq::one().to_limbs(one);
-  for (size_t lo = 0; lo < count; lo += chunk) {
-    const size_t m = count - lo < chunk ? count - lo : chunk;
-    int rc = ctx_reserve(c, m, errbuf, errlen);
+  return for_each_chunk(count, pairing_batch_chunk(ni), [&](size_t lo, size_t m) -> int {
+    int rc = reserve_chunk(c, m, false, checked, errbuf, errlen);
     if (rc != ZKHIP_OK) return rc;
-    if (ni && m * ni > c->in_cap) {
-      if (c->d_inputs) (void)hipFree(c->d_inputs);
-      if (c->d_terms) (void)hipFree(c->d_terms);
-      c->d_inputs = nullptr; c->d_terms = nullptr; c->in_cap = 0;
-      PAIR_HIP(hipMalloc(&c->d_inputs, m * ni * 48));
-      PAIR_HIP(hipMalloc(&c->d_terms, m * ni * sizeof(XYZZ)));
-      c->in_cap = m * ni;
-    }
-    c->h_g1.resize(m * 96); c->h_g2.resize(m * 96); c->h_gt.resize(m * 72);
-    for (size_t j = 0; j < m; j++) {
-      const uint64_t* pr = proofs + (lo + j) * 72;
-      uint64_t* p1 = &c->h_g1[j * 96];
-      uint64_t* p2 = &c->h_g2[j * 96];
-      memcpy(p1, pr, 192);           memcpy(p2, pr + 24, 192);            // e(A, B)
-      memset(p1 + 24, 0, 192);       memcpy(p2 + 24, c->neg_g2, 192);     // e(acc, -g2): k_acc_sum writes acc
-      memcpy(p1 + 48, c->alpha, 192); memcpy(p2 + 48, c->neg_beta, 192);  // e(alpha, -beta)
-      memcpy(p1 + 72, pr + 48, 192); memcpy(p2 + 72, c->neg_delta, 192);  // e(C, -delta)
-    }
-    PAIR_HIP(hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
-    PAIR_HIP(hipMemcpyAsync(c->d_g2, c->h_g2.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
-    const uint32_t* flags = checked ? reinterpret_cast<const uint32_t*>(c->d_codes) : nullptr;
-    if (ni) PAIR_HIP(hipMemcpyAsync(c->d_inputs, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
-    if (checked) {
-      c->h_codes.resize(m * 4);
-      hipLaunchKernelGGL(k_point_check, dim3(blocks_for(m * 3, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_inputs, ni, m * 3, 0, c->d_const,
-                         c->d_codes);
-    }
-    if (ni) hipLaunchKernelGGL(k_acc_terms, dim3(blocks_for(m * ni, 64)), dim3(64), 0, c->st, c->d_inputs, c->d_abc, ni, m * ni, c->d_terms, flags);
-    hipLaunchKernelGGL(k_acc_sum, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_terms, c->d_abc, ni, m, c->d_g1, flags);
+    stage_chunk(c, proofs + lo * 72, m, false, true);
+    c->h_gt.resize(m * 72);
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
+    if ((rc = upload_g2_and_inputs(c, inputs + lo * ni * 6, m, errbuf, errlen)) != ZKHIP_OK) return rc;
+    const uint32_t* flags = checked ? enqueue_point_check(c, m) : nullptr;
+    if (ni) hipLaunchKernelGGL(k_acc_terms, dim3(blocks_for(m * ni, 64)), dim3(64), 0, c->st, c->d_inputs.get(), c->d_abc.get(), ni, m * ni,
+                               c->d_terms.get(), flags);
+    hipLaunchKernelGGL(k_acc_sum, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_terms.get(), c->d_abc.get(), ni, m, c->d_g1.get(), flags);
     if ((rc = run_products(c, 4, m, c->h_gt.data(), flags, checked ? c->h_codes.data() : nullptr, errbuf, errlen)) != ZKHIP_OK) return rc;
-    for (size_t j = 0; j < m; j++) {
-      const bool is_one = memcmp(&c->h_gt[j * 72], one, sizeof one) == 0;
-      if (!checked) { ok[lo + j] = is_one ? 1 : 0; continue; }
-      const uint8_t refused = verify_refusal(&c->h_codes[j * 4]);
-      ok[lo + j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
-    }
-  }
-  return ZKHIP_OK;
+    chunk_verdicts(c, m, checked, ok + lo);
+    return ZKHIP_OK;
+  });
 }
 
 // One random-combination check of the whole batch.  Per chunk the device scales A and C by rho (k_rho_scale), runs the existing
@@ -634,80 +612,42 @@ int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* pr
     for (size_t j = 0; j < m; j++)
       if (!codes || !verify_refusal(codes + j * 4)) sums.add(rho + (lo + j) * 2, inputs + (lo + j) * ni * 6);
   };
-  for (size_t lo = 0; lo < count; lo += PAIRING_CHUNK) {
-    const size_t m = count - lo < PAIRING_CHUNK ? count - lo : PAIRING_CHUNK;
-    int rc = ctx_reserve(c, m, errbuf, errlen);
-    if (rc == ZKHIP_OK) rc = ctx_reserve_comb(c, m, errbuf, errlen);
+  const int rc_all = for_each_chunk(count, PAIRING_CHUNK, [&](size_t lo, size_t m) -> int {
+    int rc = reserve_chunk(c, m, true, checked, errbuf, errlen);
     if (rc != ZKHIP_OK) return rc;
-    // the staged chunk has the layout of pairing_verify_batch (k_point_check reads it): A and C in the first and the fourth G1 slot
-    c->h_g1.resize(m * 96); c->h_b.resize(m * 24);
-    if (checked) c->h_g2.resize(m * 96);
-    for (size_t j = 0; j < m; j++) {
-      const uint64_t* pr = proofs + (lo + j) * 72;
-      memcpy(&c->h_g1[j * 96], pr, 192);
-      memcpy(&c->h_g1[j * 96 + 72], pr + 48, 192);
-      memcpy(&c->h_b[j * 24], pr + 24, 192);
-      if (checked) memcpy(&c->h_g2[j * 96], pr + 24, 192);
-    }
-    PAIR_HIP(hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
-    PAIR_HIP(hipMemcpyAsync(c->d_b, c->h_b.data(), m * 192, hipMemcpyHostToDevice, c->st));
-    PAIR_HIP(hipMemcpyAsync(c->d_rho, rho + lo * 2, m * 16, hipMemcpyHostToDevice, c->st));
-    const uint32_t* flags = nullptr;
-    if (checked) {
-      if (ni && m * ni > c->in_cap) {
-        if (c->d_inputs) (void)hipFree(c->d_inputs);
-        if (c->d_terms) (void)hipFree(c->d_terms);
-        c->d_inputs = nullptr; c->d_terms = nullptr; c->in_cap = 0;
-        PAIR_HIP(hipMalloc(&c->d_inputs, m * ni * 48));
-        PAIR_HIP(hipMalloc(&c->d_terms, m * ni * sizeof(XYZZ)));
-        c->in_cap = m * ni;
-      }
-      PAIR_HIP(hipMemcpyAsync(c->d_g2, c->h_g2.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
-      if (ni) PAIR_HIP(hipMemcpyAsync(c->d_inputs, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
-      c->h_codes.resize(m * 4);
-      hipLaunchKernelGGL(k_point_check, dim3(blocks_for(m * 3, 64)), dim3(64), 0, c->st, c->d_g1, c->d_g2, c->d_inputs, ni, m * 3, 0, c->d_const,
-                         c->d_codes);
-      flags = reinterpret_cast<const uint32_t*>(c->d_codes);
-    }
-    hipLaunchKernelGGL(k_rho_scale, dim3(blocks_for(2 * m, 64)), dim3(64), 0, c->st, c->d_g1, c->d_rho, m, c->d_ra, c->d_rc, flags);
-    hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_ra, c->d_b, c->d_const + 72, m, c->d_pairs, c->d_inf, flags, 1);
-    hipLaunchKernelGGL(k_miller, dim3(blocks_for(m, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs, c->d_inf, 1, m, c->d_const, c->d_f);
-    {
-      const Fq* in = c->d_f;
-      Fq* out = c->d_f2;
-      for (size_t n = m;;) {
-        const size_t strips = (n + PAIRING_STRIP - 1) / PAIRING_STRIP;
-        hipLaunchKernelGGL(k_gt_product, dim3(blocks_for(strips, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, in, n, out,
-                           strips == 1 ? c->d_res : nullptr);
-        if (strips == 1) break;
-        n = strips;
-        Fq* t = const_cast<Fq*>(in); in = out; out = t;      // the values of the level before are dead: their buffer takes the next level
-      }
-    }
-    {
-      const XYZZ* in = c->d_rc;
-      XYZZ* out = c->d_rc2;
-      for (size_t n = m;;) {
-        const size_t strips = (n + PAIRING_STRIP - 1) / PAIRING_STRIP;
-        hipLaunchKernelGGL(k_g1_sum, dim3(blocks_for(strips, 64)), dim3(64), 0, c->st, in, n, out, strips == 1 ? c->d_res + 72 : nullptr);
-        if (strips == 1) break;
-        n = strips;
-        XYZZ* t = const_cast<XYZZ*>(in); in = out; out = t;
-      }
-    }
-    PAIR_HIP(hipGetLastError());
+    stage_chunk(c, proofs + lo * 72, m, true, checked);
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_b, c->h_b.data(), m * 192, hipMemcpyHostToDevice, c->st));
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_rho, rho + lo * 2, m * 16, hipMemcpyHostToDevice, c->st));
+    if (checked && (rc = upload_g2_and_inputs(c, inputs + lo * ni * 6, m, errbuf, errlen)) != ZKHIP_OK) return rc;
+    const uint32_t* flags = checked ? enqueue_point_check(c, m) : nullptr;
+    hipLaunchKernelGGL(k_rho_scale, dim3(blocks_for(2 * m, 64)), dim3(64), 0, c->st, c->d_g1.get(), c->d_rho.get(), m, c->d_ra.get(), c->d_rc.get(), flags);
+    hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_ra.get(), c->d_b.get(), c->d_const + 72, m, c->d_pairs.get(),
+                       c->d_inf.get(), flags, 1);
+    hipLaunchKernelGGL(k_miller, dim3(blocks_for(m, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs.get(), c->d_inf.get(), 1, m,
+                       c->d_const.get(), c->d_f.get());
+    reduce_tree(c->d_f.get(), c->d_f2.get(), m, [&](const Fq* in, size_t n, Fq* out, bool last) {
+      hipLaunchKernelGGL(k_gt_product, dim3(blocks_for(pairing_strips(n), PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, in, n, out,
+                         last ? c->d_res.get() : nullptr);
+    });
+    reduce_tree(c->d_rc.get(), c->d_rc2.get(), m, [&](const XYZZ* in, size_t n, XYZZ* out, bool last) {
+      hipLaunchKernelGGL(k_g1_sum, dim3(blocks_for(pairing_strips(n), 64)), dim3(64), 0, c->st, in, n, out, last ? c->d_res + 72 : nullptr);
+    });
+    ZK_HIP_TRY("pairing", hipGetLastError());
     uint64_t res[72 + 24];
-    PAIR_HIP(hipMemcpyAsync(res, c->d_res, sizeof res, hipMemcpyDeviceToHost, c->st));
-    if (checked) PAIR_HIP(hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));
+    ZK_HIP_TRY("pairing", hipMemcpyAsync(res, c->d_res, sizeof res, hipMemcpyDeviceToHost, c->st));
+    if (checked) ZK_HIP_TRY("pairing", hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));
     if (!checked) add_sums(lo, m, nullptr);
-    PAIR_HIP(hipStreamSynchronize(c->st));
+    ZK_HIP_TRY("pairing", hipStreamSynchronize(c->st));
     if (checked) {
       add_sums(lo, m, c->h_codes.data());
       if (status) for (size_t j = 0; j < m; j++) status[lo + j] = verify_refusal(&c->h_codes[j * 4]);
     }
     product = product * fq6_from_limbs(res);
     s_c = s_c.add(jac_from_limbs(res + 72));
-  }
+    return ZKHIP_OK;
+  });
+  if (rc_all != ZKHIP_OK) return rc_all;
   const auto t0 = std::chrono::steady_clock::now();
   const CombineKey key = {c->alpha, c->neg_g2, c->neg_beta, c->neg_delta, c->abc.data(), ni};
   fq6_to_limbs(combined_value(key, sums, s_c, product), value);
@@ -716,19 +656,7 @@ int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* pr
 }
 
 int pairing_fq6_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen) {
-  uint64_t *da = nullptr, *db = nullptr, *dr = nullptr;
-  hipError_t e = hipMalloc(&da, n * 576);
-  if (e == hipSuccess) e = hipMalloc(&db, n * 576);
-  if (e == hipSuccess) e = hipMalloc(&dr, n * 576);
-  if (e == hipSuccess) e = hipMemcpy(da, a, n * 576, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(db, b, n * 576, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_fq6_selftest, dim3(blocks_for(n, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, 0, op, da, db, n, dr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out, dr, n * 576, hipMemcpyDeviceToHost);
-  for (void* p : {(void*)da, (void*)db, (void*)dr}) if (p) (void)hipFree(p);
-  PAIR_HIP(e);
+  ZK_HIP_TRY("pairing", selftest_launch(k_fq6_selftest, PAIRING_WG, PAIRING_BLOCK, op, a, b, n, out));
   return ZKHIP_OK;
 }
 

@@ -21,6 +21,7 @@
 #include <string.h>
 #include <vector>
 
+#include "device_buffer.hpp"
 #include "pairing_bls.cuh"
 #include "pairing_bls.h"
 
@@ -214,83 +215,46 @@ __global__ void __launch_bounds__(NESTED_BLOCK) k_fq12_selftest(int op, const ui
   }
 }
 
-#define NEST_HIP(x)                                                                                   \
-  do {                                                                                                \
-    hipError_t e_ = (x);                                                                              \
-    if (e_ != hipSuccess) {                                                                           \
-      if (errbuf) snprintf(errbuf, errlen, "nested pairing: %s: %s", #x, hipGetErrorString(e_));      \
-      return ZKHIP_ERR_HIP;                                                                           \
-    }                                                                                                 \
-  } while (0)
-
-namespace {
-unsigned blocks_for(size_t n, size_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-}  // namespace
-
 // the constants and the key on the device, in elements of d_fr
 constexpr size_t NK_FROB = 0, NK_FIFTH = 12, NK_ALPHA = 13, NK_ABC0 = 15, NK_LINES = 17, NK_CHAIN = NK_LINES + 3 * NESTED_LINES * 4;
 
 struct NestedCtx {
-  hipStream_t st = nullptr;
-  Fr* d_fr = nullptr;               // constants, then the key (NK_*)
-  Fq12Op* d_prog = nullptr;
+  DeviceStream st;                            // in front of the buffers: destroyed behind them
+  DeviceBuffer<Fr> d_fr;                      // constants, then the key (NK_*)
+  DeviceBuffer<Fq12Op> d_prog;
   int n_ops = 0;
   bool has_key = false;
   size_t n_inputs = 0;
-  size_t cap = 0;                   // products (of four pairs) the work space holds
-  uint64_t *d_in1 = nullptr, *d_in2 = nullptr, *d_gt = nullptr;     // staged ABI limbs: proofs or G1 points / inputs or G2 points; GT values
-  Fr *d_g1 = nullptr, *d_f = nullptr;
-  NestedLine* d_lines = nullptr;
-  uint8_t* d_status = nullptr;      // cap x 4: per proof of a chunk of m at [0, m) and [m, 2 m) (prep, accumulator); per G2 point (products)
-  uint8_t* d_codes = nullptr;       // checked batches: four codes per proof (k_nested_point_check), read as one word per proof behind it
-  size_t codes_cap = 0;
+  // the work space of a chunk (nctx_reserve)
+  DeviceBuffer<uint64_t> d_in1, d_in2, d_gt;  // staged ABI limbs: proofs or G1 points / inputs or G2 points; GT values
+  DeviceBuffer<Fr> d_g1, d_f;
+  DeviceBuffer<NestedLine> d_lines;
+  DeviceBuffer<uint8_t> d_status;             // four per product: per proof of a chunk of m at [0, m) and [m, 2 m) (prep, accumulator); per G2 point (products)
+  DeviceBuffer<uint8_t> d_codes;              // checked batches: four codes per proof (k_nested_point_check), read as one word per proof behind it
   std::vector<uint64_t> h_gt;
   std::vector<uint8_t> h_status, h_codes;
 };
 
-static void nctx_release_work(NestedCtx* c) {
-  for (void* p : {(void*)c->d_in1, (void*)c->d_in2, (void*)c->d_gt, (void*)c->d_g1, (void*)c->d_f, (void*)c->d_lines, (void*)c->d_status, (void*)c->d_codes})
-    if (p) (void)hipFree(p);
-  c->d_in1 = c->d_in2 = c->d_gt = nullptr; c->d_g1 = c->d_f = nullptr; c->d_lines = nullptr; c->d_status = c->d_codes = nullptr; c->cap = c->codes_cap = 0;
-}
-
-// work space for `count` products of four pairs (a proof is one): 4 G2 points of 24 limbs or a proof's 48; 16 inputs of 6 limbs at most
-static int nctx_reserve(NestedCtx* c, size_t count, char* errbuf, size_t errlen) {
-  if (count <= c->cap) return ZKHIP_OK;
-  nctx_release_work(c);
-  NEST_HIP(hipMalloc(&c->d_in1, count * 48 * 8));
-  NEST_HIP(hipMalloc(&c->d_in2, count * 96 * 8));
-  NEST_HIP(hipMalloc(&c->d_gt, count * 72 * 8));
-  NEST_HIP(hipMalloc(&c->d_g1, count * 8 * sizeof(Fr)));
-  NEST_HIP(hipMalloc(&c->d_f, count * 12 * sizeof(Fr)));
-  NEST_HIP(hipMalloc(&c->d_lines, count * 4 * NESTED_LINES * sizeof(NestedLine)));
-  NEST_HIP(hipMalloc(&c->d_status, count * 4));
-  c->cap = count;
+// work space for `count` products of four pairs (a proof is one): 4 G2 points of 24 limbs or a proof's 48; 16 inputs of 6 limbs at most;
+// the codes only for a checked batch
+static int nctx_reserve(NestedCtx* c, size_t count, bool checked, char* errbuf, size_t errlen) {
+  ZK_HIP_TRY("nested pairing", c->d_in1.reserve(count * 48));
+  ZK_HIP_TRY("nested pairing", c->d_in2.reserve(count * 96));
+  ZK_HIP_TRY("nested pairing", c->d_gt.reserve(count * 72));
+  ZK_HIP_TRY("nested pairing", c->d_g1.reserve(count * 8));
+  ZK_HIP_TRY("nested pairing", c->d_f.reserve(count * 12));
+  ZK_HIP_TRY("nested pairing", c->d_lines.reserve(count * 4 * NESTED_LINES));
+  ZK_HIP_TRY("nested pairing", c->d_status.reserve(count * 4));
+  if (checked) ZK_HIP_TRY("nested pairing", c->d_codes.reserve(count * 4));
   return ZKHIP_OK;
 }
 
-// the codes of `count` proofs: only a checked batch asks for them
-static int nctx_reserve_codes(NestedCtx* c, size_t count, char* errbuf, size_t errlen) {
-  if (count <= c->codes_cap) return ZKHIP_OK;
-  if (c->d_codes) (void)hipFree(c->d_codes);
-  c->d_codes = nullptr; c->codes_cap = 0;
-  NEST_HIP(hipMalloc(&c->d_codes, count * 4));
-  c->codes_cap = count;
-  return ZKHIP_OK;
-}
-
-void nested_ctx_free(NestedCtx* c) {
-  if (!c) return;
-  nctx_release_work(c);
-  for (void* p : {(void*)c->d_fr, (void*)c->d_prog}) if (p) (void)hipFree(p);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  delete c;
-}
+void nested_ctx_free(NestedCtx* c) { delete c; }       // every buffer, then the stream
 
 size_t nested_ctx_num_inputs(const NestedCtx* c) { return c ? c->n_inputs : 0; }
 
 static int nctx_init(NestedCtx* c, const NestedKeyData* key, char* errbuf, size_t errlen) {
-  NEST_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  ZK_HIP_TRY("nested pairing", c->st.create());
   const bool has_key = key->alpha != nullptr;
   const size_t n = has_key ? NK_CHAIN + key->n_inputs * NESTED_INPUT_BITS_DEV * 2 : NK_ALPHA;
   std::vector<uint64_t> abi(n * 6);
@@ -304,19 +268,15 @@ static int nctx_init(NestedCtx* c, const NestedKeyData* key, char* errbuf, size_
   }
   const std::vector<Fq12Op> prog = fq12_final_exp_program();
   c->n_ops = (int)prog.size();
-  uint64_t* d_abi = nullptr;
-  NEST_HIP(hipMalloc(&c->d_fr, n * sizeof(Fr)));
-  NEST_HIP(hipMalloc(&c->d_prog, prog.size() * sizeof(Fq12Op)));
-  NEST_HIP(hipMalloc(&d_abi, n * 48));
-  hipError_t e = hipMemcpyAsync(d_abi, abi.data(), n * 48, hipMemcpyHostToDevice, c->st);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_prog, prog.data(), prog.size() * sizeof(Fq12Op), hipMemcpyHostToDevice, c->st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_nested_from_abi, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, d_abi, n, c->d_fr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->st);       // (abi and prog are read by the copies until here)
-  (void)hipFree(d_abi);
-  NEST_HIP(e);
+  DeviceBuffer<uint64_t> d_abi;
+  ZK_HIP_TRY("nested pairing", c->d_fr.reserve(n));
+  ZK_HIP_TRY("nested pairing", c->d_prog.reserve(prog.size()));
+  ZK_HIP_TRY("nested pairing", d_abi.reserve(n * 6));
+  ZK_HIP_TRY("nested pairing", hipMemcpyAsync(d_abi, abi.data(), n * 48, hipMemcpyHostToDevice, c->st));
+  ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_prog, prog.data(), prog.size() * sizeof(Fq12Op), hipMemcpyHostToDevice, c->st));
+  hipLaunchKernelGGL(k_nested_from_abi, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, d_abi.get(), n, c->d_fr.get());
+  ZK_HIP_TRY("nested pairing", hipGetLastError());
+  ZK_HIP_TRY("nested pairing", hipStreamSynchronize(c->st));       // (abi and prog are read by the copies until here)
   c->has_key = has_key;
   c->n_inputs = has_key ? key->n_inputs : 0;
   return ZKHIP_OK;
@@ -332,41 +292,40 @@ int nested_ctx_new(const NestedKeyData* key, NestedCtx** out, char* errbuf, size
 
 // Miller loop and final exponentiation of `count` products, GT values and `n_status` status bytes to the host
 static int nested_run(NestedCtx* c, const NestedMillerArgs& args, int pairs, size_t count, uint64_t* out, size_t n_status, char* errbuf, size_t errlen) {
-  hipLaunchKernelGGL(k_nested_miller, dim3(blocks_for(count, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, args, pairs, count, c->d_f);
-  hipLaunchKernelGGL(k_nested_final_exp, dim3(blocks_for(count, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, c->d_f, c->d_prog, c->n_ops,
-                     c->d_fr + NK_FROB, count, c->d_gt);
-  NEST_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_nested_miller, dim3(blocks_for(count, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, args, pairs, count, c->d_f.get());
+  hipLaunchKernelGGL(k_nested_final_exp, dim3(blocks_for(count, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, c->d_f.get(), c->d_prog.get(), c->n_ops,
+                     c->d_fr + NK_FROB, count, c->d_gt.get());
+  ZK_HIP_TRY("nested pairing", hipGetLastError());
   c->h_status.resize(n_status);
-  NEST_HIP(hipMemcpyAsync(out, c->d_gt, count * 72 * 8, hipMemcpyDeviceToHost, c->st));
-  NEST_HIP(hipMemcpyAsync(c->h_status.data(), c->d_status, n_status, hipMemcpyDeviceToHost, c->st));
-  NEST_HIP(hipStreamSynchronize(c->st));
+  ZK_HIP_TRY("nested pairing", hipMemcpyAsync(out, c->d_gt, count * 72 * 8, hipMemcpyDeviceToHost, c->st));
+  ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->h_status.data(), c->d_status, n_status, hipMemcpyDeviceToHost, c->st));
+  ZK_HIP_TRY("nested pairing", hipStreamSynchronize(c->st));
   return ZKHIP_OK;
 }
 
 int nested_products(NestedCtx* c, const uint64_t* g1, const uint64_t* g2, int pairs, size_t count, uint64_t* out, uint8_t* status, char* errbuf,
                     size_t errlen) {
-  for (size_t lo = 0; lo < count; lo += NESTED_CHUNK) {
-    const size_t m = count - lo < NESTED_CHUNK ? count - lo : NESTED_CHUNK, n = m * (size_t)pairs;
-    const int rc = nctx_reserve(c, m, errbuf, errlen);
+  return for_each_chunk(count, NESTED_CHUNK, [&](size_t lo, size_t m) -> int {
+    const size_t n = m * (size_t)pairs;
+    int rc = nctx_reserve(c, m, false, errbuf, errlen);
     if (rc != ZKHIP_OK) return rc;
-    NEST_HIP(hipMemcpyAsync(c->d_in1, g1 + lo * pairs * 12, n * 96, hipMemcpyHostToDevice, c->st));
-    NEST_HIP(hipMemcpyAsync(c->d_in2, g2 + lo * pairs * 24, n * 192, hipMemcpyHostToDevice, c->st));
-    hipLaunchKernelGGL(k_nested_from_abi, dim3(blocks_for(n * 2, 64)), dim3(64), 0, c->st, c->d_in1, n * 2, c->d_g1);
-    hipLaunchKernelGGL(k_nested_g2_lines, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_in2, n, c->d_lines, c->d_status);
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_in1, g1 + lo * pairs * 12, n * 96, hipMemcpyHostToDevice, c->st));
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_in2, g2 + lo * pairs * 24, n * 192, hipMemcpyHostToDevice, c->st));
+    hipLaunchKernelGGL(k_nested_from_abi, dim3(blocks_for(n * 2, 64)), dim3(64), 0, c->st, c->d_in1.get(), n * 2, c->d_g1.get());
+    hipLaunchKernelGGL(k_nested_g2_lines, dim3(blocks_for(n, 64)), dim3(64), 0, c->st, c->d_in2.get(), n, c->d_lines.get(), c->d_status.get());
     NestedMillerArgs args = {};
     for (int p = 0; p < pairs; p++) {
       args.g1[p] = c->d_g1 + p * 2; args.g1_stride[p] = (size_t)pairs * 2;
       args.lines[p] = c->d_lines + (size_t)p * NESTED_LINES; args.line_stride[p] = (size_t)pairs * NESTED_LINES;
     }
-    int rc2 = nested_run(c, args, pairs, m, out + lo * 72, n, errbuf, errlen);
-    if (rc2 != ZKHIP_OK) return rc2;
+    if ((rc = nested_run(c, args, pairs, m, out + lo * 72, n, errbuf, errlen)) != ZKHIP_OK) return rc;
     for (size_t j = 0; j < m; j++) {
       uint8_t s = 0;
       for (int p = 0; p < pairs; p++) s |= c->h_status[j * pairs + p];
       status[lo + j] = s;
     }
-  }
-  return ZKHIP_OK;
+    return ZKHIP_OK;
+  });
 }
 
 // checked: k_nested_point_check runs on the staged chunk in front, k_nested_prep_checked takes k_nested_prep's place, and ok[i] is the
@@ -382,25 +341,24 @@ int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* pr
   uint64_t one[72] = {0};
   memcpy(one, FrParams::ONE64, 48);
   const NestedLine* key_lines = reinterpret_cast<const NestedLine*>(c->d_fr + NK_LINES);
-  for (size_t lo = 0; lo < count; lo += NESTED_CHUNK) {
-    const size_t m = count - lo < NESTED_CHUNK ? count - lo : NESTED_CHUNK;
-    const int rc = nctx_reserve(c, m, errbuf, errlen);
+  return for_each_chunk(count, NESTED_CHUNK, [&](size_t lo, size_t m) -> int {
+    int rc = nctx_reserve(c, m, checked, errbuf, errlen);
     if (rc != ZKHIP_OK) return rc;
-    NEST_HIP(hipMemcpyAsync(c->d_in1, proofs + lo * 48, m * 48 * 8, hipMemcpyHostToDevice, c->st));
-    if (ni) NEST_HIP(hipMemcpyAsync(c->d_in2, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_in1, proofs + lo * 48, m * 48 * 8, hipMemcpyHostToDevice, c->st));
+    if (ni) ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_in2, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
     if (checked) {
-      const int rc1 = nctx_reserve_codes(c, m, errbuf, errlen);
-      if (rc1 != ZKHIP_OK) return rc1;
-      hipLaunchKernelGGL(k_nested_point_check, dim3(blocks_for(4 * m, 64)), dim3(64), 0, c->st, c->d_in1, c->d_in2, ni, m, c->d_fr, c->d_codes);
-      hipLaunchKernelGGL(k_nested_prep_checked, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1, m, reinterpret_cast<const uint32_t*>(c->d_codes),
-                         c->d_fr + NK_ALPHA, c->d_g1, c->d_lines, c->d_status);
+      hipLaunchKernelGGL(k_nested_point_check, dim3(blocks_for(4 * m, 64)), dim3(64), 0, c->st, c->d_in1.get(), c->d_in2.get(), ni, m, c->d_fr.get(),
+                         c->d_codes.get());
+      hipLaunchKernelGGL(k_nested_prep_checked, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1.get(), m,
+                         reinterpret_cast<const uint32_t*>(c->d_codes.get()), c->d_fr + NK_ALPHA, c->d_g1.get(), c->d_lines.get(), c->d_status.get());
       c->h_codes.resize(m * 4);
-      NEST_HIP(hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));     // (nested_run synchronises)
+      ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));     // (nested_run synchronises)
     } else {
-      hipLaunchKernelGGL(k_nested_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1, m, c->d_fr, c->d_g1, c->d_lines, c->d_status);
+      hipLaunchKernelGGL(k_nested_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1.get(), m, c->d_fr.get(), c->d_g1.get(), c->d_lines.get(),
+                         c->d_status.get());
     }
-    hipLaunchKernelGGL(k_nested_acc, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in2, ni, m, c->d_fr + NK_ABC0, c->d_fr + NK_CHAIN, c->d_g1,
-                       c->d_status + m);
+    hipLaunchKernelGGL(k_nested_acc, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in2.get(), ni, m, c->d_fr + NK_ABC0, c->d_fr + NK_CHAIN,
+                       c->d_g1.get(), c->d_status + m);
     NestedMillerArgs args = {};
     args.g1[0] = c->d_g1;     args.g1_stride[0] = 6; args.lines[0] = c->d_lines;                    args.line_stride[0] = NESTED_LINES;   // e(A, B)
     args.g1[1] = c->d_g1 + 2; args.g1_stride[1] = 6; args.lines[1] = key_lines + 2 * NESTED_LINES;  args.line_stride[1] = 0;              // e(acc, -g2)
@@ -409,8 +367,7 @@ int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* pr
     args.standin = key_lines;
     args.status = c->d_status;
     c->h_gt.resize(m * 72);
-    const int rc2 = nested_run(c, args, 4, m, c->h_gt.data(), 2 * m, errbuf, errlen);
-    if (rc2 != ZKHIP_OK) return rc2;
+    if ((rc = nested_run(c, args, 4, m, c->h_gt.data(), 2 * m, errbuf, errlen)) != ZKHIP_OK) return rc;
     for (size_t j = 0; j < m; j++) {
       const uint8_t prep = c->h_status[j];
       const uint8_t s = (prep & NESTED_OFF_CURVE) ? NESTED_OFF_CURVE : (uint8_t)(prep | c->h_status[m + j]);
@@ -424,24 +381,12 @@ int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* pr
       status[lo + j] = refused ? 0 : s;
       ok[lo + j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
     }
-  }
-  return ZKHIP_OK;
+    return ZKHIP_OK;
+  });
 }
 
 int nested_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen) {
-  uint64_t *da = nullptr, *db = nullptr, *dr = nullptr;
-  hipError_t e = hipMalloc(&da, n * 576);
-  if (e == hipSuccess) e = hipMalloc(&db, n * 576);
-  if (e == hipSuccess) e = hipMalloc(&dr, n * 576);
-  if (e == hipSuccess) e = hipMemcpy(da, a, n * 576, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(db, b, n * 576, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_fq12_selftest, dim3(blocks_for(n, NESTED_WG)), dim3(NESTED_BLOCK), 0, 0, op, da, db, n, dr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out, dr, n * 576, hipMemcpyDeviceToHost);
-  for (void* p : {(void*)da, (void*)db, (void*)dr}) if (p) (void)hipFree(p);
-  NEST_HIP(e);
+  ZK_HIP_TRY("nested pairing", selftest_launch(k_fq12_selftest, NESTED_WG, NESTED_BLOCK, op, a, b, n, out));
   return ZKHIP_OK;
 }
 

@@ -9,8 +9,10 @@
 // the four Miller loops share one accumulator (one Fq6 squaring per bit for the whole product).
 #pragma once
 #include <errno.h>
+#include <string.h>
 #include <sys/random.h>
 
+#include <array>
 #include <thread>
 #include <vector>
 
@@ -246,9 +248,66 @@ inline int point_check_host(const uint64_t* p, bool g2) {
   return HJac::from_affine(x, y).mul_canonical(FqParams::R_ORDER64, 6).is_inf() ? 0 : ZKHIP_VERIFY_NOT_ORDER_R;
 }
 
+// The codes of a checked proof's four elements (A, B, C, the inputs as one) on the host: what k_point_check writes for it, and what
+// verify_refusal (pairing.cuh) turns into its status byte
+inline void proof_check_codes_host(const uint64_t* proof /* 72 */, const uint64_t* inputs, size_t n_inputs, uint8_t e[4]) {
+  e[0] = (uint8_t)point_check_host(proof, false);
+  e[1] = (uint8_t)point_check_host(proof + 24, true);
+  e[2] = (uint8_t)point_check_host(proof + 48, false);
+  e[3] = ZKHIP_VERIFY_ACCEPT;
+  for (size_t i = 0; i < n_inputs; i++) if (HFr::geq_p(inputs + i * 6)) e[3] = ZKHIP_VERIFY_ENCODING;
+}
+
 // prod_i t(P_i, Q_i) == 1 ?
 inline bool pairing_product_is_one(const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2) {
   return pairing_product_value(g1, g2).is_one();
+}
+
+// ---- points and GT values in ABI limbs
+
+// -P (infinity stays infinity)
+inline void neg_point_abi(const uint64_t* p, uint64_t* o) {
+  memcpy(o, p, 96);
+  const HFq y = HFq::from_limbs(p + 12);
+  const bool inf = HFq::from_limbs(p).is_zero() && y.is_zero();
+  (inf ? y : y.neg()).to_limbs(o + 12);
+}
+
+// -g2, the second member of the pair of acc
+inline void neg_g2_generator(uint64_t o[24]) {
+  uint64_t g2[24];
+  memcpy(g2, FqParams::G2_GEN_X64, 96);
+  memcpy(g2 + 12, FqParams::G2_GEN_Y64, 96);
+  neg_point_abi(g2, o);
+}
+
+// a GT value (6 x 12 limbs) is one
+inline bool gt_is_one(const uint64_t* value) {
+  static const std::array<uint64_t, 72> one = [] {
+    std::array<uint64_t, 72> v = {};
+    HFq::one().to_limbs(v.data());
+    return v;
+  }();
+  return memcmp(value, one.data(), sizeof one) == 0;
+}
+
+// y^2 = x^3 - 1 (G1) or x^3 + 4 (G2), both over Fq; the all-zero encoding of the point at infinity passes
+inline bool on_curve_abi(const uint64_t* p, bool g2) {
+  const HFq x = HFq::from_limbs(p), y = HFq::from_limbs(p + 12);
+  if (x.is_zero() && y.is_zero()) return true;
+  const HFq rhs = x.sqr() * x + (g2 ? HFq::one().dbl().dbl() : HFq::one().neg());
+  return y.sqr() == rhs;
+}
+
+// well-formedness (libsnark: is_well_formed()) of a key's n_inputs + 4 points and of a proof's three: an off-curve point would put
+// the pairing in an invalid-curve setting
+inline bool key_on_curve(const uint64_t* alpha, const uint64_t* beta, const uint64_t* delta, const uint64_t* abc, size_t n_inputs) {
+  bool wf = on_curve_abi(alpha, false) && on_curve_abi(beta, true) && on_curve_abi(delta, true);
+  for (size_t i = 0; i <= n_inputs && wf; i++) wf = on_curve_abi(abc + i * 24, false);
+  return wf;
+}
+inline bool proof_on_curve(const uint64_t* proof /* 72 */) {
+  return on_curve_abi(proof, false) && on_curve_abi(proof + 24, true) && on_curve_abi(proof + 48, false);
 }
 
 }  // namespace host

@@ -914,9 +914,11 @@ def bls12_377_groth16_verify_checked(nested_vk, inputs, proof):
 
 
 # the nested batch verifier's kernels (zecale_amd/csrc/pairing_bls.cuh / pairing_bls.hip): a verification owns sixteen lanes, so one
-# wave holds NESTED_VERIFIER_GROUP of them and one 128-thread workgroup NESTED_VERIFIER_WORKGROUP
+# wave holds NESTED_VERIFIER_GROUP of them and one 128-thread workgroup NESTED_VERIFIER_WORKGROUP; a batch runs in chunks of
+# NESTED_VERIFIER_CHUNK proofs
 NESTED_VERIFIER_GROUP = 4
 NESTED_VERIFIER_WORKGROUP = 8
+NESTED_VERIFIER_CHUNK = 8192
 
 
 class NestedVerifier:
