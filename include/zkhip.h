@@ -720,6 +720,12 @@ int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n,
  * otherwise: 1 lockstep, 0 sliced, -1 not an Edwards launch. */
 int zkhip_internal_set_lockstep(int mode, int min_buckets);
 int zkhip_internal_last_acc_path(int* out);
+/* Test hook of the bucket reduction's tail (no counterpart): the two small weighted sums per bucket window by bit planes and
+ * R * hi + lo, alone.  items_affine: 2W groups of N affine points (24 limbs each, all-zero = infinity), the W hi
+ * groups first; item i of a group has weight i + 1.  out_jac[w] = 2^lo_bits sum_i (i+1) hi_w[i] + sum_i (i+1) lo_w[i], and, if total,
+ * out_jac[W + w] = sum_i lo_w[i] (36 limbs each).  edw 0: XYZZ points; 1: the Edwards model - the items go through chi, the results
+ * back through psi, and psi(chi(P)) = 2 P: every output is TWICE the sum above.  W in 1 .. 5, N a power of two in 2 .. 2048. */
+int zkhip_internal_msm_tail(int edw, const uint64_t* items_affine, int W, unsigned N, int lo_bits, int total, uint64_t* out_jac);
 /* Test hooks of the pairing kernels (no counterpart).
  * fq6_selftest: n independent operand sets through the per-lane bodies of pairing.cuh inside a real kernel, eight lanes per set:
  * op 0 = a b, 1 = a^2, 2 = a (b_0 + b_3 w^3 + b_4 w^4) (the sparse line product; b's other coefficients are ignored) in

@@ -506,4 +506,13 @@ int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n,
   return msm_field_selftest(field, limbs_in, n, limbs_out, t_err, sizeof t_err);
 }
 
+// Test hook of the bucket reduction's tail (msm.hip enqueue_tail)
+int zkhip_internal_msm_tail(int edw, const uint64_t* items_affine, int W, unsigned N, int lo_bits, int total, uint64_t* out_jac) {
+  BIND_CUR();
+  if (!items_affine || !out_jac || W < 1 || W > MSM_MAX_JOBS || N < 2 || N > 2048 || (N & (N - 1)) || lo_bits < 0 || lo_bits > 11)
+    return fail(ZKHIP_ERR_ARG, "W in 1 .. 5, N a power of two in 2 .. 2048, lo_bits in 0 .. 11");
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return msm_tail_selftest(edw, items_affine, W, N, lo_bits, total, out_jac, t_err, sizeof t_err);
+}
+
 }  // extern "C"

@@ -61,7 +61,7 @@ struct MsmCtx {      // all zeros: no plan
   uint32_t lock_min_live;       // non-empty buckets a launch needs for the lockstep route: two waves for every SIMD of the chip
   uint2* fix_list;      // (first, last) F slot of the buckets cut into more than four F pieces (k_accumulate -> k_fixup_fold)
   uint2* fix_short;     // (first F slot, number of F pieces) of the buckets with two to four (k_accumulate -> k_fixup_fold)
-  uint32_t *buckets, *segS[2], *segR, *sumR[2], *Rlevels, *colS[2], *hilo;
+  uint32_t *buckets, *segS[2], *colS[2], *hilo, *planes[2];
   uint64_t *win_abi, *win_host;
   // batched-affine levels in front of the XYZZ accumulation (k_affine_level): per level the bucket counts / offsets of its output,
   // two point buffers used alternately, the prefix-product scratch of one launch
@@ -136,6 +136,9 @@ static inline const EdwPacked* msm_edw_at(const EdwPacked* t, size_t i) {
 // Fq multiplications per second of the whole device, measured now: dependent fp_mul chains at two waves per SIMD (~25 ms)
 int msm_field_selftest(int field, const uint32_t* in_host, size_t n, uint32_t* out_host, char* errbuf, size_t errlen);
 int msm_measure_fqmul_rate(double* fq_mul_per_s, char* errbuf, size_t errlen);
+// test hook: the tail of the bucket reduction (bit planes, R * hi + lo) on 2W groups of N affine ABI points given on the host;
+// an Edwards run (edw != 0) returns twice the sums.  out_jac: W points (+ W plain totals of the lo groups if total), 36 limbs each
+int msm_tail_selftest(int edw, const uint64_t* items_aff, int W, uint32_t N, int lo_bits, int total, uint64_t* out_jac, char* errbuf, size_t errlen);
 
 int fixed_base_mul(const uint64_t base_aff[24], const uint64_t* d_scalars, size_t n, int montgomery, uint64_t* d_out,
                    char* errbuf, size_t errlen);

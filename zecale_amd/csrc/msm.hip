@@ -10,8 +10,8 @@
 //   k_bucket_sort       a workgroup per part orders its entries by bucket: bucket-ordered list of (point index, sign), offsets, counts
 //   k_accumulate        one lane per fixed-size SLICE of the sorted list: XYZZ mixed additions   <-- dominant
 //   k_fixup_fold / k_fixup  stitch the buckets that slice boundaries cut
-//   k_sum / k_seg       bucket reduction  sum_j (j+1) B_j : two-level split of the bucket index, then L-ary running sums
-//   k_window_combine / k_hilo_combine   per bucket window: Horner over the levels, R * hi + lo
+//   k_sum_lds / k_sum   bucket reduction  sum_j (j+1) B_j : two-level split of the bucket index, row and column trees
+//   k_plane_sum / k_plane_combine   the two small weighted sums per bucket window by bit planes, then R * hi + lo
 // Plain base sets: one bucket window per digit position, and the last step, sum_w 2^(off_w) W_w (about 380 serial
 // doublings of ONE point), runs on the host.  Table-backed base sets: ONE bucket window for all digit positions (nothing
 // left to combine), and up to five MSMs share one launch sequence with a bucket window each (msm_launch_multi).
@@ -1076,29 +1076,6 @@ __global__ void __launch_bounds__(256, 2) k_fixup_edw(ZK_FIXUP_PARAMS, const uin
   fixup_impl<true>(offsets, counts, goff, nb, S_host, tight, T, slots, stride, wf);
 }
 
-// Segment pass of the bucket reduction.  in: n_in items (XYZZ limb-major, stride n_in), grouped in
-// runs of L.  For segment t: S_t = sum_u item[tL+u],  R_t = sum_u (u + o) item[tL+u]   (o in {0,1}).
-// The running sums live in the output arrays themselves (memory-resident accumulators).
-#define ZK_SEG_PARAMS uint32_t* __restrict__ in, size_t n_in, uint32_t in_stride, int L, int o, uint32_t* __restrict__ outS, uint32_t* __restrict__ outR
-template <bool QUAD, bool EDW>
-__device__ __forceinline__ void seg_impl(ZK_SEG_PARAMS) {
-  ADD_SCRATCH_DECL(QUAD || EDW);
-  size_t n_out = n_in / L;
-  size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x, t = QUAD ? gt >> 2 : gt;    // one lane / quad per segment
-  const uint32_t q = (uint32_t)(gt & 3);
-  if (t >= n_out) return;
-  XyzzRef run = make_ref(outS, (uint32_t)n_out, (uint32_t)t), acc = make_ref(outR, (uint32_t)n_out, (uint32_t)t);
-  pt_set_inf<QUAD>(run, q);
-  pt_set_inf<QUAD>(acc, q);
-  for (int u = L - 1; u >= 0; u--) {
-    XyzzRef it = make_ref(in, in_stride, (uint32_t)(t * L + u));
-    pt_add<QUAD, EDW>(run, it, q, sc);
-    if (u + o > 0) pt_add<QUAD, EDW>(acc, run, q, sc);
-  }
-}
-template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_seg(ZK_SEG_PARAMS) { seg_impl<QUAD, false>(in, n_in, in_stride, L, o, outS, outR); }
-template <bool QUAD> __global__ void __launch_bounds__(256, 2) k_seg_edw(ZK_SEG_PARAMS) { seg_impl<QUAD, true>(in, n_in, in_stride, L, o, outS, outR); }
-
 // out[t] = sum_u in[i(t) + u * row_len],  i(t) = (t / row_len) * (L * row_len) + (t % row_len).
 // row_len = 1: sums of L consecutive items (row sums);  row_len = R: for items laid out [g][h][R] it sums L
 // consecutive h for every (g, h / L, lo) (column sums).  in: n_in items with row stride in_stride words.
@@ -1174,48 +1151,91 @@ __global__ void __launch_bounds__(256, 2) k_place_hilo(uint32_t* __restrict__ ro
   }
 }
 
-// per window w: out[w] = R[0][w] + L_0 (R[1][w] + L_1 (R[2][w] + ...)).
-// R_all: `levels` arrays of W XYZZ points each, limb-major with stride W, consecutive (108*W words apart);
-// `work`: scratch for W accumulators.
-struct LevelShifts { uint8_t log_l[32]; };
-#define ZK_WCOMB_PARAMS uint32_t* __restrict__ R_all, int levels, int G, LevelShifts ls, uint32_t* __restrict__ work /* G accumulators, result left here */
+// The two small weighted sums by bit planes (msm_plan.hpp): F_g = sum_i (i+1) item_{g,i} = sum_j 2^j P_{g,j}, where plane j of group
+// g sums the items whose weight i+1 has bit j set.  k_plane_sum is one level of the planes' trees, a quad per output:
+//   out[p][r] = sum_{u < L} in[p'][r L + u],  r < per_plane / L
+// The FIRST level (select != 0) reads the one item array for every plane (p' = 0; item i of a group has weight i % left + 1) and takes
+// the items whose weight has bit p set - every item for plane total_plane (a NAF plan's plain total; -1: none).  The later levels
+// are ordinary sums inside each plane (p' = p).  Ordering between the levels comes from the stream alone.
+#define ZK_PLANE_PARAMS                                                                                                  \
+  uint32_t* __restrict__ in, uint32_t in_stride, uint32_t per_plane /* G groups x `left` items */, uint32_t left, int L, \
+      int planes, int select, int total_plane, uint32_t* __restrict__ out
 template <bool EDW>
-__device__ __forceinline__ void window_combine_impl(uint32_t* __restrict__ R_all, int levels, int G, const LevelShifts& ls, uint32_t* __restrict__ work) {
-  int gt = blockIdx.x * blockDim.x + threadIdx.x, w = gt >> 2;   // one quad per group
-  const uint32_t q = (uint32_t)(gt & 3);
-  if (w >= G) return;
-  XyzzRef acc = make_ref(work, (uint32_t)G, (uint32_t)w);
-  mem_st_lane(acc, q, mem_ld_lane(make_ref(R_all + (size_t)(levels - 1) * 108 * G, (uint32_t)G, (uint32_t)w), q));
-  for (int k = levels - 2; k >= 0; k--) {
-    for (int d = 0; d < ls.log_l[k]; d++) pt_dbl_quad<EDW>(acc, q);
-    pt_add<true, EDW>(acc, make_ref(R_all + (size_t)k * 108 * G, (uint32_t)G, (uint32_t)w), q, AddScratch{nullptr, nullptr});
+__device__ __forceinline__ void plane_sum_impl(ZK_PLANE_PARAMS) {
+  const uint32_t per_out = per_plane / (uint32_t)L, n_out = (uint32_t)planes * per_out;
+  const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x, t = gt >> 2, q = gt & 3u;
+  if (t >= n_out) return;
+  const uint32_t p = t / per_out, r = t % per_out;
+  const XyzzRef acc = make_ref(out, n_out, t);
+  bool first = true;
+  for (int u = 0; u < L; u++) {
+    const uint32_t i = r * (uint32_t)L + (uint32_t)u;
+    if (select && (int)p != total_plane && !(((i % left) + 1u) >> p & 1u)) continue;
+    const XyzzRef it = make_ref(in, in_stride, select ? i : p * per_plane + i);
+    if (mem_is_inf(it)) continue;      // (an empty slot has only its ZZ / Z words cleared: it must not reach the output by a copy)
+    if (first) pt_copy<true>(acc, it, q);
+    else pt_add<true, EDW>(acc, it, q, AddScratch{nullptr, nullptr});
+    first = false;
   }
+  if (first) pt_set_inf<true>(acc, q);
 }
-__global__ void __launch_bounds__(64, 2) k_window_combine(ZK_WCOMB_PARAMS) { window_combine_impl<false>(R_all, levels, G, ls, work); }
-__global__ void __launch_bounds__(64, 2) k_window_combine_edw(ZK_WCOMB_PARAMS) { window_combine_impl<true>(R_all, levels, G, ls, work); }
+__global__ void __launch_bounds__(256, 2) k_plane_sum(ZK_PLANE_PARAMS) { plane_sum_impl<false>(in, in_stride, per_plane, left, L, planes, select, total_plane, out); }
+__global__ void __launch_bounds__(256, 2) k_plane_sum_edw(ZK_PLANE_PARAMS) { plane_sum_impl<true>(in, in_stride, per_plane, left, L, planes, select, total_plane, out); }
 
-// per window: R * (hi part) + (lo part), converted to ABI limbs
-// total (optional): the plain sums of the 2W groups (the last S of the k_seg chain); the lo group's is sum_b S_b of the window and
-// goes out behind the W weighted sums (the NAF finish needs it)
-#define ZK_HCOMB_PARAMS                                                                                                \
-  uint32_t* __restrict__ work /* 2W */, int W, int lo_bits, uint64_t* __restrict__ out_abi /* W x 4 x 12 u64 (+ W more with total) */, \
-      uint32_t* __restrict__ total /* 2W or null */
-template <bool EDW>
-__device__ __forceinline__ void hilo_combine_impl(ZK_HCOMB_PARAMS) {
-  int gt = blockIdx.x * blockDim.x + threadIdx.x, w = gt >> 2;
-  const uint32_t q = (uint32_t)(gt & 3);
-  if (w >= W) return;
-  XyzzRef hi = make_ref(work, (uint32_t)(2 * W), (uint32_t)w), lo = make_ref(work, (uint32_t)(2 * W), (uint32_t)(W + w));
-  for (int d = 0; d < lo_bits; d++) pt_dbl_quad<EDW>(hi, q);
-  pt_add<true, EDW>(hi, lo, q, AddScratch{nullptr, nullptr});
-  uint64_t* o = out_abi + (size_t)w * 48;
-  fp_to_abi<FqParams>(mem_ld_lane(hi, q), o + 12 * q);            // lane q converts coordinate q
-  if (total) fp_to_abi<FqParams>(mem_ld_lane(make_ref(total, (uint32_t)(2 * W), (uint32_t)(W + w)), q), out_abi + (size_t)(W + w) * 48 + 12 * q);
-}
+// The planes of one bucket window recombined, one workgroup per window w: `sums` holds one point per (plane, group), point
+// p * 2W + g.  Quad s < 2 wp takes weight plane j = s % wp of the hi group (s < wp: group w) or of the lo group (group W + w)
+// and doubles it j times, the hi group's lo_bits times more (the window's sum is R * hi + lo, R = 2^lo_bits): side by side, not
+// one Horner chain.  Then the 2 wp points are summed pairwise in place, a barrier between the rounds (the points live in global
+// memory, coherent inside a CU, as in k_fixup_fold), and quad 0 writes the ABI limbs.  has_total: plane wp of the lo group is
+// sum_b S_b of the window and goes out behind the W weighted sums (the NAF finish needs it).
 // (an Edwards launch leaves (X : Y : Z : T) per window in out_abi: the host applies psi, edw_abi_to_jac)
-__global__ void __launch_bounds__(64, 2) k_hilo_combine(ZK_HCOMB_PARAMS) { hilo_combine_impl<false>(work, W, lo_bits, out_abi, total); }
-__global__ void __launch_bounds__(64, 2) k_hilo_combine_edw(ZK_HCOMB_PARAMS) { hilo_combine_impl<true>(work, W, lo_bits, out_abi, total); }
+#define ZK_PCOMB_PARAMS \
+  uint32_t* __restrict__ sums, int W, int wp /* weight planes, 2 wp <= 64 */, int has_total, int lo_bits, uint64_t* __restrict__ out_abi
+template <bool EDW>
+__device__ __forceinline__ void plane_combine_impl(ZK_PCOMB_PARAMS) {
+  const uint32_t w = blockIdx.x, s = threadIdx.x >> 2, q = threadIdx.x & 3u, n = 2u * (uint32_t)wp;
+  const uint32_t stride = (uint32_t)((wp + has_total) * 2 * W);
+  auto ref = [&](uint32_t k) { return make_ref(sums, stride, (k % (uint32_t)wp) * 2u * (uint32_t)W + (k < (uint32_t)wp ? w : (uint32_t)W + w)); };
+  if (s < n) {
+    const XyzzRef a = ref(s);
+    const int dbl = (int)(s % (uint32_t)wp) + (s < (uint32_t)wp ? lo_bits : 0);
+    for (int d = 0; d < dbl; d++) pt_dbl_quad<EDW>(a, q);
+  }
+#pragma unroll 1
+  for (uint32_t d = 1; d < n; d <<= 1) {
+    __threadfence_block();
+    __syncthreads();
+    if (s % (2 * d) == 0 && s + d < n) pt_add<true, EDW>(ref(s), ref(s + d), q, AddScratch{nullptr, nullptr});
+  }
+  if (s != 0) return;
+  fp_to_abi<FqParams>(mem_ld_lane(ref(0), q), out_abi + (size_t)w * 48 + 12 * q);            // lane q converts coordinate q
+  if (has_total) fp_to_abi<FqParams>(mem_ld_lane(make_ref(sums, stride, (uint32_t)(wp * 2 * W + W) + w), q), out_abi + (size_t)(W + w) * 48 + 12 * q);
+}
+__global__ void __launch_bounds__(256, 2) k_plane_combine(ZK_PCOMB_PARAMS) { plane_combine_impl<false>(sums, W, wp, has_total, lo_bits, out_abi); }
+__global__ void __launch_bounds__(256, 2) k_plane_combine_edw(ZK_PCOMB_PARAMS) { plane_combine_impl<true>(sums, W, wp, has_total, lo_bits, out_abi); }
 
+// Test hook (msm_tail_selftest): n affine points in ABI form (all-zero = infinity) -> points of the reduction's arrays (limb-major,
+// stride n), XYZZ (x, y, 1, 1) or, edw != 0, chi of the point in extended coordinates (4 x_e : 4 y_e : 4 : 4 x_e y_e).
+__global__ void __launch_bounds__(256) k_tail_items(const uint64_t* __restrict__ in, uint32_t n, int edw, uint32_t* __restrict__ out, uint32_t* __restrict__ bad) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t x[12], y[12], nz = 0;
+#pragma unroll
+  for (int k = 0; k < 12; k++) { x[k] = in[(size_t)i * 24 + k]; y[k] = in[(size_t)i * 24 + 12 + k]; nz |= x[k] | y[k]; }
+  const XyzzRef dst = make_ref(out, n, i);
+  if (nz == 0) { mem_set_inf(dst); return; }
+  const Fq fx = fp_cond_sub_p(fp_from_abi<FqParams>(x)), fy = fp_cond_sub_p(fp_from_abi<FqParams>(y));
+  if (!edw) {
+    mem_st(dst, CX, fx); mem_st(dst, CY, fy); mem_st(dst, CZZ, fp_one<FqParams>()); mem_st(dst, CZZZ, fp_one<FqParams>());
+    return;
+  }
+  EdwPacked e;
+  if (!edw_from_affine(fx, fy, &e)) atomicAdd(bad, 1u);
+  const Fq ymx = edw_ld(e.ymx), ypx = edw_ld(e.ypx), two = fp_dbl(fp_one<FqParams>());
+  const Fq dx = fp_sub<FqParams, 2>(ypx, ymx);                                                // 2 x_e [3]
+  const Fq sy = fp_add(ypx, ymx);                                                             // 2 y_e [2]
+  mem_st(dst, CX, fp_mul(dx, two)); mem_st(dst, CY, fp_mul(sy, two)); mem_st(dst, CZZ, fp_mul(two, two)); mem_st(dst, CZZZ, fp_mul(dx, sy));
+}
 // ---- batch fixed-base scalar multiplication: out[i] = k_i * G (the inner loop of Groth16 setup:
 // reference libzecale/circuits/aggregator_circuit.tcc:100-109 -> wsnarkT::generate_setup) ----
 // table[w*15 + (d-1)] = d * 2^(4w) * G, w < 95, d = 1..15 (packed device form).
@@ -1741,13 +1761,10 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   HIP_TRY(hipMalloc(&ctx->fix_short, plan::cap_fix_short(ctx->T) * sizeof(uint2)));
   HIP_TRY(hipMalloc(&ctx->segS[0], plan::cap_segS(nb) * pt));
   HIP_TRY(hipMalloc(&ctx->segS[1], plan::cap_segS(nb) * pt));
-  HIP_TRY(hipMalloc(&ctx->segR, plan::cap_segR(nb, ctx->W) * pt));
-  HIP_TRY(hipMalloc(&ctx->sumR[0], plan::cap_sumR(nb, ctx->W, ctx->L) * pt));
-  HIP_TRY(hipMalloc(&ctx->sumR[1], plan::cap_sumR(nb, ctx->W, ctx->L) * pt));
-  HIP_TRY(hipMalloc(&ctx->Rlevels, plan::cap_Rlevels(ctx->W) * pt));
   HIP_TRY(hipMalloc(&ctx->colS[0], plan::cap_segS(nb) * pt));
   HIP_TRY(hipMalloc(&ctx->colS[1], plan::cap_segS(nb) * pt));
   HIP_TRY(hipMalloc(&ctx->hilo, plan::cap_hilo(ctx->W, c) * pt));
+  for (int k = 0; k < 2; k++) HIP_TRY(hipMalloc(&ctx->planes[k], plan::cap_tail(ctx->W, (size_t)1 << plan::lo_bits(c), k) * pt));
   HIP_TRY(hipMalloc(&ctx->win_abi, (size_t)ctx->W * 48 * 8 * 2));       // (the second half: the plain totals of a NAF plan)
   HIP_TRY(hipHostMalloc(&ctx->win_host, (size_t)ctx->W * 48 * 8 * 2));
   ctx->planned = true;
@@ -1756,7 +1773,7 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
 
 void msm_plan_free(MsmCtx* ctx) {
   void* ptrs[] = {ctx->hist, ctx->pairs, ctx->counts, ctx->offsets, ctx->block_tot, ctx->entries, ctx->buckets,
-                  ctx->segS[0], ctx->segS[1], ctx->segR, ctx->sumR[0], ctx->sumR[1], ctx->Rlevels, ctx->win_abi,
+                  ctx->segS[0], ctx->segS[1], ctx->planes[0], ctx->planes[1], ctx->win_abi,
                   ctx->colS[0], ctx->colS[1], ctx->hilo, ctx->pbuf[0], ctx->pbuf[1], ctx->aff_scratch,
                   ctx->lcnt[0], ctx->lcnt[1], ctx->lcnt[2], ctx->lcnt[3], ctx->loff[0], ctx->loff[1], ctx->loff[2], ctx->loff[3],
                   ctx->fix_list, ctx->fix_short, ctx->dbg_times, ctx->goff, ctx->prio_board, ctx->order, ctx->ord_hist};
@@ -1798,8 +1815,7 @@ static void enqueue_scan(hipStream_t st, const uint32_t* in, uint32_t* out, uint
 struct RedKernels {      // the stitching and reduction kernels that exist for XYZZ and for Edwards points (red_kernels)
   void (*fold_quad)(ZK_FOLD_PARAMS), (*fold)(ZK_FOLD_PARAMS);
   void (*sum_lds)(ZK_SUM_PARAMS), (*sum_quad)(ZK_SUM_PARAMS);
-  void (*seg)(ZK_SEG_PARAMS), (*seg_quad)(ZK_SEG_PARAMS);
-  void (*window_combine)(ZK_WCOMB_PARAMS), (*hilo_combine)(ZK_HCOMB_PARAMS);
+  void (*plane_sum)(ZK_PLANE_PARAMS), (*plane_combine)(ZK_PCOMB_PARAMS);
 };
 struct Launch {      // what the stages of one msm_launch_multi share
   int K;                                  // jobs of this launch (<= ctx->K)
@@ -1926,8 +1942,7 @@ static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
 static RedKernels red_kernels(bool edw) {
   return {edw ? k_fixup_fold_edw<true> : k_fixup_fold<true>, edw ? k_fixup_fold_edw<false> : k_fixup_fold<false>,
           edw ? k_sum_lds_edw : k_sum_lds,                   edw ? k_sum_edw<true> : k_sum<true>,
-          edw ? k_seg_edw<false> : k_seg<false>,             edw ? k_seg_edw<true> : k_seg<true>,
-          edw ? k_window_combine_edw : k_window_combine,     edw ? k_hilo_combine_edw : k_hilo_combine};
+          edw ? k_plane_sum_edw : k_plane_sum,               edw ? k_plane_combine_edw : k_plane_combine};
 }
 
 // (4) stitching: fold the F pieces of the buckets that have several (lists made by k_accumulate), then L + F for every cut bucket
@@ -1969,10 +1984,27 @@ static uint32_t* enqueue_tree(MsmCtx* ctx, const Launch& lp, hipStream_t s, uint
   return in;
 }
 
+// The tail of the reduction: 2W groups of N items (limb-major, stride 2W N, weights index + 1; the hi groups first) -> the W window
+// results R * hi + lo in ABI limbs, W plain totals of the lo groups behind them if `total`.  By bit planes (msm_plan.hpp): one
+// k_plane_sum launch per tree level - at most six, N <= 2048 - and k_plane_combine, all on ONE stream, no events.
+// planes[0], planes[1]: cap_tail points each.
+static void enqueue_tail(const RedKernels& red, hipStream_t st, uint32_t* items, int W, uint32_t N, int lo_bits, bool total,
+                         uint32_t* const planes[2], uint64_t* out_abi) {
+  const int G = 2 * W, wp = plan::tail_weight_planes(N), P = plan::tail_planes(N, total);
+  uint32_t* in = items;
+  uint32_t in_stride = (uint32_t)G * N, left = N;
+  for (int level = 0; left > 1; level++) {
+    const int L = plan::tail_fan_in(left);
+    const size_t n_out = plan::tail_level_outputs(P, G, N, level);
+    hipLaunchKernelGGL(red.plane_sum, dim3(nblk(n_out * 4, 256)), dim3(256), 0, st, in, in_stride, (uint32_t)G * left, left, L, P, level == 0 ? 1 : 0,
+                       total ? wp : -1, planes[level & 1]);
+    in = planes[level & 1]; in_stride = (uint32_t)n_out; left /= (uint32_t)L;
+  }
+  hipLaunchKernelGGL(red.plane_combine, dim3(W), dim3(256), 0, st, in, W, wp, total ? 1 : 0, lo_bits, out_abi);
+}
+
 // (5) bucket reduction: (a) two-level split of the bucket index (row sums on stream 1, column sums on stream 2: plain trees), (b) the two
-// small weighted sums per window by recursive 4-ary running sums, F(items) = sum_t R_t + L * F0(S): the k_seg chain (stream 1) produces
-// one R array per level, reducing each R array to one point per group (k_sum chain) is independent of the later levels: stream 2,
-// (c) per group Horner over the levels, then per window R * hi + lo.
+// small weighted sums per window by bit planes and (c) per window R * hi + lo (enqueue_tail), on stream 1.
 static int stage_reduce(MsmCtx* ctx, const Launch& lp) {
   hipStream_t st = ctx->stream;
   // the row and the column tree run side by side on two streams - unless this context shares the chip with others anyway (one_stream)
@@ -1986,43 +2018,7 @@ static int stage_reduce(MsmCtx* ctx, const Launch& lp) {
   HIP_TRY(hipEventRecord(ctx->ev2, st2));
   HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
   hipLaunchKernelGGL(k_place_hilo, dim3(nblk((size_t)G * Nn * 4, 256)), dim3(256), 0, st, rows, cols, (uint32_t)W, Hh, Rr, Nn, ctx->hilo);
-  uint32_t* cur = ctx->hilo;
-  size_t n_cur = (size_t)G * Nn, r_off = 0;   // G groups of Nn items, weights index + 1; this level's R array starts at r_off inside segR (in points)
-  int level = 0;
-  LevelShifts ls = {};
-  // (fan-in 2 here was measured and lost: every level brings its own k_seg launch, R-sum tree and hand-over: MSM phase 5.7 -> 6.6 ms)
-  while (n_cur > (size_t)G) {
-    const int L = plan::tree_fan_in(ctx->L, n_cur, (uint32_t)(n_cur / G), 0);      // (less than ctx->L on the last level only)
-    int lg = 0; while ((1 << lg) < L) lg++;
-    ls.log_l[level] = (uint8_t)lg;
-    const size_t n_out = n_cur / L;
-    uint32_t* S = ctx->segS[level & 1];
-    uint32_t* Rk = ctx->segR + r_off * plan::POINT_WORDS;
-    const bool quad = n_out < ctx->quad_below;
-    hipLaunchKernelGGL(quad ? lp.red.seg_quad : lp.red.seg, dim3(nblk(quad ? n_out * 4 : n_out, 256)), dim3(256), 0, st, cur, n_cur, (uint32_t)n_cur, L, level == 0 ? 1 : 0, S, Rk);
-    HIP_TRY(hipEventRecord(ctx->ev, st));
-    HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
-    // reduce R (n_out items, G groups) to G items: Rlevels[level]
-    uint32_t* const Rl = ctx->Rlevels + (size_t)level * plan::POINT_WORDS * G;
-    uint32_t* rc = Rk;
-    int pp = 0;
-    for (size_t rn = n_out; rn > (size_t)G; pp ^= 1) {
-      const int Ls = plan::tree_fan_in(ctx->L, rn, (uint32_t)(rn / G), 0);
-      const size_t ro = rn / Ls;
-      uint32_t* dst = (ro == (size_t)G) ? Rl : ctx->sumR[pp];
-      enqueue_sum(ctx, lp, st2, rc, rn, (uint32_t)rn, Ls, (uint32_t)(rn / G / Ls), dst);      // same coalesced grouping inside each group
-      rc = dst; rn = ro;
-    }
-    if (n_out == (size_t)G)    // R already one per group
-      HIP_TRY(hipMemcpyAsync(Rl, Rk, plan::POINT_WORDS * G * 4, hipMemcpyDeviceToDevice, st2));
-    r_off += n_out;
-    cur = S; n_cur = n_out; level++;
-  }
-  HIP_TRY(hipEventRecord(ctx->ev2, st2));
-  HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
-  // the last S (one item per group) has weight 0 at its level (o = 0 for level >= 1) and is dropped.
-  hipLaunchKernelGGL(lp.red.window_combine, dim3(nblk((size_t)G * 4, 64)), dim3(64), 0, st, ctx->Rlevels, level, G, ls, ctx->sumR[0]);
-  hipLaunchKernelGGL(lp.red.hilo_combine, dim3(nblk((size_t)W * 4, 64)), dim3(64), 0, st, ctx->sumR[0], W, plan::lo_bits(c), ctx->win_abi, ctx->merged == 2 ? cur : (uint32_t*)nullptr);
+  enqueue_tail(lp.red, st, ctx->hilo, W, Nn, plan::lo_bits(c), ctx->merged == 2, ctx->planes, ctx->win_abi);
   HIP_TRY(hipGetLastError());
   return ZKHIP_OK;
 }
@@ -2150,6 +2146,43 @@ int msm_finish(MsmCtx* ctx, uint64_t out_jac[36]) {
     acc = acc.add(q);
   }
   acc.X.to_limbs(out_jac); acc.Y.to_limbs(out_jac + 12); acc.Z.to_limbs(out_jac + 24);
+  return ZKHIP_OK;
+}
+
+// Test hook: the tail of the reduction alone (enqueue_tail) on 2W groups of N points given as affine ABI points on the host, the hi
+// groups first, weights index + 1.  An Edwards run maps every item through chi and the results back through psi: psi(chi(P)) = 2P,
+// so it returns TWICE the weighted sums.  out_jac: W Jacobian points R * hi + lo, W plain totals of the lo groups behind them if total.
+int msm_tail_selftest(int edw, const uint64_t* items_aff, int W, uint32_t N, int lo_bits, int total, uint64_t* out_jac, char* errbuf, size_t errlen) {
+  using namespace host;
+  if (W < 1 || W > MSM_MAX_JOBS || N < 2 || N > 2048 || (N & (N - 1)) || lo_bits < 0 || lo_bits > 11 || !items_aff || !out_jac) return ZKHIP_ERR_ARG;
+  const size_t n = (size_t)2 * W * N, pt = plan::POINT_WORDS * 4, n_out = (size_t)W * (total ? 2 : 1);
+  uint64_t *d_aff = nullptr, *d_abi = nullptr;
+  uint32_t *d_items = nullptr, *planes[2] = {nullptr, nullptr}, *d_bad = nullptr, bad = 0;
+  std::vector<uint64_t> abi(n_out * 48);
+  hipError_t e = hipMalloc(&d_aff, n * 24 * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_items, n * pt);
+  for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipMalloc(&planes[k], plan::cap_tail(W, N, k) * pt);
+  if (e == hipSuccess) e = hipMalloc(&d_abi, n_out * 48 * 8);
+  if (e == hipSuccess) e = hipMalloc(&d_bad, 4);
+  if (e == hipSuccess) e = hipMemset(d_bad, 0, 4);
+  if (e == hipSuccess) e = hipMemcpy(d_aff, items_aff, n * 24 * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_tail_items, dim3(nblk(n, 256)), dim3(256), 0, 0, d_aff, (uint32_t)n, edw, d_items, d_bad);
+    enqueue_tail(red_kernels(edw != 0), 0, d_items, W, N, lo_bits, total != 0, planes, d_abi);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(abi.data(), d_abi, n_out * 48 * 8, hipMemcpyDeviceToHost);      // (synchronises)
+  if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
+  for (void* q : {(void*)d_aff, (void*)d_items, (void*)planes[0], (void*)planes[1], (void*)d_abi, (void*)d_bad}) if (q) (void)hipFree(q);
+  if (e != hipSuccess || bad) {
+    if (errbuf) snprintf(errbuf, errlen, e != hipSuccess ? "msm_tail_selftest: %s" : "msm_tail_selftest: items without an Edwards image%s", e != hipSuccess ? hipGetErrorString(e) : "");
+    return e != hipSuccess ? ZKHIP_ERR_HIP : ZKHIP_ERR_ARG;
+  }
+  for (size_t k = 0; k < n_out; k++) {
+    HJac q;
+    if (edw) edw_abi_to_jac(abi.data() + k * 48, q); else xyzz_abi_to_jac(abi.data() + k * 48, q);
+    q.X.to_limbs(out_jac + 36 * k); q.Y.to_limbs(out_jac + 36 * k + 12); q.Z.to_limbs(out_jac + 36 * k + 24);
+  }
   return ZKHIP_OK;
 }
 

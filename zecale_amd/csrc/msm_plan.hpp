@@ -88,12 +88,31 @@ inline int lo_bits(int c) { return (c - 1 + 1) / 2; }
 inline int hi_bits(int c) { return (c - 1) - lo_bits(c); }
 // fan-in of a row / column tree level: L while it is throughput-bound (one lane per output); 2 once it is latency-bound (a quad per
 // output, ONE addition deep: the chain of dependent additions shrinks from 3 log4 to log2 of its length); at most the `left` items of a row.
-// With left = n_in / G and quad_below = 0: of a level of the weighted-sum recursion and of its R-sum trees, G groups (never 2 by latency)
+// (Fan-in 4 for the latency-bound levels - the second level on quads, seven launches less per MSM - was measured beside this and
+// does not gain: profiles/msm_chain_ab.txt.)  quad_below = 0: never latency-bound.
 inline int tree_fan_in(int L, size_t n_in, uint32_t left, size_t quad_below) {
   for (L = n_in / (size_t)L < quad_below ? 2 : L; (uint32_t)L > left;) L >>= 1;
   return L;
 }
+// The tail of the reduction: per group g of N items (N a power of two) the weighted sum F_g = sum_i (i+1) item_i by BIT PLANES,
+//   F_g = sum_j 2^j P_{g,j},  P_{g,j} = the sum of the items whose weight i+1 has bit j set   (weights 1 .. N: log2 N + 1 planes),
+// plus, for a NAF plan, one plane that takes every item (the plain total).  The planes are plain tree sums over a (plane, group,
+// item) grid, one quad per output and one launch per level; the first level selects by weight bit.
+constexpr int TAIL_FAN_IN = 4;             // three additions deep per launch: a launch's fixed cost is worth about three quad additions
+inline int tail_weight_planes(size_t N) { int b = 0; while (((size_t)1 << b) <= N) b++; return b; }      // bits of N
+inline int tail_planes(size_t N, bool total) { return tail_weight_planes(N) + (total ? 1 : 0); }
+inline int tail_fan_in(size_t left) { return left < (size_t)TAIL_FAN_IN ? (int)left : TAIL_FAN_IN; }      // items of a group that are left
+inline int tail_levels(size_t N) { int l = 0; for (size_t left = N; left > 1; left /= (size_t)tail_fan_in(left)) l++; return l; }
+// outputs of level `level` (0: the selecting one): planes x G groups x what is left of a group
+inline size_t tail_level_outputs(int planes, int G, size_t N, int level) {
+  size_t left = N;
+  for (int l = 0; l <= level && left > 1; l++) left /= (size_t)tail_fan_in(left);
+  return (size_t)planes * (size_t)G * left;
+}
+// the two ping-pong buffers of the levels: level 0 writes [0], level 1 [1], ...; the last level's output is where the planes are combined
+inline size_t cap_tail(int W, size_t N, int which) { return tail_level_outputs(tail_planes(N, true), 2 * W, N, which) + 1; }
 // capacities of the plan's buffers, in points of POINT_WORDS words unless stated
+// (cap_segR, cap_sumR, cap_Rlevels: the buffers of the recursion the plane form replaced; the plan no longer allocates them)
 inline size_t cap_entries(int Wd, size_t total_terms) { return (size_t)Wd * total_terms + 1; }      // words; `pairs`: as many uint2
 // words: the block totals of the longest scan (slice weights, sort histogram, bucket order), with room for words [0..2] after them
 inline size_t cap_block_tot(size_t nb, size_t hist_len, size_t lock_keys) { return std::max({nb, hist_len, lock_keys * ceil_div(nb, 1024)}) / 1024 + 4; }

@@ -39,7 +39,7 @@ EXPORTS = [
     "zkhip_aggregator_app_new", "zkhip_aggregator_app_free", "zkhip_aggregator_app_num_constants", "zkhip_aggregator_app_constants", "zkhip_aggregator_app_mask",
     "zkhip_aggregator_witness_app", "zkhip_groth16_prove_app", "zkhip_prover_prove_app", "zkhip_prover_prove_app_dev", "zkhip_gpu_witness_run_batched_app",
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
-    "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path",
+    "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path", "zkhip_internal_msm_tail",
     "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
     "zkhip_nested_verifier_new", "zkhip_nested_verifier_num_inputs", "zkhip_nested_verifier_verify_batch", "zkhip_nested_verifier_last_fallbacks",
     "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
@@ -1676,6 +1676,18 @@ def last_acc_path():
     out = ctypes.c_int(-1)
     _check(load().zkhip_internal_last_acc_path(ctypes.byref(out)))
     return int(out.value)
+
+
+def msm_tail(items_affine, W, lo_bits, edw=False, total=False):
+    """Test hook: the tail of the bucket reduction alone (zkhip_internal_msm_tail).  items_affine: uint64 [2W][N][24], the W hi groups
+    first (all-zero = infinity); returns uint64 [W or 2W][36] Jacobian points: 2^lo_bits sum (i+1) hi[i] + sum (i+1) lo[i] per window,
+    then, with total, the plain sums of the lo groups.  edw: the Edwards kernels - every output is TWICE that sum."""
+    x = np.ascontiguousarray(items_affine, dtype=np.uint64).reshape(2 * W, -1, 24)
+    out = np.zeros((W * (2 if total else 1), 36), dtype=np.uint64)
+    lib = load()
+    lib.zkhip_internal_msm_tail.argtypes = [ctypes.c_int, c_u64p_t, ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.c_int, c_u64p_t]
+    _check(lib.zkhip_internal_msm_tail(int(edw), _p(x), int(W), x.shape[1], int(lo_bits), int(total), _p(out)))
+    return out
 
 
 def field_selftest(field, limbs_in):
