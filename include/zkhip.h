@@ -720,6 +720,11 @@ int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n,
  * otherwise: 1 lockstep, 0 sliced, -1 not an Edwards launch. */
 int zkhip_internal_set_lockstep(int mode, int min_buckets);
 int zkhip_internal_last_acc_path(int* out);
+/* Test / A-B hook (no counterpart; results never depend on it).
+ * set_msm_stream_layout: how the zkhip_msm_streams made from now on place their contexts' HIP streams:
+ * 0 = every context creates its pair at its first submit, 1 = all primaries, then all secondaries, when the stream is made,
+ * 2 = primaries only, a context's whole launch sequence on it; -1 = the environment (ZKHIP_MSM_STREAM_LAYOUT) / default. */
+int zkhip_internal_set_msm_stream_layout(int layout);
 /* Test hook of the bucket reduction's tail (no counterpart): the two small weighted sums per bucket window by bit planes and
  * R * hi + lo, alone.  items_affine: 2W groups of N affine points (24 limbs each, all-zero = infinity), the W hi
  * groups first; item i of a group has weight i + 1.  out_jac[w] = 2^lo_bits sum_i (i+1) hi_w[i] + sum_i (i+1) lo_w[i], and, if total,

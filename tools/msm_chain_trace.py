@@ -15,6 +15,31 @@ import sys
 from collections import defaultdict
 
 
+def is_acc(name):
+    """the Edwards accumulation launch that does the work on the lockstep route"""
+    return "k_accumulate_edw_lock" in name
+
+
+def queue_table(rows, t0, t1):
+    """per hardware queue: the timed accumulations (primary streams) and the k_sum_edw launches of the region (both streams of a
+    context launch them: the column tree's are the secondary stream's only kernels) with the distinct streams they came from"""
+    if "Queue_Id" not in rows[0]:
+        print("the trace has no Queue_Id column: no per-queue table")
+        return
+    has_stream = "Stream_Id" in rows[0]
+    for title, pick in (("accumulations", is_acc), ("k_sum_edw launches", lambda nm: "k_sum_edw" in nm)):
+        per = defaultdict(lambda: [0, set()])
+        for r in rows:
+            if pick(r["Kernel_Name"]) and t0 <= int(r["Start_Timestamp"]) <= t1:
+                per[r["Queue_Id"]][0] += 1
+                per[r["Queue_Id"]][1].add(r["Stream_Id"] if has_stream else "?")
+        print("%s of the region per Queue_Id: launches, distinct Stream_Ids" % title)
+        for q in sorted(per, key=lambda x: (len(x), x)):
+            print("  queue %-6s %5d  %3d  streams %s" % (q, per[q][0], len(per[q][1]), " ".join(sorted(per[q][1], key=lambda x: (len(x), x)))))
+    allq = sorted({r["Queue_Id"] for r in rows}, key=lambda x: (len(x), x))
+    print("queues in the whole trace: %s" % " ".join(allq))
+
+
 def main():
     d = sys.argv[1]
     timed = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -25,7 +50,7 @@ def main():
     key = "Stream_Id" if "Stream_Id" in rows[0] and len({r["Stream_Id"] for r in rows}) > 2 else "Queue_Id"
     ev = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r[key]) for r in rows]
     ev.sort()
-    acc = [e for e in ev if "k_accumulate_edw_lock" in e[2]]
+    acc = [e for e in ev if is_acc(e[2])]
     if len(acc) < timed:
         sys.exit("only %d accumulations in the trace" % len(acc))
     acc = acc[-timed:]
@@ -53,12 +78,12 @@ def main():
             if "k_digit_pass<0" in x[2]:
                 first = x
                 break
-            if "k_accumulate_edw_lock" in x[2]:
+            if is_acc(x[2]):
                 break
         after = []
         for x in seq:
             if x[0] >= e:
-                if "k_digit_pass<0" in x[2] or "k_accumulate_edw_lock" in x[2]:
+                if "k_digit_pass<0" in x[2] or is_acc(x[2]):
                     break
                 after.append(x)
         if first:
@@ -70,6 +95,7 @@ def main():
     mean = lambda v: sum(v) / len(v) if v else float("nan")
     print("front chain (first digit pass -> accumulation starts): mean %.3f ms, min %.3f, max %.3f  (%d sequences)" % (mean(front), min(front, default=0), max(front, default=0), len(front)))
     print("back chain (accumulation ends -> last kernel of the sequence on that %s ends): mean %.3f ms, min %.3f, max %.3f; %.1f launches, %.3f ms of kernel durations" % (key, mean(back), min(back, default=0), max(back, default=0), mean(nback), mean(busy_back)))
+    queue_table(rows, t0, t1)
     names = defaultdict(lambda: [0, 0])
     for s, e, nm, _ in ev:
         if s >= t0 and e <= t1:

@@ -142,7 +142,7 @@ struct Scratch {
 // api_msm.hip
 int auto_table_window(size_t n);
 bool ctx_reusable(const MsmCtx* cx, size_t n, int table_c, int K, int naf, size_t total, int plain_c = 0);
-int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K = 1, int naf = 0, size_t total = 0, int plain_c = 0, hipStream_t* adopt = nullptr);
+int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K = 1, int naf = 0, size_t total = 0, int plain_c = 0, hipStream_t* adopt = nullptr, int one_stream = -1);
 void note_last_acc(ProveState& ps, MsmCtx* cx);
 int last_entries_of(ProveState& ps, uint64_t* out);
 bool naf_tables_fit(size_t total_points);

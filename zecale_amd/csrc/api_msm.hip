@@ -46,11 +46,11 @@ bool ctx_reusable(const MsmCtx* cx, size_t n, int table_c, int K, int naf, size_
   return cx->planned && !cx->pending && cx->max_n >= n && cx->total_terms >= total && cx->c == plan_window(n, table_c, plain_c) &&
          cx->merged == plan_merged(table_c, naf) && cx->K == K && cx->aff_forced == msm_forced_aff_levels();
 }
-int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K, int naf, size_t total, int plain_c, hipStream_t* adopt) {
+int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K, int naf, size_t total, int plain_c, hipStream_t* adopt, int one_stream) {
   if (cx->pending) return fail(ZKHIP_ERR_STATE, "an MSM submitted on this context has not been collected (zkhip_msm_collect)");
   if (ctx_reusable(cx, n, table_c, K, naf, total, plain_c)) return ZKHIP_OK;
   if (cx->planned) msm_plan_free(cx);
-  const int rc = msm_plan_init(cx, n, plan_window(n, table_c, plain_c), plan_merged(table_c, naf), K, total, adopt);
+  const int rc = msm_plan_init(cx, n, plan_window(n, table_c, plain_c), plan_merged(table_c, naf), K, total, adopt, one_stream);
   if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "msm_plan_init: %s", cx->errbuf); msm_plan_free(cx); }   // (frees what the failed plan had allocated: "no plan" again)
   return rc;
 }
@@ -172,8 +172,27 @@ struct zkhip_msm_stream {
   std::vector<size_t> stage_cap;
   uint64_t next_ticket = 1;
   float last_accumulate_ms = 0.f, last_interval[2] = {0.f, 0.f};
+  int layout = 0;                        // msm_stream_layout() when the stream was made
+  std::vector<hipStream_t> pool;         // layouts 1, 2: slot k's primary HIP stream at [k], its secondary at [depth + k] - null while the slot's plan owns it
   std::mutex mu;
 };
+
+// How a zkhip_msm_stream places the HIP streams of its contexts on the runtime's hardware queues.  The runtime deals streams to its
+// queues round robin in the order they are CREATED, and kernels of streams that share a queue do not overlap (the provers' finding:
+// zkhip_prover_create_streams).  That is OBSERVED behaviour of the runtime (kernel traces, 4 queues), not a contract of HIP: the
+// layouts differ in speed only, and if a runtime binds streams otherwise the gain goes and nothing else changes.  A context's primary stream carries its whole launch sequence, its secondary only the column tree.
+//   0  every context creates its pair at its first submit: p0 s0 p1 s1 .. - with an even number of queues every primary lands on
+//      every second queue (profiles/msm_queues_before.txt: 16 of 20 accumulations on two of the four queues)
+//   1  zkhip_msm_stream_new creates all primaries, consecutively, then all secondaries
+//   2  primaries only: the contexts of a stream deeper than 1 run their whole sequence on the primary (MsmCtx::one_stream)
+// ZKHIP_MSM_STREAM_LAYOUT, read once; zkhip_internal_set_msm_stream_layout overrides it for the streams made afterwards.
+#define ZK_MSM_STREAM_LAYOUT_DEFAULT 1
+static std::atomic<int> g_stream_layout{-1};
+static int msm_stream_layout() {
+  static const int env_layout = [] { const char* e = getenv("ZKHIP_MSM_STREAM_LAYOUT"); const int v = e ? atoi(e) : ZK_MSM_STREAM_LAYOUT_DEFAULT; return (v < 0 || v > 2) ? ZK_MSM_STREAM_LAYOUT_DEFAULT : v; }();
+  const int cur = g_stream_layout.load();
+  return cur >= 0 ? cur : env_layout;
+}
 
 static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const void* d_scalars, const uint64_t* h_scalars, size_t len,
                                   int scalars_montgomery, uint64_t* ticket) {
@@ -186,7 +205,20 @@ static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const voi
   for (int k = 0; k < st->depth; k++) if (!st->ticket_of[k]) { slot = k; break; }
   if (slot < 0) return fail(ZKHIP_ERR_STATE, "every slot of this stream is in flight: collect a result first");
   MsmCtx* cx = &st->ctx[slot];
-  int rc = ensure_ctx(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c);
+  int rc = ZKHIP_OK;
+  if (st->layout == 0) rc = ensure_ctx(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c);
+  else if (!ctx_reusable(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c)) {
+    // the slot's plan adopts the streams made for it by zkhip_msm_stream_new; a plan that has to be made again (a longer MSM) hands
+    // them back first, so that the slot keeps its place on the hardware queues (msm_plan_free skips the null streams)
+    const int d = st->depth;
+    if (cx->planned && !cx->pending) {
+      st->pool[slot] = cx->stream; st->pool[d + slot] = cx->stream2;
+      cx->stream = cx->stream2 = nullptr;
+    }
+    hipStream_t adopt[2] = {st->pool[slot], st->pool[d + slot]};
+    rc = ensure_ctx(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c, adopt, (st->layout == 2 && d > 1) ? 1 : -1);
+    st->pool[slot] = adopt[0]; st->pool[d + slot] = adopt[1];      // (null once the plan owns them)
+  }
   if (rc != ZKHIP_OK) return rc;
   if (h_scalars && len) {
     // host scalars: one asynchronous copy in front of the MSM's kernels, on the context's own stream (truly asynchronous from pinned
@@ -421,6 +453,21 @@ int zkhip_msm_stream_new(const zkhip_bases* bases, int depth, zkhip_msm_stream**
   st->device = bases->device; st->bases = bases; st->depth = depth;
   st->ctx.resize(depth); st->ticket_of.assign(depth, 0);
   st->d_stage.assign(depth, nullptr); st->stage_cap.assign(depth, 0);
+  st->layout = msm_stream_layout();
+  if (st->layout) {
+    // two passes, as zkhip_prover_create_streams: every primary stream first - consecutive creations go to different hardware
+    // queues -, then the secondaries (none when the contexts keep to their primary)
+    st->pool.assign(2 * (size_t)depth, nullptr);
+    const int n_streams = (st->layout == 2 && depth > 1) ? depth : 2 * depth;
+    for (int k = 0; k < n_streams; k++) {
+      const hipError_t e = hipStreamCreateWithFlags(&st->pool[k], hipStreamNonBlocking);
+      if (e != hipSuccess) {
+        snprintf(t_err, sizeof t_err, "zkhip_msm_stream_new: %s", hipGetErrorString(e));
+        zkhip_msm_stream_free(st);
+        return ZKHIP_ERR_HIP;
+      }
+    }
+  }
   *out = st;
   return ZKHIP_OK;
 }
@@ -435,6 +482,7 @@ void zkhip_msm_stream_free(zkhip_msm_stream* st) {
     }
     if (st->d_stage[k]) (void)hipFree(st->d_stage[k]);
   }
+  for (hipStream_t s : st->pool) if (s) (void)hipStreamDestroy(s);      // the streams of slots that never made a plan (a plan destroys its own)
   delete st;
 }
 
@@ -484,6 +532,12 @@ int zkhip_measure_fq_mul_rate(double* fq_mul_per_s) {
 // Test hooks of the lockstep route of the Edwards accumulation (msm.hip k_accumulate_edw_lock)
 int zkhip_internal_set_lockstep(int mode, int min_buckets) {
   msm_force_lockstep(mode, min_buckets);
+  return ZKHIP_OK;
+}
+// Test / A-B hook of the stream layout of a zkhip_msm_stream (above)
+int zkhip_internal_set_msm_stream_layout(int layout) {
+  if (layout < -1 || layout > 2) return fail(ZKHIP_ERR_ARG, "layout must be -1 (the environment), 0, 1 or 2");
+  g_stream_layout.store(layout);
   return ZKHIP_OK;
 }
 int zkhip_internal_last_acc_path(int* out) {

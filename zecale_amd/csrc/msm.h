@@ -44,7 +44,7 @@ struct MsmCtx {      // all zeros: no plan
   int one_stream;       // 1: the whole launch sequence on `stream` (a prover that shares the chip); 0: row / column trees side by side
   uint32_t quad_below;  // reduction launches with fewer outputs than this spread an addition over four lanes (latency) instead of one (total work)
   uint32_t S, T, slot_stride;   // slice length, slice count, words per row of the slot array
-  hipStream_t stream, stream2;
+  hipStream_t stream, stream2;   // (stream2 is null in a plan made with one_stream set: stage_reduce then keeps to `stream` whatever one_stream says later)
   hipEvent_t ev, ev2, ev_acc0, ev_acc1, ev_done;
   hipEvent_t acc_gate;  // optional (not owned): the accumulation of this launch sequence starts after this event - the end of the
                         // accumulation of the MSM submitted before it on another context (zkhip_msm_submit): the sort of MSM i+1 and
@@ -100,7 +100,9 @@ void msm_force_lockstep(int mode, int min_buckets);
 int msm_last_acc_path(MsmCtx* ctx, int* out);
 // total_terms: upper bound on the terms (finite bases) of all K jobs of one launch together; 0 = K * max_n
 // adopt: two streams created by the caller beforehand (or null): the plan's main and side stream - the plan owns them from here on
-int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms = 0, hipStream_t* adopt = nullptr);
+// (the entries it took are set to null; a one_stream plan takes adopt[0] alone and has no side stream at all)
+// one_stream: 1 / 0 the plan's one_stream from the start, -1 the environment (ZKHIP_MSM_ONE_STREAM, default 0)
+int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms = 0, hipStream_t* adopt = nullptr, int one_stream = -1);
 // a per-device event recorded once: the origin of last_acc_begin_ms / last_acc_end_ms
 hipEvent_t msm_time_base();
 // record the origin again (now): intervals read afterwards are relative to this moment

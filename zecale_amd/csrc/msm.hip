@@ -1679,14 +1679,14 @@ static void read_accumulate_times(MsmCtx* ctx) {
   }
 }
 
-int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms, hipStream_t* adopt) {
+int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms, hipStream_t* adopt, int one_stream) {
   memset(ctx, 0, sizeof *ctx);
   ctx->total_terms = total_terms = plan::total_terms(K, max_n, total_terms);
   (void)msm_time_base();
   if (K < 1 || K > MSM_MAX_JOBS || (!merged && K != 1)) return ZKHIP_ERR_ARG;
   ctx->K = K;
   ctx->quad_below = (uint32_t)env_int("ZKHIP_QUAD_BELOW", 65536, 1, 1 << 30);
-  ctx->one_stream = env_int("ZKHIP_MSM_ONE_STREAM", 0, 0, 1);
+  ctx->one_stream = one_stream >= 0 ? (one_stream ? 1 : 0) : env_int("ZKHIP_MSM_ONE_STREAM", 0, 0, 1);
   // 108 * (W * 2^(c-1) + 2T) * 4 bytes must stay below 4 GiB (buffer descriptor); checked below
   if (c < 4 || c > (merged ? 22 : 18)) return ZKHIP_ERR_ARG;
   ctx->c = c;
@@ -1700,10 +1700,11 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   ctx->max_n = max_n;
   ctx->logL = env_int("ZKHIP_SUM_LOGL", 2, 2, 5); ctx->L = 1 << ctx->logL;      // fan-in of the reduction trees (tuning knob; the R arrays are sized for L >= 4)
   size_t nb = ctx->B * ctx->W;
-  if (adopt && adopt[0] && adopt[1]) { ctx->stream = adopt[0]; ctx->stream2 = adopt[1]; adopt[0] = adopt[1] = nullptr; }
+  // (a plan that starts as one_stream never creates a side stream: an idle stream still takes a place in the runtime's round over its hardware queues)
+  if (adopt && adopt[0] && (adopt[1] || ctx->one_stream)) { ctx->stream = adopt[0]; ctx->stream2 = adopt[1]; adopt[0] = adopt[1] = nullptr; }
   else {
     HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));   // no implicit ordering against the null stream (the host application's, e.g. torch's)
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    if (!ctx->one_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
   }
   HIP_TRY(hipEventCreateWithFlags(&ctx->ev, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&ctx->ev2, hipEventDisableTiming));
@@ -2008,7 +2009,7 @@ static void enqueue_tail(const RedKernels& red, hipStream_t st, uint32_t* items,
 static int stage_reduce(MsmCtx* ctx, const Launch& lp) {
   hipStream_t st = ctx->stream;
   // the row and the column tree run side by side on two streams - unless this context shares the chip with others anyway (one_stream)
-  hipStream_t st2 = ctx->one_stream ? ctx->stream : ctx->stream2;
+  hipStream_t st2 = (ctx->one_stream || !ctx->stream2) ? ctx->stream : ctx->stream2;
   const int c = ctx->c, W = ctx->W, G = 2 * W;
   const uint32_t Rr = 1u << plan::lo_bits(c), Hh = 1u << plan::hi_bits(c), Nn = Rr > Hh ? Rr : Hh;
   HIP_TRY(hipEventRecord(ctx->ev, st));

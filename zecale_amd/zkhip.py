@@ -40,6 +40,7 @@ EXPORTS = [
     "zkhip_aggregator_witness_app", "zkhip_groth16_prove_app", "zkhip_prover_prove_app", "zkhip_prover_prove_app_dev", "zkhip_gpu_witness_run_batched_app",
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
     "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path", "zkhip_internal_msm_tail",
+    "zkhip_internal_set_msm_stream_layout",
     "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
     "zkhip_nested_verifier_new", "zkhip_nested_verifier_num_inputs", "zkhip_nested_verifier_verify_batch", "zkhip_nested_verifier_last_fallbacks",
     "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
@@ -1669,6 +1670,12 @@ def set_lockstep(mode, min_buckets=-1):
     """Test / A-B knob of the Edwards accumulation's lockstep route (zkhip_internal_set_lockstep): mode 0 sliced, 1 the device decides,
     -1 the environment (ZKHIP_LOCKSTEP); min_buckets: non-empty buckets a launch needs for it (-1: the chip's own figure)."""
     _check(load().zkhip_internal_set_lockstep(int(mode), int(min_buckets)))
+
+
+def set_msm_stream_layout(layout):
+    """Test / A-B knob (zkhip_internal_set_msm_stream_layout): how the MsmStreams made from now on place their HIP streams: 0 a pair
+    per context at its first submit, 1 all primaries then all secondaries up front, 2 primaries only; -1 the environment / default."""
+    _check(load().zkhip_internal_set_msm_stream_layout(int(layout)))
 
 
 def last_acc_path():
