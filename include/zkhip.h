@@ -285,7 +285,8 @@ int zkhip_prover_set_streaming(zkhip_prover* p, int on);
  * The runtime spreads streams over its hardware queues in creation order and kernels of streams that share a queue do not overlap; an
  * instance in streaming mode keeps one of its three streams busy.  Call with which = 0 for every instance (the busy streams: spread
  * evenly), then with which = 1 for every instance (the idle ones), before the first proof; without it the streams are created by the
- * first proofs, in whatever order the provers' threads arrive. */
+ * first proofs, in whatever order the provers' threads arrive.  Either call creates only what the instance does not have yet, and
+ * the instance keeps its streams until it is freed. */
 int zkhip_prover_create_streams(zkhip_prover* p, int which);
 int zkhip_prover_prove(zkhip_prover* p, const uint64_t* z, const uint64_t r[6], const uint64_t s[6], uint64_t proof_affine[72]);
 /* the same with the assignment already in device memory (n_vars x 6 limbs, e.g. from zkhip_gpu_witness_run; must be complete) */

@@ -296,6 +296,34 @@ def test_submit_collect_slots_in_flight(zk, oracle_lib, table_kind):
     b.free()
 
 
+def test_submit_collect_a_slot_planned_again_with_its_neighbour_pending(zk, table_kind):
+    """The process-wide slots keep their streams and events when their plan is made again: slot 0 - left with a plan for eight plain
+    bases, so that what follows does not depend on the tests before - is planned for a prefix of the table-backed set and collected,
+    then, with slot 1 in flight, given the whole set, which that plan is too short for.  Every result is the blocking call's."""
+    n, short = 6000, 2500
+    bases = zk.fixed_base_mul(aff_limbs(R.G1_GEN), random_fr_canonical(701, n), montgomery=False)
+    b = zk.Bases.upload(bases).precompute(table_naf=table_kind)
+    plain = zk.Bases.upload(bases[:8])
+    scal = [random_fr_canonical(710 + i, n) for i in range(2)]
+    dev = [zk.DeviceBuffer(s) for s in scal]
+    aff = zk.jac_to_affine
+    plain.msm_submit(dev[0].ptr, 8, slot=0)
+    got_plain = aff(zk.msm_collect(0))
+    b.msm_submit(dev[0].ptr, short, slot=0)
+    got_short = aff(zk.msm_collect(0))
+    b.msm_submit(dev[1].ptr, n, slot=1)
+    b.msm_submit(dev[0].ptr, n, slot=0)
+    got_all, got_1 = aff(zk.msm_collect(0)), aff(zk.msm_collect(1))
+    assert (got_plain == aff(plain.msm(scal[0][:8]))).all()
+    assert (got_short == aff(b.msm(scal[0][:short]))).all()
+    assert (got_all == aff(b.msm(scal[0]))).all()
+    assert (got_1 == aff(b.msm(scal[1]))).all()
+    for d in dev:
+        d.free()
+    plain.free()
+    b.free()
+
+
 def test_table_2_22_closed_form(zk, oracle_lib):
     """BASELINE config 4 size on one GPU (2^22 terms, window table with c = 21): sum s_i (k_i G) = (sum s_i k_i mod r) G
     against ONE oracle scalar multiplication - the size-independent check at the largest configured size."""

@@ -117,9 +117,10 @@ def test_a_stream_freed_with_launches_pending_and_slots_unused(zk, vectors, knob
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_a_slot_planned_again_for_a_longer_msm_keeps_its_streams(zk, vectors, knobs, layout):
-    """A slot's plan is sized by its first launch; a longer one makes it again.  Under layouts 1 and 2 the old plan hands its HIP
-    streams back to the stream's pool and the new plan adopts them - here for slot 0 with nothing in flight, for slot 1 while slot
-    0's long MSM is pending -, and free() afterwards destroys every stream once: a stream made after it works."""
+    """A slot's plan is sized by its first launch; a longer one makes it again.  The plan owns memory only: the slot's HIP streams and
+    events are its lane's, which the stream holds from zkhip_msm_stream_new (layouts 1 and 2) or the slot's first submit (layout 0)
+    until free(), so the new plan runs where the old one did - here for slot 0 with nothing in flight, for slot 1 while slot 0's
+    long MSM is pending -, and free() afterwards destroys every lane once: a stream made after it works."""
     b, n, dev, exp, short = vectors
     assert short < n
     first = SEQ[0]                                               # its range is the prefix [0, short) of the base set
@@ -141,3 +142,28 @@ def test_a_slot_planned_again_for_a_longer_msm_keeps_its_streams(zk, vectors, kn
         assert (zk.jac_to_affine(again.collect(t)) == exp["mixed_cap"]).all()
     finally:
         again.free()
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_a_slot_planned_again_while_its_neighbour_is_in_flight(zk, vectors, knobs, layout):
+    """Slot 0 is planned for a prefix longer than `short`, serves the short prefix with that plan, and - with slot 1's launch (a plan
+    of the same length, made while slot 0's was pending) still in flight - is given the whole set: its plan is made again on its own
+    lane while the neighbour's lane is busy.  Collected newest first."""
+    b, n, dev, exp, short = vectors
+    first = SEQ[0]                                               # zero outside [0, short): every prefix from `short` on has its sum
+    mid = (short + n) // 2
+    assert short < mid < n
+    stream = _stream(zk, b, 2, layout)
+    try:
+        t = stream.submit(dev[first].ptr, mid, montgomery=False)                 # slot 0: planned for mid
+        assert (zk.jac_to_affine(stream.collect(t)) == exp[first]).all(), "long"
+        t_short = stream.submit(dev[first].ptr, short, montgomery=False)         # slot 0: the long plan serves it
+        t_mid = stream.submit(dev[first].ptr, mid, montgomery=False)             # slot 1: planned for mid, slot 0 pending
+        assert (zk.jac_to_affine(stream.collect(t_short)) == exp[first]).all(), "short"
+        t_all = stream.submit(dev["uniform"].ptr, n, montgomery=False)           # slot 0: planned again, slot 1 pending
+        with pytest.raises(zk.ZkhipError):
+            stream.submit(dev[first].ptr, short, montgomery=False)               # (both slots in flight)
+        assert (zk.jac_to_affine(stream.collect(t_all)) == exp["uniform"]).all(), "whole set"
+        assert (zk.jac_to_affine(stream.collect(t_mid)) == exp[first]).all(), "neighbour"
+    finally:
+        stream.free()

@@ -54,6 +54,53 @@ def test_golden_small_circuit(zk, key_mode):
     crs.free(); r1.free()
 
 
+def test_prover_lanes_made_ahead_after_or_never(zk, key_mode):
+    """A prover instance holds the streams and events of its MSM contexts in lanes of its own, whatever becomes of the plans
+    (zkhip_prover_create_streams makes the launch sequence's pair ahead of the first proof and only what is missing after it; a
+    streaming prover chains its proofs on that lane's main stream from the second one on).  Every proof is the golden one."""
+    g, pk = _golden_case()
+    A, B, C = (csr_from_rows(g[k]) for k in "ABC")
+    z, r, s = fr_array([h2i(x) for x in g["z"]]), fr_limbs(h2i(g["r"])), fr_limbs(h2i(g["s"]))
+    crs = zk.Crs(pk, len(g["z"]), g["n_primary"], 1 << g["log_d"], opts=_opts(zk, key_mode))
+    desc, keep = zk.make_r1cs_desc(A, B, C, len(g["z"]), g["n_primary"])      # (keep: the arrays the descriptor points into)
+    want = tuple(pt_from_json(g["proof"][k]) for k in "abc")
+
+    def proves(p, times):
+        for k in range(times):
+            proof = p.prove(z, r, s)
+            assert (aff_point(proof[:24]), aff_point(proof[24:48]), aff_point(proof[48:])) == want, k
+
+    def streams(p):
+        p.create_streams(0)
+        p.create_streams(1)
+
+    p = zk.Prover(crs, desc)                   # streams first, then two proofs
+    streams(p)
+    with pytest.raises(zk.ZkhipError):
+        p.create_streams(2)
+    proves(p, 2)
+    p.free()
+    p = zk.Prover(crs, desc)                   # a proof, then the calls that find everything made, then a proof
+    proves(p, 1)
+    streams(p)
+    proves(p, 1)
+    p.free()
+    p = zk.Prover(crs, desc)                   # streams and no proof
+    streams(p)
+    p.free()
+    p = zk.Prover(crs, desc)                   # streaming: from the second proof on the chained path where the key batches its MSMs
+    p.set_streaming(True)
+    proves(p, 1)
+    assert not p.timings()["chained"]          # (its plan is made under it: never a prover's first proof)
+    proves(p, 2)
+    assert p.timings()["chained"] == (key_mode == "tables+batched")
+    p.set_streaming(False)
+    proves(p, 1)
+    assert not p.timings()["chained"]
+    p.free()
+    crs.free()
+
+
 @pytest.mark.parametrize("n,bool_frac,domain", [(3000, 0.0, None), (3000, 0.0, "step"), (4000, 0.6, None)])
 def test_synthetic_circuit_vs_oracle_and_trapdoor(zk, oracle_lib, key_mode, n, bool_frac, domain):
     """domain None: the reference's forced power of two (libzeth passes force_pow_2_domain) - the default of every

@@ -60,6 +60,7 @@ struct ProveState {
   // separate launch sequences), [ZK_MSM_SLOTS] the context of a proof's five MSMs in ONE launch sequence, [ZK_CTX_Z] / [ZK_CTX_H] the
   // two sequences of a proof ALONE (round 6): the four MSMs over the assignment, and the H MSM behind the QAP map
   MsmCtx ctx[ZK_CTX_TOTAL] = {};   // (all zeros: no plan yet - msm.h)
+  MsmLane lane[ZK_CTX_TOTAL] = {}; // ctx[k]'s streams and events, from its first plan (or zkhip_prover_create_streams) to release(), whatever becomes of the plans
   hipStream_t st = nullptr;
   hipEvent_t ev_st = nullptr;      // blocking-sync event for waits on st (the waiting host thread sleeps)
   hipEvent_t ev_up = nullptr, ev_qap = nullptr;   // split proofs: the assignment is on the device / the QAP map has finished (stream-to-stream)
@@ -74,10 +75,10 @@ struct ProveState {
   float last_acc_interval[2] = {0.f, 0.f};   // begin / end of that launch on the device's time base
   int last_submit_slot = -1;       // zkhip_msm_submit: the slot of the previous submission (its accumulation gates the next one's)
   uint32_t quad_below = 0;         // 0: the engine's default; else the MSM contexts' quad_below (zkhip_prover_set_streaming)
-  hipStream_t pre[2] = {nullptr, nullptr};   // streams made ahead of the first proof (zkhip_prover_create_streams): the launch sequence's plan adopts them
   void release() {
-    for (int k = 0; k < 2; k++) if (pre[k]) { (void)hipStreamDestroy(pre[k]); pre[k] = nullptr; }
-    for (int k = 0; k < ZK_CTX_TOTAL; k++) if (ctx[k].planned) msm_plan_free(&ctx[k]);
+    for (MsmCtx& c : ctx) if (c.pending) { uint64_t drop[36]; (void)msm_finish(&c, drop); }      // never free work space or a lane under a running launch
+    for (MsmCtx& c : ctx) if (c.planned) msm_plan_free(&c);
+    for (MsmLane& l : lane) msm_lane_free(&l);
     if (st) { (void)hipStreamDestroy(st); st = nullptr; }
     if (ev_st) { (void)hipEventDestroy(ev_st); ev_st = nullptr; }
     if (ev_up) { (void)hipEventDestroy(ev_up); ev_up = nullptr; }
@@ -142,7 +143,7 @@ struct Scratch {
 // api_msm.hip
 int auto_table_window(size_t n);
 bool ctx_reusable(const MsmCtx* cx, size_t n, int table_c, int K, int naf, size_t total, int plain_c = 0);
-int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K = 1, int naf = 0, size_t total = 0, int plain_c = 0, hipStream_t* adopt = nullptr, int one_stream = -1);
+int ensure_ctx(MsmCtx* cx, MsmLane& lane, size_t n, int table_c, int K = 1, int naf = 0, size_t total = 0, int plain_c = 0, int one_stream = -1);
 void note_last_acc(ProveState& ps, MsmCtx* cx);
 int last_entries_of(ProveState& ps, uint64_t* out);
 bool naf_tables_fit(size_t total_points);

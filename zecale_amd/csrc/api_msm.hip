@@ -46,11 +46,17 @@ bool ctx_reusable(const MsmCtx* cx, size_t n, int table_c, int K, int naf, size_
   return cx->planned && !cx->pending && cx->max_n >= n && cx->total_terms >= total && cx->c == plan_window(n, table_c, plain_c) &&
          cx->merged == plan_merged(table_c, naf) && cx->K == K && cx->aff_forced == msm_forced_aff_levels();
 }
-int ensure_ctx(MsmCtx* cx, size_t n, int table_c, int K, int naf, size_t total, int plain_c, hipStream_t* adopt, int one_stream) {
+// lane: cx's, held by the owner of cx.  What it lacks is made here - main, then side (not for a plan that starts as one_stream: an idle stream still takes
+// a place in the runtime's round over its hardware queues), then the events -; a plan made again (a longer MSM) finds everything there and stays where it ran.
+int ensure_ctx(MsmCtx* cx, MsmLane& lane, size_t n, int table_c, int K, int naf, size_t total, int plain_c, int one_stream) {
   if (cx->pending) return fail(ZKHIP_ERR_STATE, "an MSM submitted on this context has not been collected (zkhip_msm_collect)");
   if (ctx_reusable(cx, n, table_c, K, naf, total, plain_c)) return ZKHIP_OK;
   if (cx->planned) msm_plan_free(cx);
-  const int rc = msm_plan_init(cx, n, plan_window(n, table_c, plain_c), plan_merged(table_c, naf), K, total, adopt, one_stream);
+  (void)msm_time_base();      // (recorded on the null stream the first time: before the lane's streams, as ever)
+  API_HIP(msm_lane_create_main(&lane));
+  if (!msm_one_stream(one_stream)) API_HIP(msm_lane_create_side(&lane));
+  API_HIP(msm_lane_create_events(&lane));
+  const int rc = msm_plan_init(cx, &lane, n, plan_window(n, table_c, plain_c), plan_merged(table_c, naf), K, total, one_stream);
   if (rc != ZKHIP_OK) { snprintf(t_err, sizeof t_err, "msm_plan_init: %s", cx->errbuf); msm_plan_free(cx); }   // (frees what the failed plan had allocated: "no plan" again)
   return rc;
 }
@@ -161,26 +167,27 @@ static bool edw_tables_wanted() {
 
 // ---- handle-owned MSM streams ---------------------------------------------------------------------------------------------
 // zkhip_msm_submit / collect above address eight PROCESS-WIDE slot numbers: two threads streaming MSMs on one device collide.  A
-// zkhip_msm_stream owns its contexts (streams, work space), like a zkhip_prover: any number of them run side by side.
+// zkhip_msm_stream owns its contexts (work space) and their lanes (streams, events), like a zkhip_prover: any number of them run side by side.
 struct zkhip_msm_stream {
   int device = 0;
   const zkhip_bases* bases = nullptr;
   int depth = 0;
   std::vector<MsmCtx> ctx;               // (value-initialised: all zeros, no plan - msm.h)
+  std::vector<MsmLane> lane;             // slot k's streams and events, from zkhip_msm_stream_new (layouts 1, 2) or its first submit to zkhip_msm_stream_free
   std::vector<uint64_t> ticket_of;       // per slot: the ticket in flight there, 0 = free
   std::vector<void*> d_stage;            // per slot: device copy of host scalars (zkhip_msm_stream_submit_host)
   std::vector<size_t> stage_cap;
   uint64_t next_ticket = 1;
   float last_accumulate_ms = 0.f, last_interval[2] = {0.f, 0.f};
   int layout = 0;                        // msm_stream_layout() when the stream was made
-  std::vector<hipStream_t> pool;         // layouts 1, 2: slot k's primary HIP stream at [k], its secondary at [depth + k] - null while the slot's plan owns it
   std::mutex mu;
 };
 
 // How a zkhip_msm_stream places the HIP streams of its contexts on the runtime's hardware queues.  The runtime deals streams to its
 // queues round robin in the order they are CREATED, and kernels of streams that share a queue do not overlap (the provers' finding:
 // zkhip_prover_create_streams).  That is OBSERVED behaviour of the runtime (kernel traces, 4 queues), not a contract of HIP: the
-// layouts differ in speed only, and if a runtime binds streams otherwise the gain goes and nothing else changes.  A context's primary stream carries its whole launch sequence, its secondary only the column tree.
+// layouts differ in speed only, and if a runtime binds streams otherwise the gain goes and nothing else changes.
+// A context's primary stream (its lane's main) carries its whole launch sequence, its secondary (side) only the column tree; the lanes are the stream's until zkhip_msm_stream_free: a slot planned again for a longer MSM stays where it is.
 //   0  every context creates its pair at its first submit: p0 s0 p1 s1 .. - with an even number of queues every primary lands on
 //      every second queue (profiles/msm_queues_before.txt: 16 of 20 accumulations on two of the four queues)
 //   1  zkhip_msm_stream_new creates all primaries, consecutively, then all secondaries
@@ -205,20 +212,7 @@ static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const voi
   for (int k = 0; k < st->depth; k++) if (!st->ticket_of[k]) { slot = k; break; }
   if (slot < 0) return fail(ZKHIP_ERR_STATE, "every slot of this stream is in flight: collect a result first");
   MsmCtx* cx = &st->ctx[slot];
-  int rc = ZKHIP_OK;
-  if (st->layout == 0) rc = ensure_ctx(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c);
-  else if (!ctx_reusable(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c)) {
-    // the slot's plan adopts the streams made for it by zkhip_msm_stream_new; a plan that has to be made again (a longer MSM) hands
-    // them back first, so that the slot keeps its place on the hardware queues (msm_plan_free skips the null streams)
-    const int d = st->depth;
-    if (cx->planned && !cx->pending) {
-      st->pool[slot] = cx->stream; st->pool[d + slot] = cx->stream2;
-      cx->stream = cx->stream2 = nullptr;
-    }
-    hipStream_t adopt[2] = {st->pool[slot], st->pool[d + slot]};
-    rc = ensure_ctx(cx, len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c, adopt, (st->layout == 2 && d > 1) ? 1 : -1);
-    st->pool[slot] = adopt[0]; st->pool[d + slot] = adopt[1];      // (null once the plan owns them)
-  }
+  int rc = ensure_ctx(cx, st->lane[slot], len ? len : 1, b->table_c, 1, b->table_naf, 0, b->plain_c, (st->layout == 2 && st->depth > 1) ? 1 : -1);
   if (rc != ZKHIP_OK) return rc;
   if (h_scalars && len) {
     // host scalars: one asynchronous copy in front of the MSM's kernels, on the context's own stream (truly asynchronous from pinned
@@ -228,7 +222,7 @@ static int msm_stream_submit_impl(zkhip_msm_stream* st, size_t offset, const voi
       API_HIP(hipMalloc(&st->d_stage[slot], len * 48));
       st->stage_cap[slot] = len;
     }
-    API_HIP(hipMemcpyAsync(st->d_stage[slot], h_scalars, len * 48, hipMemcpyHostToDevice, cx->stream));
+    API_HIP(hipMemcpyAsync(st->d_stage[slot], h_scalars, len * 48, hipMemcpyHostToDevice, st->lane[slot].main));
     d_scalars = st->d_stage[slot];
   }
   const MsmJob job = single_job(b, offset, d_scalars, len, scalars_montgomery);
@@ -317,7 +311,7 @@ int zkhip_msm_dev(const zkhip_bases* bases, size_t offset, const void* d_scalars
   std::lock_guard<std::mutex> lk(g.dev[bases->device].mu);
   if (offset > bases->len || len > bases->len - offset) return fail(ZKHIP_ERR_ARG, "offset + len exceeds the base set");
   MsmCtx* cx = &ps.ctx[0];
-  int rc = ensure_ctx(cx, len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
+  int rc = ensure_ctx(cx, ps.lane[0], len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
   if (rc != ZKHIP_OK) return rc;
   const MsmJob job = single_job(bases, offset, d_scalars, len, scalars_montgomery);
   if ((rc = msm_launch_multi(cx, 1, &job)) == ZKHIP_OK) rc = msm_finish(cx, out_jac);
@@ -337,7 +331,7 @@ int zkhip_msm_submit(const zkhip_bases* bases, size_t offset, const void* d_scal
   if (offset > bases->len || len > bases->len - offset) return fail(ZKHIP_ERR_ARG, "offset + len exceeds the base set");
   MsmCtx* cx = &ps.ctx[slot];
   if (cx->pending) return fail(ZKHIP_ERR_STATE, "slot busy: collect its result first");
-  int rc = ensure_ctx(cx, len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
+  int rc = ensure_ctx(cx, ps.lane[slot], len ? len : 1, bases->table_c, 1, bases->table_naf, 0, bases->plain_c);
   if (rc != ZKHIP_OK) return rc;
   // a stream of MSMs, optionally GATED (ZKHIP_MSM_GATE=1): the accumulation of this one waits for the end of the accumulation
   // submitted before it on another slot, so that two accumulations never share the chip.  Measured (tools/gate_ab.sh, 2^20 terms,
@@ -345,7 +339,7 @@ int zkhip_msm_submit(const zkhip_bases* bases, size_t offset, const void* d_scal
   // head of the next - so the default is off; the gate gives event-timed kernel durations that are per-launch costs.
   static const bool gate = getenv("ZKHIP_MSM_GATE") ? atoi(getenv("ZKHIP_MSM_GATE")) != 0 : false;
   const int prev = ps.last_submit_slot;
-  cx->acc_gate = (gate && prev >= 0 && prev != slot && ps.ctx[prev].planned) ? ps.ctx[prev].ev_acc1 : nullptr;
+  cx->acc_gate = (gate && prev >= 0 && prev != slot && ps.ctx[prev].planned) ? ps.lane[prev].ev_acc1 : nullptr;
   const MsmJob job = single_job(bases, offset, d_scalars, len, scalars_montgomery);
   rc = msm_launch_multi(cx, 1, &job);
   cx->acc_gate = nullptr;                   // (the event belongs to another context: never kept beyond this launch)
@@ -451,22 +445,18 @@ int zkhip_msm_stream_new(const zkhip_bases* bases, int depth, zkhip_msm_stream**
   BIND(bases);
   zkhip_msm_stream* st = new zkhip_msm_stream();
   st->device = bases->device; st->bases = bases; st->depth = depth;
-  st->ctx.resize(depth); st->ticket_of.assign(depth, 0);
+  st->ctx.resize(depth); st->lane.resize(depth); st->ticket_of.assign(depth, 0);
   st->d_stage.assign(depth, nullptr); st->stage_cap.assign(depth, 0);
   st->layout = msm_stream_layout();
-  if (st->layout) {
-    // two passes, as zkhip_prover_create_streams: every primary stream first - consecutive creations go to different hardware
-    // queues -, then the secondaries (none when the contexts keep to their primary)
-    st->pool.assign(2 * (size_t)depth, nullptr);
-    const int n_streams = (st->layout == 2 && depth > 1) ? depth : 2 * depth;
-    for (int k = 0; k < n_streams; k++) {
-      const hipError_t e = hipStreamCreateWithFlags(&st->pool[k], hipStreamNonBlocking);
-      if (e != hipSuccess) {
-        snprintf(t_err, sizeof t_err, "zkhip_msm_stream_new: %s", hipGetErrorString(e));
-        zkhip_msm_stream_free(st);
-        return ZKHIP_ERR_HIP;
-      }
-    }
+  // two passes, as zkhip_prover_create_streams: every primary stream first - consecutive creations go to different hardware
+  // queues -, then the secondaries (none when the contexts keep to their primary); layout 0 leaves both to the slots' first submits
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < depth && st->layout && e == hipSuccess; k++) e = msm_lane_create_main(&st->lane[k]);
+  for (int k = 0; k < depth && (st->layout == 1 || (st->layout == 2 && depth == 1)) && e == hipSuccess; k++) e = msm_lane_create_side(&st->lane[k]);
+  if (e != hipSuccess) {
+    snprintf(t_err, sizeof t_err, "zkhip_msm_stream_new: %s", hipGetErrorString(e));
+    zkhip_msm_stream_free(st);
+    return ZKHIP_ERR_HIP;
   }
   *out = st;
   return ZKHIP_OK;
@@ -475,14 +465,10 @@ int zkhip_msm_stream_new(const zkhip_bases* bases, int depth, zkhip_msm_stream**
 void zkhip_msm_stream_free(zkhip_msm_stream* st) {
   if (!st) return;
   (void)bind_dev(st->device);
-  for (int k = 0; k < st->depth; k++) {
-    if (st->ctx[k].planned) {
-      if (st->ctx[k].pending) { uint64_t drop[36]; (void)msm_finish(&st->ctx[k], drop); }      // never free work space under a running launch
-      msm_plan_free(&st->ctx[k]);
-    }
-    if (st->d_stage[k]) (void)hipFree(st->d_stage[k]);
-  }
-  for (hipStream_t s : st->pool) if (s) (void)hipStreamDestroy(s);      // the streams of slots that never made a plan (a plan destroys its own)
+  for (MsmCtx& c : st->ctx) if (c.pending) { uint64_t drop[36]; (void)msm_finish(&c, drop); }      // never free work space or a lane under a running launch
+  for (MsmCtx& c : st->ctx) if (c.planned) msm_plan_free(&c);
+  for (MsmLane& l : st->lane) msm_lane_free(&l);
+  for (void* p : st->d_stage) if (p) (void)hipFree(p);
   delete st;
 }
 

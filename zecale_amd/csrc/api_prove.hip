@@ -127,25 +127,25 @@ static int prove_split(ProofRun& p, bool gated) {
   const MsmJob jz[4] = {p.jobs[0], p.jobs[1], p.jobs[2], p.jobs[4]}, &jh = p.jobs[3];
   MsmCtx *cz = &ps.ctx[ZK_CTX_Z], *ch = &ps.ctx[ZK_CTX_H];
   const size_t max_z = jz[0].n > jz[3].n ? jz[0].n : jz[3].n;
-  int rc = ensure_ctx(cz, max_z ? max_z : 1, p.tc, 4, p.naf, jobs_terms(jz, 4), 0, ps.pre);
-  if (rc == ZKHIP_OK) rc = ensure_ctx(ch, jh.n, p.tc, 1, p.naf, jobs_terms(&jh, 1));
+  int rc = ensure_ctx(cz, ps.lane[ZK_CTX_Z], max_z ? max_z : 1, p.tc, 4, p.naf, jobs_terms(jz, 4));
+  if (rc == ZKHIP_OK) rc = ensure_ctx(ch, ps.lane[ZK_CTX_H], jh.n, p.tc, 1, p.naf, jobs_terms(&jh, 1));
   if (rc != ZKHIP_OK) return rc == ZKHIP_ERR_ARG ? ZK_PLAN_UNFIT : rc;
   if (!ps.ev_up) API_HIP(hipEventCreateWithFlags(&ps.ev_up, hipEventDisableTiming));
   if (!ps.ev_qap) API_HIP(hipEventCreateWithFlags(&ps.ev_qap, hipEventDisableTiming));
   if (p.z_host) API_HIP(hipMemcpyAsync(ps.dz, p.z_host, p.rd->n_vars * 48, hipMemcpyHostToDevice, ps.st));
   API_HIP(hipEventRecord(ps.ev_up, ps.st));
-  API_HIP(hipStreamWaitEvent(cz->stream, ps.ev_up, 0));
+  API_HIP(hipStreamWaitEvent(ps.lane[ZK_CTX_Z].main, ps.ev_up, 0));
   ps.ms[0] = ms_since(p.t0);
   const auto tl0 = p.t0 = clk::now();
   if ((rc = msm_launch_multi(cz, 4, jz)) != ZKHIP_OK) return ctx_fail(rc, cz);
   rc = qap_h_dev(p.rd, p.dz, ps.st, t_err, sizeof t_err, p.d_z_app);
   if (rc == ZKHIP_OK) {
     hipError_t e = hipEventRecord(ps.ev_qap, ps.st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ch->stream, ps.ev_qap, 0);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ps.lane[ZK_CTX_H].main, ps.ev_qap, 0);
     if (e != hipSuccess) { snprintf(t_err, sizeof t_err, "split proof: %s", hipGetErrorString(e)); rc = ZKHIP_ERR_HIP; }
   }
   if (rc == ZKHIP_OK) {
-    ch->acc_gate = gated ? cz->ev_acc1 : nullptr;        // H's accumulation starts when the first one has ended
+    ch->acc_gate = gated ? ps.lane[ZK_CTX_Z].ev_acc1 : nullptr;        // H's accumulation starts when the first one has ended
     if ((rc = msm_launch_multi(ch, 1, &jh)) != ZKHIP_OK) (void)ctx_fail(rc, ch);
     ch->acc_gate = nullptr;
   }
@@ -190,7 +190,7 @@ static int prove_batched(ProofRun& p, size_t maxlen, bool chain) {
   ProveState& ps = p.ps;
   MsmCtx* cx = &ps.ctx[ZK_MSM_SLOTS];
   const size_t total = jobs_terms(p.jobs, 5);
-  int rc = ensure_ctx(cx, maxlen, p.tc, 5, p.naf, total, 0, ps.pre);
+  int rc = ensure_ctx(cx, ps.lane[ZK_MSM_SLOTS], maxlen, p.tc, 5, p.naf, total);
   if (rc == ZKHIP_ERR_ARG) {
     // (a silent performance cliff) the plan's 32-bit entry positions / slice weights do not hold this key's terms at
     // this window: said once per process, then one launch sequence per MSM
@@ -221,7 +221,7 @@ static int prove_separate(ProofRun& p, size_t maxlen) {
   ProveState& ps = p.ps;
   const int nctx = (maxlen <= ((size_t)1 << 18)) ? 5 : 2;
   for (int k = 0, rc; k < nctx; k++) {
-    if ((rc = ensure_ctx(&ps.ctx[k], maxlen, p.tc, 1, p.naf)) != ZKHIP_OK) return rc;
+    if ((rc = ensure_ctx(&ps.ctx[k], ps.lane[k], maxlen, p.tc, 1, p.naf)) != ZKHIP_OK) return rc;
     if (ps.quad_below) { ps.ctx[k].quad_below = ps.quad_below; ps.ctx[k].one_stream = 1; }
   }
   clk::time_point tl[5];
@@ -276,9 +276,9 @@ static int prove_partial(ProveState& ps, const zkhip_crs* crs, R1csDev* rd, cons
   // A/B pairs; ZKHIP_STREAM_CHAIN=0 restores the two waits, =2 chains every prover instance: +0.8 % for four 2^20 provers, not
   // adopted - the plain entry point's phase timings are the bench's one-proof-alone figures).  A chained proof's phase timings measure
   // enqueueing, not execution.
-  // (only when the launch sequence's context will be used as it stands: a context that ensure_ctx is about to rebuild gets a new stream)
+  // (only when the launch sequence's context will be used as it stands: its lane outlives a plan made again, so the clause guards no stream - it decides which proofs report enqueueing times, never a prover's first)
   static const int chain_env = getenv("ZKHIP_STREAM_CHAIN") ? atoi(getenv("ZKHIP_STREAM_CHAIN")) : 1;
-  const bool chain = chain_env && (ps.quad_below || chain_env == 2) && tc > 0 && crs->batch_msms && ps.ctx[ZK_MSM_SLOTS].stream &&
+  const bool chain = chain_env && (ps.quad_below || chain_env == 2) && tc > 0 && crs->batch_msms &&
                      ctx_reusable(&ps.ctx[ZK_MSM_SLOTS], maxlen, tc, 5, naf, jobs_terms(p.jobs, 5));
   ps.chained_last = chain;
   ps.split_last = false;
@@ -287,7 +287,7 @@ static int prove_partial(ProveState& ps, const zkhip_crs* crs, R1csDev* rd, cons
   const int split_env = g_prove_split.load();
   if (split_env && !chain && !ps.quad_below && tc > 0 && crs->batch_msms && h_len > 0 && a_len > 0)
     if ((rc = prove_split(p, split_env != 2)) != ZK_PLAN_UNFIT) return rc;
-  if ((rc = prove_upload_and_map(p, chain ? ps.ctx[ZK_MSM_SLOTS].stream : ps.st, chain)) != ZKHIP_OK) return rc;
+  if ((rc = prove_upload_and_map(p, chain ? ps.lane[ZK_MSM_SLOTS].main : ps.st, chain)) != ZKHIP_OK) return rc;
   if (tc > 0 && crs->batch_msms)
     if ((rc = prove_batched(p, maxlen, chain)) != ZK_PLAN_UNFIT) return rc;
   return prove_separate(p, maxlen);
@@ -594,16 +594,16 @@ int zkhip_groth16_prove_app(const zkhip_crs* crs, zkhip_r1cs* r1cs, const zkhip_
 // on the queues as the race decides: a pipeline whose busy streams crowd a few queues proves 8-10 % fewer proofs/s for as long as it
 // lives (round 5: 391 against 425-434 proofs/s, instance after instance in one process; same clock, 10 % less power).  A caller
 // that owns several instances therefore creates the streams itself, in two passes over the instances: which = 0 the stream that will be
-// busy (consecutive creations go to different queues), which = 1 the two that idle.
+// busy (consecutive creations go to different queues), which = 1 the two that idle.  The busy one and the first idle one are main and side of the
+// launch sequence's lane (ProveState::lane, held until release()), the other is the QAP map's; each call makes what is missing, so one after the first proof makes nothing.
 int zkhip_prover_create_streams(zkhip_prover* p, int which) {
   if (!p || which < 0 || which > 1) return fail(ZKHIP_ERR_ARG, "null prover or unknown pass");
   BIND(p);
   std::lock_guard<std::mutex> lk(p->mu);
   ProveState& ps = p->ps;
-  if (which == 0) {
-    if (!ps.pre[0] && !ps.ctx[ZK_MSM_SLOTS].planned) API_HIP(hipStreamCreateWithFlags(&ps.pre[0], hipStreamNonBlocking));
-  } else {
-    if (!ps.pre[1] && !ps.ctx[ZK_MSM_SLOTS].planned) API_HIP(hipStreamCreateWithFlags(&ps.pre[1], hipStreamNonBlocking));
+  if (which == 0) API_HIP(msm_lane_create_main(&ps.lane[ZK_MSM_SLOTS]));
+  else {
+    API_HIP(msm_lane_create_side(&ps.lane[ZK_MSM_SLOTS]));
     if (!ps.st) API_HIP(hipStreamCreateWithFlags(&ps.st, hipStreamNonBlocking));
   }
   return ZKHIP_OK;

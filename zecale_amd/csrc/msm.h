@@ -28,6 +28,17 @@ struct MsmJob {
 // the terms of a job that can produce an entry: a base at infinity never does (plans are sized by this, launches counted by it)
 static inline size_t msm_job_terms(const MsmJob& j) { return (j.n_finite && j.n_finite < j.n) ? j.n_finite : j.n; }
 
+// A context's place on the runtime's hardware queues: its streams and the events that order and time its launch sequences.  The context's
+// OWNER holds the lane for as long as the slot exists (all mains of its contexts are made first, then all sides: api_msm.hip); plans own memory only.
+struct MsmLane {     // all zeros: nothing made yet
+  hipStream_t main, side;   // side may stay null: the whole launch sequence then runs on main (stage_reduce)
+  hipEvent_t ev, ev2, ev_acc0, ev_acc1, ev_done;
+};
+hipError_t msm_lane_create_main(MsmLane* lane);      // (the three create what is missing and leave the rest alone)
+hipError_t msm_lane_create_side(MsmLane* lane);
+hipError_t msm_lane_create_events(MsmLane* lane);
+void msm_lane_free(MsmLane* lane);      // destroys what was made: all zeros again (nothing of it may be in flight)
+
 #define ZK_PRIO_BOARD_WORDS (8 * 8 * 2 * 16 * 4 * 16)
 struct MsmCtx {      // all zeros: no plan
   bool planned;        // msm_plan_init succeeded and msm_plan_free has not run since: every field below is valid
@@ -41,11 +52,10 @@ struct MsmCtx {      // all zeros: no plan
   uint8_t win_bits[96];
   size_t B, max_n;
   size_t total_terms;   // bound on the terms of one launch sequence (all jobs): sizes the entry list, the slices and the slot array
-  int one_stream;       // 1: the whole launch sequence on `stream` (a prover that shares the chip); 0: row / column trees side by side
+  int one_stream;       // 1: the whole launch sequence on the lane's main stream (a prover that shares the chip); 0: row / column trees side by side
   uint32_t quad_below;  // reduction launches with fewer outputs than this spread an addition over four lanes (latency) instead of one (total work)
   uint32_t S, T, slot_stride;   // slice length, slice count, words per row of the slot array
-  hipStream_t stream, stream2;   // (stream2 is null in a plan made with one_stream set: stage_reduce then keeps to `stream` whatever one_stream says later)
-  hipEvent_t ev, ev2, ev_acc0, ev_acc1, ev_done;
+  MsmLane* lane;        // not owned: this context's streams and events (without a side stream stage_reduce keeps to main whatever one_stream says later)
   hipEvent_t acc_gate;  // optional (not owned): the accumulation of this launch sequence starts after this event - the end of the
                         // accumulation of the MSM submitted before it on another context (zkhip_msm_submit): the sort of MSM i+1 and
                         // the reduction of MSM i-1 run under the accumulation of MSM i, two accumulations never share the chip
@@ -99,15 +109,15 @@ void msm_force_lockstep(int mode, int min_buckets);
 // the route the plan's last launch took, read back from the device: 1 lockstep, 0 sliced, -1 not an Edwards launch
 int msm_last_acc_path(MsmCtx* ctx, int* out);
 // total_terms: upper bound on the terms (finite bases) of all K jobs of one launch together; 0 = K * max_n
-// adopt: two streams created by the caller beforehand (or null): the plan's main and side stream - the plan owns them from here on
-// (the entries it took are set to null; a one_stream plan takes adopt[0] alone and has no side stream at all)
-// one_stream: 1 / 0 the plan's one_stream from the start, -1 the environment (ZKHIP_MSM_ONE_STREAM, default 0)
-int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms = 0, hipStream_t* adopt = nullptr, int one_stream = -1);
+// lane: the caller's, with its main stream and its events made; the plan refers to it and never creates or destroys a part of it
+// one_stream: 1 / 0 the plan's one_stream from the start, -1 the environment (ZKHIP_MSM_ONE_STREAM, default 0): msm_one_stream resolves it
+int msm_one_stream(int one_stream);
+int msm_plan_init(MsmCtx* ctx, MsmLane* lane, size_t max_n, int c, int merged, int K, size_t total_terms = 0, int one_stream = -1);
 // a per-device event recorded once: the origin of last_acc_begin_ms / last_acc_end_ms
 hipEvent_t msm_time_base();
 // record the origin again (now): intervals read afterwards are relative to this moment
 int msm_time_base_reset();
-void msm_plan_free(MsmCtx* ctx);
+void msm_plan_free(MsmCtx* ctx);      // the plan's memory; the lane stays with its owner
 int msm_bases_convert(const uint64_t* d_bases_abi, size_t n, AffPacked* d_out, uint8_t* d_inf_flags, char* errbuf, size_t errlen);
 // table_stride: distance (in points) between the levels of a precomputed table (merged plans only)
 // edw: the table in precomputed Edwards form (or null)

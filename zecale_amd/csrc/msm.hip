@@ -1668,25 +1668,42 @@ int msm_last_entries(MsmCtx* ctx, uint64_t* out) {
 static void read_accumulate_times(MsmCtx* ctx) {
   debug_dump(ctx);
   float ms = 0;
-  (void)hipEventElapsedTime(&ms, ctx->ev_acc0, ctx->ev_acc1);
+  (void)hipEventElapsedTime(&ms, ctx->lane->ev_acc0, ctx->lane->ev_acc1);
   ctx->last_accumulate_ms = ms;
   hipEvent_t base = msm_time_base();
   float t0 = 0, t1 = 0;
   // (a launch recorded before the last msm_time_base_reset would be measured against an origin that lies AFTER it: no interval)
   if (ctx->acc_gen != time_base_gen()) { ctx->last_acc_begin_ms = ctx->last_acc_end_ms = -1.f; return; }
-  if (base && hipEventElapsedTime(&t0, base, ctx->ev_acc0) == hipSuccess && hipEventElapsedTime(&t1, base, ctx->ev_acc1) == hipSuccess) {
+  if (base && hipEventElapsedTime(&t0, base, ctx->lane->ev_acc0) == hipSuccess && hipEventElapsedTime(&t1, base, ctx->lane->ev_acc1) == hipSuccess) {
     ctx->last_acc_begin_ms = t0; ctx->last_acc_end_ms = t1;
   }
 }
 
-int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t total_terms, hipStream_t* adopt, int one_stream) {
+// (non-blocking streams: no implicit ordering against the null stream - the host application's, e.g. torch's)
+hipError_t msm_lane_create_main(MsmLane* lane) { return lane->main ? hipSuccess : hipStreamCreateWithFlags(&lane->main, hipStreamNonBlocking); }
+hipError_t msm_lane_create_side(MsmLane* lane) { return lane->side ? hipSuccess : hipStreamCreateWithFlags(&lane->side, hipStreamNonBlocking); }
+// (ev_done, the end of a launch sequence, is BLOCKING: the host thread that collects the result sleeps instead of spinning - provers wait side by side and share the cores with the witness generators)
+hipError_t msm_lane_create_events(MsmLane* lane) {
+  const std::pair<hipEvent_t*, unsigned> want[] = {{&lane->ev, hipEventDisableTiming}, {&lane->ev2, hipEventDisableTiming}, {&lane->ev_acc0, hipEventDefault},
+                                                   {&lane->ev_acc1, hipEventDefault}, {&lane->ev_done, hipEventBlockingSync | hipEventDisableTiming}};
+  for (const auto& [ev, flags] : want) if (!*ev) { const hipError_t e = hipEventCreateWithFlags(ev, flags); if (e != hipSuccess) return e; }
+  return hipSuccess;
+}
+void msm_lane_free(MsmLane* lane) {
+  for (hipStream_t st : {lane->main, lane->side}) if (st) (void)hipStreamDestroy(st);
+  for (hipEvent_t ev : {lane->ev, lane->ev2, lane->ev_acc0, lane->ev_acc1, lane->ev_done}) if (ev) (void)hipEventDestroy(ev);
+  *lane = MsmLane{};
+}
+int msm_one_stream(int one_stream) { return one_stream >= 0 ? (one_stream ? 1 : 0) : env_int("ZKHIP_MSM_ONE_STREAM", 0, 0, 1); }
+
+int msm_plan_init(MsmCtx* ctx, MsmLane* lane, size_t max_n, int c, int merged, int K, size_t total_terms, int one_stream) {
   memset(ctx, 0, sizeof *ctx);
   ctx->total_terms = total_terms = plan::total_terms(K, max_n, total_terms);
-  (void)msm_time_base();
   if (K < 1 || K > MSM_MAX_JOBS || (!merged && K != 1)) return ZKHIP_ERR_ARG;
+  if (!(ctx->lane = lane) || !lane->main || !lane->ev || !lane->ev2 || !lane->ev_acc0 || !lane->ev_acc1 || !lane->ev_done) return ZKHIP_ERR_ARG;
   ctx->K = K;
   ctx->quad_below = (uint32_t)env_int("ZKHIP_QUAD_BELOW", 65536, 1, 1 << 30);
-  ctx->one_stream = one_stream >= 0 ? (one_stream ? 1 : 0) : env_int("ZKHIP_MSM_ONE_STREAM", 0, 0, 1);
+  ctx->one_stream = msm_one_stream(one_stream);
   // 108 * (W * 2^(c-1) + 2T) * 4 bytes must stay below 4 GiB (buffer descriptor); checked below
   if (c < 4 || c > (merged ? 22 : 18)) return ZKHIP_ERR_ARG;
   ctx->c = c;
@@ -1700,19 +1717,6 @@ int msm_plan_init(MsmCtx* ctx, size_t max_n, int c, int merged, int K, size_t to
   ctx->max_n = max_n;
   ctx->logL = env_int("ZKHIP_SUM_LOGL", 2, 2, 5); ctx->L = 1 << ctx->logL;      // fan-in of the reduction trees (tuning knob; the R arrays are sized for L >= 4)
   size_t nb = ctx->B * ctx->W;
-  // (a plan that starts as one_stream never creates a side stream: an idle stream still takes a place in the runtime's round over its hardware queues)
-  if (adopt && adopt[0] && (adopt[1] || ctx->one_stream)) { ctx->stream = adopt[0]; ctx->stream2 = adopt[1]; adopt[0] = adopt[1] = nullptr; }
-  else {
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));   // no implicit ordering against the null stream (the host application's, e.g. torch's)
-    if (!ctx->one_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-  }
-  HIP_TRY(hipEventCreateWithFlags(&ctx->ev, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&ctx->ev2, hipEventDisableTiming));
-  HIP_TRY(hipEventCreate(&ctx->ev_acc0));
-  HIP_TRY(hipEventCreate(&ctx->ev_acc1));
-  // completion of a launch sequence: a BLOCKING event, so that the host thread that collects the result sleeps instead of
-  // spinning on the stream (several prover instances wait side by side and share the cores with the witness generators)
-  HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventBlockingSync | hipEventDisableTiming));
   if ((size_t)ctx->Wd * max_n >= ((size_t)1 << 31)) return ZKHIP_ERR_ARG;   // entry = 31-bit point index + sign
   if ((size_t)ctx->Wd * total_terms >= ((size_t)1 << 32)) return ZKHIP_ERR_ARG;  // positions in the entry list are 32-bit
   const int sort_parts = env_int("ZKHIP_SORT_PARTS", 1024, 64, 8192), sort_tile = env_int("ZKHIP_SORT_TILE", 1024, 256, 16384);      // (tuning knobs)
@@ -1780,8 +1784,6 @@ void msm_plan_free(MsmCtx* ctx) {
                   ctx->fix_list, ctx->fix_short, ctx->dbg_times, ctx->goff, ctx->prio_board, ctx->order, ctx->ord_hist};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (ctx->win_host) (void)hipHostFree(ctx->win_host);
-  for (hipStream_t st : {ctx->stream, ctx->stream2}) if (st) (void)hipStreamDestroy(st);
-  for (hipEvent_t ev : {ctx->ev, ctx->ev2, ctx->ev_acc0, ctx->ev_acc1, ctx->ev_done}) if (ev) (void)hipEventDestroy(ev);
   memset(ctx, 0, sizeof *ctx);
 }
 
@@ -1837,7 +1839,7 @@ struct Launch {      // what the stages of one msm_launch_multi share
 // windows of the jobs this call does not use (K < ctx->K) stay empty: their rows of hist are written as zeros by grid row k.
 static int stage_sort(MsmCtx* ctx, const Launch& lp) {
   const int KK = ctx->merged ? ctx->K : 1;                       // every bucket window's rows of hist are (re)written
-  hipStream_t st = ctx->stream;
+  hipStream_t st = ctx->lane->main;
   WindowPlan wp = {};
   for (int w = 0; w < ctx->Wd; w++) { wp.off[w] = ctx->win_off[w]; wp.bits[w] = ctx->win_bits[w]; }
   DigitJobs dj = {};
@@ -1867,9 +1869,9 @@ static int stage_sort(MsmCtx* ctx, const Launch& lp) {
 
 // (2) batched-affine levels: the sorted list is summed pairwise inside every bucket, ctx->aff_levels times
 static int stage_affine_levels(MsmCtx* ctx, Launch& lp) {
-  hipStream_t st = ctx->stream;
+  hipStream_t st = ctx->lane->main;
   ctx->acc_gen = time_base_gen();
-  if (ctx->aff_levels > 0) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));     // the timed accumulation includes the affine levels
+  if (ctx->aff_levels > 0) HIP_TRY(hipEventRecord(ctx->lane->ev_acc0, st));     // the timed accumulation includes the affine levels
   for (int l = 0; l < ctx->aff_levels; l++) {
     const size_t m_out = plan::level_bound(lp.m_cur, lp.nb);
     hipLaunchKernelGGL(k_half_counts, dim3(nblk(lp.nb, 256)), dim3(256), 0, st, lp.cur_cnt, ctx->lcnt[l], lp.nb);
@@ -1894,7 +1896,7 @@ static int stage_affine_levels(MsmCtx* ctx, Launch& lp) {
 
 // (3) slice weights, the lockstep route's bucket order, the slot array's zero fill, the accumulation between ev_acc0 and ev_acc1
 static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
-  hipStream_t st = ctx->stream;
+  hipStream_t st = ctx->lane->main;
   const size_t nb = lp.nb;
   const bool dense = ctx->aff_levels > 0;
   // slice weights: goff = exclusive scan of (8 count - 7) over the non-empty buckets of the list k_accumulate sums (nb + 1 values)
@@ -1925,7 +1927,7 @@ static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
 #endif
   if (ctx->dbg_times) HIP_TRY(hipMemsetAsync(ctx->dbg_times, 0, ((size_t)ctx->T / 64 + 8) * 32, st));
   if (ctx->acc_gate) HIP_TRY(hipStreamWaitEvent(st, ctx->acc_gate, 0));
-  if (!dense) HIP_TRY(hipEventRecord(ctx->ev_acc0, st));
+  if (!dense) HIP_TRY(hipEventRecord(ctx->lane->ev_acc0, st));
   static const int acc_prio = env_int("ZKHIP_ACC_PRIO", 1, 0, 2);      // 2: by quarters of the slice only (no board)
   const uint32_t prio_tag = (++ctx->prio_seq & 0x7fffu) + 1u;     // (see k_accumulate: the wave that is behind asks for priority; 0 = the arbiter's own order)
   if (lp.edw)
@@ -1933,7 +1935,7 @@ static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
   const auto accumulate = lp.edw ? k_accumulate_edw : (ctx->K == 1 || dense) ? k_accumulate<1> : k_accumulate<MSM_MAX_JOBS>;
   hipLaunchKernelGGL(accumulate, dim3(nblk(lp.T_run, 256)), dim3(256), 0, st, lp.bp, lp.bshift, dense ? (const uint32_t*)nullptr : ctx->entries, lp.cur_off, lp.cur_cnt, ctx->goff, (uint32_t)nb,
                      lp.S_run, lp.tight, lp.T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
-  HIP_TRY(hipEventRecord(ctx->ev_acc1, st));
+  HIP_TRY(hipEventRecord(ctx->lane->ev_acc1, st));
   ctx->last_S = lp.S_run; ctx->last_T = lp.T_run; ctx->last_tight = lp.tight;
   HIP_TRY(hipGetLastError());
   return ZKHIP_OK;
@@ -1948,7 +1950,7 @@ static RedKernels red_kernels(bool edw) {
 
 // (4) stitching: fold the F pieces of the buckets that have several (lists made by k_accumulate), then L + F for every cut bucket
 static int stage_stitch(MsmCtx* ctx, const Launch& lp) {
-  hipStream_t st = ctx->stream;
+  hipStream_t st = ctx->lane->main;
   const uint32_t nb = (uint32_t)lp.nb, T_run = lp.T_run;
   if (T_run > 2) {
     const bool fold_quads = T_run < (1u << 18) && ctx->quad_below > 1024;     // a small launch that has the chip to itself is latency-bound
@@ -2007,17 +2009,17 @@ static void enqueue_tail(const RedKernels& red, hipStream_t st, uint32_t* items,
 // (5) bucket reduction: (a) two-level split of the bucket index (row sums on stream 1, column sums on stream 2: plain trees), (b) the two
 // small weighted sums per window by bit planes and (c) per window R * hi + lo (enqueue_tail), on stream 1.
 static int stage_reduce(MsmCtx* ctx, const Launch& lp) {
-  hipStream_t st = ctx->stream;
+  hipStream_t st = ctx->lane->main;
   // the row and the column tree run side by side on two streams - unless this context shares the chip with others anyway (one_stream)
-  hipStream_t st2 = (ctx->one_stream || !ctx->stream2) ? ctx->stream : ctx->stream2;
+  hipStream_t st2 = (ctx->one_stream || !ctx->lane->side) ? ctx->lane->main : ctx->lane->side;
   const int c = ctx->c, W = ctx->W, G = 2 * W;
   const uint32_t Rr = 1u << plan::lo_bits(c), Hh = 1u << plan::hi_bits(c), Nn = Rr > Hh ? Rr : Hh;
-  HIP_TRY(hipEventRecord(ctx->ev, st));
-  HIP_TRY(hipStreamWaitEvent(st2, ctx->ev, 0));
+  HIP_TRY(hipEventRecord(ctx->lane->ev, st));
+  HIP_TRY(hipStreamWaitEvent(st2, ctx->lane->ev, 0));
   uint32_t* rows = enqueue_tree(ctx, lp, st, Rr, 0, ctx->segS);       // [W][H][R] -> [W][H]  (sum over lo, contiguous)
   uint32_t* cols = enqueue_tree(ctx, lp, st2, Hh, Rr, ctx->colS);     // [W][H][R] -> [W][R]  (sum over hi, stride R)
-  HIP_TRY(hipEventRecord(ctx->ev2, st2));
-  HIP_TRY(hipStreamWaitEvent(st, ctx->ev2, 0));
+  HIP_TRY(hipEventRecord(ctx->lane->ev2, st2));
+  HIP_TRY(hipStreamWaitEvent(st, ctx->lane->ev2, 0));
   hipLaunchKernelGGL(k_place_hilo, dim3(nblk((size_t)G * Nn * 4, 256)), dim3(256), 0, st, rows, cols, (uint32_t)W, Hh, Rr, Nn, ctx->hilo);
   enqueue_tail(lp.red, st, ctx->hilo, W, Nn, plan::lo_bits(c), ctx->merged == 2, ctx->planes, ctx->win_abi);
   HIP_TRY(hipGetLastError());
@@ -2026,8 +2028,8 @@ static int stage_reduce(MsmCtx* ctx, const Launch& lp) {
 
 // (6) the window results to the host; ev_done ends the launch sequence
 static int stage_copy_out(MsmCtx* ctx, const Launch& lp) {
-  HIP_TRY(hipMemcpyAsync(ctx->win_host, ctx->win_abi, (size_t)ctx->W * 48 * 8 * (ctx->merged == 2 ? 2 : 1), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->win_host, ctx->win_abi, (size_t)ctx->W * 48 * 8 * (ctx->merged == 2 ? 2 : 1), hipMemcpyDeviceToHost, ctx->lane->main));
+  HIP_TRY(hipEventRecord(ctx->lane->ev_done, ctx->lane->main));
   ctx->win_edw = lp.edw;      // what win_host will hold for THIS launch (the context may serve an XYZZ set next)
   ctx->pending = true;        // only a completely enqueued sequence is collectable; a failed launch leaves the context reusable
   return ZKHIP_OK;
@@ -2106,7 +2108,7 @@ int msm_finish_multi(MsmCtx* ctx, int K, uint64_t* out_jac) {
   if (!ctx->pending || !ctx->merged || K < 1 || K > ctx->K) return ZKHIP_ERR_STATE;
   ctx->pending = false;
   if (ctx->pending_n) {
-    HIP_TRY(zk_event_wait(ctx->ev_done));
+    HIP_TRY(zk_event_wait(ctx->lane->ev_done));
     read_accumulate_times(ctx);
   }
   for (int k = 0; k < K; k++) {
@@ -2135,7 +2137,7 @@ int msm_finish(MsmCtx* ctx, uint64_t out_jac[36]) {
     inf.X.to_limbs(out_jac); inf.Y.to_limbs(out_jac + 12); inf.Z.to_limbs(out_jac + 24);
     return ZKHIP_OK;
   }
-  HIP_TRY(zk_event_wait(ctx->ev_done));
+  HIP_TRY(zk_event_wait(ctx->lane->ev_done));
   read_accumulate_times(ctx);
 
   // host: sum_w 2^(c w) W_w  (Horner from the top window)
