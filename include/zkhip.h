@@ -486,6 +486,45 @@ int zkhip_bls12_377_groth16_verify_checked(const uint64_t vk_alpha_g1[12], const
                                            const uint64_t* vk_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t proof_a[12],
                                            const uint64_t proof_b[24], const uint64_t proof_c[12], uint8_t* status);
 
+/* ---- combined nested batches: ONE random-combination check for a whole batch ---------------------------------------------------
+ * zkhip_nested_verifier_verify_batch answers "which of these proofs are valid?" and pays four Miller pairs and a full final
+ * exponentiation per proof.  Screening asks "are these ALL valid?".  For proofs (A_i, B_i, C_i) with inputs x_i under one nested key
+ * and independent non-zero 128-bit scalars rho_i the batch is accepted iff
+ *     prod_i e(rho_i A_i, B_i) * e(S_acc, -g2) * e(sigma alpha, -beta) * e(S_C, -delta) == 1,
+ *     sigma = sum_i rho_i (mod r),  S_acc = sigma ABC_0 + sum_j (sum_i rho_i x_ij mod r) ABC_j,  S_C = sum_i rho_i C_i
+ * (r the order of BLS12-377's groups, x_ij the low 253 bits of the input's canonical value mod r, e and "== 1" those of the per-proof
+ * route): ONE Miller pair, two 128-bit scalar multiplications and a share of two reduction trees per proof on the device, no input
+ * accumulator chain; the sums, k + 1 scalar multiplications for S_acc, the three shared pairs and the single final exponentiation
+ * once per batch on the host.  GT has prime order r, so WHEN EVERY POINT HAS ORDER r a batch with an invalid proof passes with
+ * probability about 2^-128 over the choice of the rho_i.
+ * PRECONDITIONS on an unchecked handle: those of zkhip_nested_verifier_verify_batch - and they matter MORE here.  There a point outside
+ * the group of order r spoils the verdict of its own proof; here the argument for the whole batch rests on GT elements of order r:
+ * with a point of small order somebody can make an invalid proof whose error term has small order and is cancelled by the random
+ * scalar with noticeable probability, or by a second proof.  Proofs somebody else made go through a handle of
+ * zkhip_nested_verifier_new_checked with `status` set.
+ * THE STATEMENT: this route answers the group law's.  The per-proof route reproduces the host's affine accumulator chain, and for one
+ * kind of statement the host says 0 where the group law says valid - the accumulator meets -2^j ABC_i at a CLEAR bit j of input i;
+ * this route ACCEPTS such a statement (and never hands a proof to the host for its accumulator: there is no chain).
+ * What a proof does to the batch: a point off its curve (all zero included: the nested format has no infinity) fails the batch and is
+ * left out of the value; so does a B whose line schedule has a zero slope denominator - it cannot have order r, so under the
+ * precondition failing is right; zkhip_nested_verifier_last_degenerate counts them in the last combined batch (the per-proof route
+ * hands such a proof to the host).  rho_i A_i = O (an A of small order, e.g. (-1, 0) under an even scalar): that pair contributes one.
+ * all_ok = 1 iff the check passes.  rho: count x 2 words (little endian, 128 bits each, none zero: ZKHIP_ERR_ARG), or NULL to draw
+ * them from the OS (getrandom; ZKHIP_ERR_STATE if that fails, there is no weaker generator behind it) - a caller-supplied rho is for
+ * tests and reproducible measurements only: scalars an adversary knows or can predict prove nothing.
+ * status: NULL, or count bytes on a handle of zkhip_nested_verifier_new_checked: the checks of
+ * zkhip_nested_verifier_verify_batch_checked run in front, status[i] is that route's refusal byte (ENCODING / OFF_CURVE / NOT_ORDER_R
+ * with its mask) or 0; a refused proof is left out of the product and the sums and makes all_ok 0.  status != NULL on an unchecked
+ * handle: ZKHIP_ERR_STATE.  count == 0: all_ok = 1.  A failed batch does not say which proof is at fault: the per-proof routes do.
+ * zkhip_bls12_377_groth16_verify_all: the same check on the host alone (no device, no zkhip_init; the per-proof work on up to 16
+ * threads), the route the device one is pinned on. */
+int zkhip_nested_verifier_verify_all(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
+                                     const uint64_t* rho, int* all_ok, uint8_t* status);
+int zkhip_nested_verifier_last_degenerate(const zkhip_nested_verifier* v, size_t* out);
+int zkhip_bls12_377_groth16_verify_all(const uint64_t vk_alpha_g1[12], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                       const uint64_t* vk_abc, size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs, size_t count,
+                                       const uint64_t* rho, int* all_ok);
+
 /* replaces: libzecale::aggregator_circuit<wppT, wsnarkT, nverifierT, NumProofs>(inputs_per_nested_proof)
  * (libzecale/circuits/aggregator_circuit.hpp:32-114; constructor .tcc:17-98): builds the constraint system.
  * num_proofs 1 .. 32 (one result bit per nested proof, packed into one primary input), inputs_per_proof 1 .. 16; anything else:
@@ -759,6 +798,14 @@ int zkhip_internal_verify_all_finish_ms(const zkhip_verifier* v, double* ms);
  * zkhip_nested_verifier_verify_batch.  A point off its curve: ZKHIP_ERR_ARG on both routes. */
 int zkhip_internal_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
 int zkhip_internal_nested_pairing_product(int route, const uint64_t* g1, const uint64_t* g2, size_t pairs_per_product, size_t count, uint64_t* out);
+/* nested_verify_all_value: the REDUCED GT value of zkhip_nested_verifier_verify_all's combined product over the proofs that are not
+ * left out (12 x 6 ABI limbs; one iff the product check passes) for the handle's key; rho is required.  route 0: the host code of
+ * zkhip_bls12_377_groth16_verify_all; route 1: the device route.  On a handle of zkhip_nested_verifier_new_checked both routes run the
+ * point checks first and leave a refused proof out.  nested_verify_all_finish_ms: the host's time in the last device-route call on this
+ * handle behind the last chunk's synchronisation (the sums, the scalar multiplications, the shared pairs, the final exponentiation). */
+int zkhip_internal_nested_verify_all_value(int route, zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs,
+                                           size_t count, const uint64_t* rho, uint64_t out[72]);
+int zkhip_internal_nested_verify_all_finish_ms(const zkhip_nested_verifier* v, double* ms);
 /* Test hook (no counterpart), HOST ONLY - works without a device: the prover's tail (row a9) on the paths a healthy proof never
  * takes: `rounds` proofs abandoned between the start of the tail's key-only scalar multiplications and their collection, the key's
  * tables freed at once (run under the CPU AddressSanitizer build); a delta of small order (`small_order_g1`, e.g. (1, 0)) whose

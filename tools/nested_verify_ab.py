@@ -10,7 +10,14 @@ per batch the unchecked and the checked call on ONE checked handle and the same 
 of a library built from the parent commit in the same turns (nothing was added to that route: the two must agree within the spread of
 the repeats), and the wrapping stream without a screener, with an unchecked and with a checked one.  No gate: the ratio is the number on
 file.
-Usage: python tools/nested_verify_ab.py [--out FILE] [--stream N] [--gpu-slots K] [--checked [--parent-lib libzkhip.so]]"""
+--combined measures the COMBINED route (profiles/nested_verify_combined.txt): all-valid batches at 1, 64, 1,024 and 16,384 proofs, scalars
+drawn from the OS; verify_all on an unchecked handle, verify_all with status on a checked one, the two per-proof routes and, with
+--parent-lib, the parent build's two per-proof routes take turns in one run, medians of five.  CONDITION 1: this build's per-proof
+routes differ from the parent build's by no more than the spread (max - min) of their five repeats, the larger of the two builds'.
+CONDITION 2: at 16,384 proofs each combined route is faster than its per-proof route by more than both routes' spreads.  The ratio is
+recorded, not gated.  Then a batch WITH an invalid proof through verify_batch_combined (both routes run) against the checked batch, and
+the wrapping stream with a checked and with a combined screener on all-valid batches of 64.
+Usage: python tools/nested_verify_ab.py [--out FILE] [--stream N] [--gpu-slots K] [--checked | --combined] [--parent-lib libzkhip.so]"""
 import argparse
 import os
 import sys
@@ -34,18 +41,26 @@ SCREEN_BATCH = 64
 class ParentVerifier:
     """zkhip_nested_verifier_* of ANOTHER build of the library (the parent commit's), loaded beside this one: its unchecked route"""
 
-    def __init__(self, path, vk, k):
+    def __init__(self, path, vk, k, checked=False):
         import ctypes
         self.ct, self.lib = ctypes, ctypes.CDLL(path)
         u64p = ctypes.POINTER(ctypes.c_uint64)
         self.lib.zkhip_nested_verifier_new.argtypes = [u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        self.lib.zkhip_nested_verifier_new_checked.argtypes = [u64p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
         self.lib.zkhip_nested_verifier_verify_batch.argtypes = [ctypes.c_void_p, u64p, u64p, ctypes.c_size_t, ctypes.c_void_p]
+        self.lib.zkhip_nested_verifier_verify_batch_checked.argtypes = [ctypes.c_void_p, u64p, u64p, ctypes.c_size_t, ctypes.c_void_p]
         self.lib.zkhip_nested_verifier_free.argtypes = [ctypes.c_void_p]
         self.p = lambda a: a.ctypes.data_as(u64p)
         assert self.lib.zkhip_init(0) == 0
         self.handle = ctypes.c_void_p()
         self.vk = np.ascontiguousarray(vk, dtype=np.uint64)
-        assert self.lib.zkhip_nested_verifier_new(self.p(self.vk), k, ctypes.byref(self.handle)) == 0
+        new = self.lib.zkhip_nested_verifier_new_checked if checked else self.lib.zkhip_nested_verifier_new
+        assert new(self.p(self.vk), k, ctypes.byref(self.handle)) == 0
+
+    def verify_batch_checked(self, inp, prf):
+        st = np.zeros(prf.shape[0], dtype=np.uint8)
+        assert self.lib.zkhip_nested_verifier_verify_batch_checked(self.handle, self.p(inp), self.p(prf), prf.shape[0], st.ctypes.data) == 0
+        return st
 
     def verify_batch(self, inp, prf):
         ok = np.zeros(prf.shape[0], dtype=np.uint8)
@@ -97,16 +112,109 @@ def checked_table(say, zkhip, vk, pool, pool_in, parent_lib):
     return ver, fallbacks
 
 
+def combined_table(say, zkhip, vk, pool, pool_in, parent_lib):
+    """the combined routes, the per-proof routes and the parent build's per-proof routes taking turns on the same all-valid batches"""
+    valid, valid_in = pool[:-1], pool_in[:-1]                # (the pool's last statement is the invalid one)
+    n_valid = len(valid)
+    ver, plain = zkhip.NestedVerifier(vk, 1, checked=True), zkhip.NestedVerifier(vk, 1)
+    parent = ParentVerifier(parent_lib, vk, 1, checked=True) if parent_lib else None
+    finish, degenerate, fallbacks = {}, [0], [0]
+
+    def combined(i, p):
+        ok = plain.verify_all(i, p)
+        finish.setdefault(len(p), []).append(plain.last_finish_ms())
+        degenerate[0] += plain.last_degenerate()
+        return ok
+
+    def combined_status(i, p):
+        ok, st = ver.verify_all(i, p, status=True)
+        degenerate[0] += ver.last_degenerate()
+        return ok and not any(st)
+
+    def per_proof(i, p):
+        ok = plain.verify_batch(i, p).all()
+        fallbacks[0] += plain.last_fallbacks()
+        return ok
+
+    def checked(i, p):
+        codes, masks = ver.verify_batch_checked(i, p)
+        fallbacks[0] += ver.last_fallbacks()
+        return not (codes | masks).any()
+    routes = [("combined", combined), ("comb+status", combined_status), ("per-proof", per_proof), ("checked", checked)]
+    if parent:
+        routes += [("parent", lambda i, p: parent.verify_batch(i, p).all()), ("parent chk", lambda i, p: not parent.verify_batch_checked(i, p).any())]
+    for _, fn in routes:
+        fn(valid_in[:1], valid[:1])                          # work space
+    finish.clear()
+    spread = lambda v: max(v) - min(v)
+    say("%8s %-12s %10s %10s %10s %14s" % ("count", "route", "median ms", "min ms", "max ms", "verif./s"))
+    ahead, cond1, cond2, ratios = None, True, True, {}
+    for count in COUNTS:
+        idx = [i % n_valid for i in range(count)]
+        inp, prf = np.ascontiguousarray(valid_in[idx]), np.ascontiguousarray(valid[idx])
+        ms = {name: [] for name, _ in routes}
+        for _ in range(CHECKED_ROUNDS):
+            for name, fn in routes:
+                t = time.perf_counter()
+                ok = fn(inp, prf)
+                ms[name].append((time.perf_counter() - t) * 1e3)
+                assert ok, "%s on an all-valid batch of %d" % (name, count)
+        med = {name: sorted(v)[CHECKED_ROUNDS // 2] for name, v in ms.items()}
+        for name, _ in routes:
+            say("%8d %-12s %10.2f %10.2f %10.2f %14.1f" % (count, name, med[name], min(ms[name]), max(ms[name]), count / med[name] * 1e3))
+        fin = sorted(finish[count])[len(finish[count]) // 2]
+        ratios[count] = (med["combined"] / med["per-proof"], med["comb+status"] / med["checked"])
+        line = "%8d combined / per-proof = %.3f; combined with status / checked = %.3f; host finish %.2f ms = %.0f %% of the combined batch" % (
+            count, ratios[count][0], ratios[count][1], fin, fin / med["combined"] * 100)
+        if parent:
+            for mine, theirs in (("per-proof", "parent"), ("checked", "parent chk")):
+                d, sp = med[mine] - med[theirs], max(spread(ms[mine]), spread(ms[theirs]))
+                cond1 = cond1 and abs(d) <= sp
+                line += "; %s - parent's = %+.2f ms, spread %.2f ms: %s" % (mine, d, sp, "within" if abs(d) <= sp else "BEYOND")
+        say(line)
+        if ahead is None and med["combined"] < med["per-proof"]:
+            ahead = count
+        if count == 16384:
+            for comb, pp in (("combined", "per-proof"), ("comb+status", "checked")):
+                gap, sp = med[pp] - med[comb], max(spread(ms[comb]), spread(ms[pp]))
+                cond2 = cond2 and gap > sp
+                say("%8d %s is %.2f ms faster than %s; the larger spread of the two is %.2f ms" % (count, comb, gap, pp, sp))
+    say("the combined check is ahead of the per-proof batch from count %s on (smallest measured count at which its batch is faster)" % (ahead or "none measured"))
+    if parent:
+        say("CONDITION 1, no regression (both per-proof routes within the spread of the five repeats of the parent build's, at every count): %s" % ("met" if cond1 else "MISSED"))
+    say("CONDITION 2, speed (at 16,384 proofs each combined route faster than its per-proof route by more than both spreads): %s  (%.3f, %.3f; recorded, not gated)"
+        % ("met" if cond2 else "MISSED", ratios[16384][0], ratios[16384][1]))
+    # a batch WITH an invalid proof: verify_batch_combined runs the combined check, then the checked batch
+    say("a batch with ONE invalid proof on the checked handle: verify_batch_combined (both routes run) against verify_batch_checked")
+    for count in (64, 1024, 16384):
+        idx = [i % n_valid for i in range(count)]
+        inp, prf = np.ascontiguousarray(valid_in[idx]), np.ascontiguousarray(valid[idx])
+        inp[count // 2], prf[count // 2] = pool_in[-1], pool[-1]
+        both, one = [], []
+        for _ in range(CHECKED_ROUNDS):
+            t = time.perf_counter(); a = ver.verify_batch_combined(inp, prf); both.append((time.perf_counter() - t) * 1e3)
+            t = time.perf_counter(); b = ver.verify_batch_checked(inp, prf); one.append((time.perf_counter() - t) * 1e3)
+            assert (a[0] == b[0]).all() and (a[1] == b[1]).all() and int(b[0].sum()) == 1
+        mb, mo = sorted(both)[CHECKED_ROUNDS // 2], sorted(one)[CHECKED_ROUNDS // 2]
+        say("%8d both routes %10.2f ms, checked alone %10.2f ms: %.3f" % (count, mb, mo, mb / mo))
+    say("proofs with a degenerate line schedule (last_degenerate) summed over every combined batch of this run: %d" % degenerate[0])
+    if parent:
+        parent.free()
+    plain.free()
+    return ver, fallbacks[0], cond1 and cond2 and degenerate[0] == 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--checked", action="store_true", help="measure the checked route against the unchecked one instead of the GPU against the host")
-    ap.add_argument("--parent-lib", default=None, help="with --checked: a libzkhip.so built from the parent commit, for its unchecked route in the same turns")
+    ap.add_argument("--combined", action="store_true", help="measure the combined (random-combination) route against the per-proof routes on all-valid batches")
+    ap.add_argument("--parent-lib", default=None, help="with --checked or --combined: a libzkhip.so built from the parent commit, for its per-proof routes in the same turns")
     ap.add_argument("--stream", type=int, default=1024, help="proofs per block of the stream measurement (0: skip)")
     ap.add_argument("--gpu-slots", type=int, default=24)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "nested_verify_checked.txt" if args.checked else "nested_verify_gpu.txt")
+        args.out = os.path.join(ROOT, "profiles", "nested_verify_combined.txt" if args.combined else "nested_verify_checked.txt" if args.checked else "nested_verify_gpu.txt")
     import bench
     from tests.helpers import golden
     from zecale_amd import encoding as E
@@ -125,7 +233,11 @@ def main():
         pool.append(pr); pool_in.append(inp.reshape(1, 6))
     pool, pool_in = np.array(pool), np.array(pool_in)
     pool_in[-1] = pool_in[0]                                 # one invalid statement in the pool: proof 6 with proof 1's input
-    if args.checked:
+    if args.combined:
+        say("# nested Groth16 verification, dummy-application key (1 input): ONE combined check per batch vs the per-proof routes, all-valid batches,"
+            " scalars drawn from the OS, %d alternating runs" % CHECKED_ROUNDS)
+        ver, fallbacks, gate = combined_table(say, zkhip, vk, pool, pool_in, args.parent_lib)
+    elif args.checked:
         say("# nested Groth16 verification, dummy-application key (1 input): the checked route (every point's encoding, curve and order, every input's range,"
             " on the device) vs the unchecked one, %d alternating runs" % CHECKED_ROUNDS)
         ver, fallbacks = checked_table(say, zkhip, vk, pool, pool_in, args.parent_lib)
@@ -197,12 +309,19 @@ def stream_section(say, args, bench, zkhip, ver, pool, pool_in):
     for p_ in provers:
         p_.set_streaming(True)
         p_.prove(z, rs[0], rs[1])
+    if args.combined:
+        n_pool -= 1                                              # all-valid screening batches: the case --screen-combined is for
     idx = [i % n_pool for i in range(SCREEN_BATCH)]
     s_in, s_pr = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
-    s_want = [i != n_pool - 1 for i in idx]
+    s_want = [i != len(pool) - 1 for i in idx]
     screened = [0]
+
+    def screen_combined():                                       # GpuProver.screen_status with screen_combined
+        ok, st = ver.verify_all(s_in, s_pr, status=True)
+        return [True] * SCREEN_BATCH if ok else [int(c | m) == 0 for c, m in zip(*ver.verify_batch_checked(s_in, s_pr))]
     screen = {"unchecked": lambda: list(ver.verify_batch(s_in, s_pr)),
-              "checked": lambda: [int(c | m) == 0 for c, m in zip(*ver.verify_batch_checked(s_in, s_pr))]}
+              "checked": lambda: [int(c | m) == 0 for c, m in zip(*ver.verify_batch_checked(s_in, s_pr))],
+              "combined": screen_combined}
 
     def block(kind):
         counter, lock, stop = [args.stream], threading.Lock(), threading.Event()
@@ -232,11 +351,12 @@ def stream_section(say, args, bench, zkhip, ver, pool, pool_in):
         if sc:
             sc.join()
         return args.stream / dt, (screened[0] - n0) * SCREEN_BATCH / dt
-    kinds = (None, "unchecked", "checked") if args.checked else (None, "unchecked")
+    kinds = (None, "checked", "combined") if args.combined else (None, "unchecked", "checked") if args.checked else (None, "unchecked")
     rates = [(k, block(k)) for k in kinds + kinds]
     say("wrapping stream, %d proofs per block on %d prover instances, proofs/s (a NestedVerifier screens batches of %d back to back beside it where it runs):"
         % (args.stream, args.gpu_slots, SCREEN_BATCH))
-    name = {None: "without NestedVerifier", "unchecked": "with NestedVerifier", "checked": "with NestedVerifier, checked"}
+    name = {None: "without NestedVerifier", "unchecked": "with NestedVerifier", "checked": "with NestedVerifier, checked",
+            "combined": "with NestedVerifier, combined"}
     for k, (r, s_) in rates:
         say("  %-30s %8.1f%s" % (name[k], r, "   (%.0f nested verifications/s beside it)" % s_ if k else ""))
     mean = {k: sum(r for kk, (r, _) in rates if kk == k) / 2 for k in kinds}

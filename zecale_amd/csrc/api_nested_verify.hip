@@ -2,13 +2,17 @@
 // handle lives here: what it derives from its key (nested_key.hpp: the curve checks, the lines of -beta, -delta and the negated
 // generator, the doubling chains 2^j ABC_i), the host route of the test hook and the fallback of proofs the device does not decide;
 // and the host route of the CHECKED batches (nested_point_check_host.hpp: encoding, curve and order of a point, range of an input),
-// which also checks a checked handle's key before anything else reads it.
+// which also checks a checked handle's key before anything else reads it; and the host side of the COMBINED batches
+// (nested_combine_host.hpp: the sums, the shared finish behind both routes, the host route).
 #include <string.h>
+#include <chrono>
 #include <stdexcept>
 #include <string>
+#include <thread>
 
 #include "api_internal.hpp"
 #include "circuit/sections.hpp"
+#include "nested_combine_host.hpp"
 #include "nested_key.hpp"
 #include "nested_point_check_host.hpp"
 #include "pairing.cuh"               // verify_refusal: one definition for both checked routes
@@ -28,6 +32,12 @@ struct zkhip_nested_verifier {
   size_t last_fallbacks;
   std::vector<uint8_t> status;
   bool checked;                          // made by zkhip_nested_verifier_new_checked: the key's points passed the host point check
+  // combined batches (zkhip_nested_verifier_verify_all)
+  std::vector<zkhip::circuit::G2Lines<zkhip::circuit::NF>> key_lines;   // of -beta, -delta and the negated generator, for the host finish (made at the first call)
+  size_t last_degenerate;                // proofs of the last combined batch whose B has a degenerate line schedule
+  double finish_ms;                      // host time of the last combined batch behind the device's work
+  std::vector<uint64_t> chunk_products, chunk_sums;
+  std::vector<uint8_t> left_out;
 };
 
 namespace {
@@ -91,7 +101,7 @@ int nested_verifier_new(const uint64_t* nested_vk, size_t inputs_per_proof, bool
   NestedCtx* ctx = nullptr;
   const int rc = nested_ctx_new(&kd, &ctx, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
-  zkhip_nested_verifier* v = new zkhip_nested_verifier{ctx, cur_dev(), inputs_per_proof, {}, 0, {}, checked};
+  zkhip_nested_verifier* v = new zkhip_nested_verifier{ctx, cur_dev(), inputs_per_proof, {}, 0, {}, checked, {}, 0, 0, {}, {}, {}};
   v->vk.assign(nested_vk, nested_vk + 60 + 12 * (inputs_per_proof + 1));
   *out = v;
   return ZKHIP_OK;
@@ -120,6 +130,73 @@ int nested_verifier_run(zkhip_nested_verifier* v, const uint64_t* nested_inputs,
     out[i] = checked ? (uint8_t)(one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT) : (uint8_t)(one ? 1 : 0);
   }
   v->last_fallbacks = fallbacks;
+  return ZKHIP_OK;
+}
+
+namespace NC = zkhip::nested_combine;
+
+// the scalars of a combined batch: the caller's (none zero), or count x 16 bytes from the OS into `own`
+int nested_combine_scalars(const uint64_t* rho, size_t count, std::vector<uint64_t>& own, const uint64_t** out) {
+  if (rho) {
+    for (size_t i = 0; i < count; i++) if ((rho[i * 2] | rho[i * 2 + 1]) == 0) return fail(ZKHIP_ERR_ARG, "a combination scalar is zero");
+    *out = rho;
+    return ZKHIP_OK;
+  }
+  own.resize(count * 2);
+  if (!zkhip::host::draw_rho(own.data(), count)) return fail(ZKHIP_ERR_STATE, "getrandom failed: no scalars for the combination, and no weaker generator stands in");
+  *out = own.data();
+  return ZKHIP_OK;
+}
+
+unsigned host_route_threads() {
+  const unsigned hw = std::thread::hardware_concurrency();
+  return hw > 16 ? 16 : hw;
+}
+
+// the handle's key in the finish's form; its lines are made at the first combined batch (the key passed prepare_key: none is degenerate)
+int handle_combine_key(zkhip_nested_verifier* v, NC::CombineKey* key) {
+  if (v->key_lines.empty() && !NC::key_lines(v->vk.data() + 12, v->vk.data() + 36, &v->key_lines)) return fail(ZKHIP_ERR_STATE, "the key's line schedules are degenerate");
+  key->alpha = v->vk.data();
+  key->abc = v->vk.data() + 60;
+  key->n_inputs = v->n_inputs;
+  key->lines = v->key_lines;
+  return ZKHIP_OK;
+}
+
+// The combined check on the device route: the reduced value, the refusal bytes (checked handle, or null) and the proofs left out.
+// The device gives per chunk the unreduced product of the per-proof pairs and the sum of the rho_i C_i; the host multiplies and adds
+// the chunks' results, forms the sums in the scalar field over the proofs that are not left out, and finishes (combined_value).
+int nested_verify_all_device(zkhip_nested_verifier* v, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                             uint8_t* refusal, uint64_t* value) {
+  NC::CombineKey key;
+  int rc = handle_combine_key(v, &key);
+  if (rc != ZKHIP_OK) return rc;
+  const size_t chunks = nested_verify_all_chunks(count);
+  v->chunk_products.resize(chunks * 72);
+  v->chunk_sums.resize(chunks * 12);
+  v->left_out.resize(count);
+  if ((rc = nested_verify_all(v->ctx, inputs, proofs, count, rho, checked, v->chunk_products.data(), v->chunk_sums.data(), v->left_out.data(), refusal,
+                              t_err, sizeof t_err)) != ZKHIP_OK)
+    return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  NC::CombineSums sums(v->n_inputs);
+  size_t degenerate = 0;
+  for (size_t i = 0; i < count; i++) {
+    if (!v->left_out[i]) sums.add(rho + i * 2, inputs + i * v->n_inputs * 6);
+    else if (!(v->left_out[i] & NESTED_OFF_CURVE)) degenerate++;
+  }
+  zkhip::circuit::Fq12<zkhip::circuit::NF> product = zkhip::circuit::Fq12<zkhip::circuit::NF>::one();
+  NC::NestedJac<HFr> s_c = NC::NestedJac<HFr>::infinity();
+  for (size_t k = 0; k < chunks; k++) {
+    product = product * NC::fq12_from_limbs(&v->chunk_products[k * 72]);
+    const uint64_t* p = &v->chunk_sums[k * 12];
+    uint64_t nz = 0;
+    for (int t = 0; t < 12; t++) nz |= p[t];
+    if (nz) s_c = s_c.add_affine(HFr::from_limbs(p), HFr::from_limbs(p + 6));
+  }
+  NC::fq12_to_limbs(NC::combined_value(key, sums, NC::to_affine(s_c), product), value);
+  v->last_degenerate = degenerate;
+  v->finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return ZKHIP_OK;
 }
 
@@ -187,6 +264,102 @@ int zkhip_nested_verifier_verify_batch_checked(zkhip_nested_verifier* v, const u
 int zkhip_nested_verifier_last_fallbacks(const zkhip_nested_verifier* v, size_t* out) {
   if (!v || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
   *out = v->last_fallbacks;
+  return ZKHIP_OK;
+}
+
+// ---- combined batches: ONE random-combination check for a whole batch
+int zkhip_nested_verifier_verify_all(zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs, size_t count,
+                                     const uint64_t* rho, int* all_ok, uint8_t* status) {
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  if (!all_ok) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (status && !v->checked) return fail(ZKHIP_ERR_STATE, "a per-proof status needs a handle of zkhip_nested_verifier_new_checked");
+  v->last_degenerate = 0;
+  v->finish_ms = 0;
+  if (count == 0) { *all_ok = 1; return ZKHIP_OK; }
+  if (!nested_proofs || (v->n_inputs && !nested_inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  int rc = nested_combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  BIND(v);
+  uint64_t value[72];
+  try {
+    if ((rc = nested_verify_all_device(v, nested_inputs, nested_proofs, count, rho, status != nullptr, status, value)) != ZKHIP_OK) return rc;
+  } catch (const std::exception& e) {
+    return fail(ZKHIP_ERR_STATE, e.what());
+  }
+  bool ok = NC::gt_is_one(value);
+  for (size_t i = 0; ok && i < count; i++) ok = v->left_out[i] == 0;      // a proof that is left out of the product fails the batch
+  *all_ok = ok ? 1 : 0;
+  return ZKHIP_OK;
+}
+
+// the combined check on the host alone (nested_combine_host.hpp): the route zkhip_nested_verifier_verify_all is pinned on
+int zkhip_bls12_377_groth16_verify_all(const uint64_t vk_alpha_g1[12], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                                       size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, int* all_ok) {
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc || !all_ok) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (count == 0) { *all_ok = 1; return ZKHIP_OK; }
+  if (!proofs || (n_inputs && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  const int rc = nested_combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  try {
+    // well-formedness first, as zkhip_bls12_377_groth16_verify: a key point off its curve fails the batch before any pairing arithmetic
+    bool wf = g1_on_curve(C::g1_from<NF>(vk_alpha_g1, false)) && g2_on_curve(C::g2_from<NF>(vk_beta_g2, false)) && g2_on_curve(C::g2_from<NF>(vk_delta_g2, false));
+    for (size_t i = 0; i <= n_inputs && wf; i++) wf = g1_on_curve(C::g1_from<NF>(vk_abc + i * 12, false));
+    NC::CombineKey key = {vk_alpha_g1, vk_abc, n_inputs, {}};
+    if (!wf || !NC::key_lines(vk_beta_g2, vk_delta_g2, &key.lines)) { *all_ok = 0; return ZKHIP_OK; }
+    std::vector<uint8_t> left_out(count);
+    uint64_t value[72];
+    NC::verify_all_host(key, inputs, proofs, count, rho, nullptr, host_route_threads(), left_out.data(), value);
+    bool ok = NC::gt_is_one(value);
+    for (size_t i = 0; ok && i < count; i++) ok = left_out[i] == 0;      // a point off its curve, a degenerate line schedule
+    *all_ok = ok ? 1 : 0;
+  } catch (const std::exception& e) {
+    return fail(ZKHIP_ERR_STATE, e.what());
+  }
+  return ZKHIP_OK;
+}
+
+int zkhip_nested_verifier_last_degenerate(const zkhip_nested_verifier* v, size_t* out) {
+  if (!v || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *out = v->last_degenerate;
+  return ZKHIP_OK;
+}
+
+int zkhip_internal_nested_verify_all_value(int route, zkhip_nested_verifier* v, const uint64_t* nested_inputs, const uint64_t* nested_proofs,
+                                           size_t count, const uint64_t* rho, uint64_t out[72]) {
+  if (route != 0 && route != 1) return fail(ZKHIP_ERR_ARG, "route 0 (host) or 1 (GPU)");
+  if (!v || !out || (count && (!nested_proofs || !rho || (v->n_inputs && !nested_inputs)))) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  int rc = nested_combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  try {
+    if (route == 1 && count) {
+      BIND(v);
+      return nested_verify_all_device(v, nested_inputs, nested_proofs, count, rho, v->checked, nullptr, out);
+    }
+    NC::CombineKey key;
+    if ((rc = handle_combine_key(v, &key)) != ZKHIP_OK) return rc;
+    std::vector<uint8_t> refused, left_out(count);
+    if (v->checked) {                                // the checked route's refusals, on the host: such a proof is left out
+      namespace K = zkhip::nested_key;
+      refused.resize(count);
+      for (size_t i = 0; i < count; i++) {
+        const uint64_t* pr = nested_proofs + i * 48;
+        const uint8_t e[4] = {(uint8_t)K::point_check_host(pr, false), (uint8_t)K::point_check_host(pr + 12, true), (uint8_t)K::point_check_host(pr + 36, false),
+                              (uint8_t)K::inputs_check_host(nested_inputs + i * v->n_inputs * 6, v->n_inputs)};
+        refused[i] = verify_refusal(e);
+      }
+    }
+    NC::verify_all_host(key, nested_inputs, nested_proofs, count, rho, v->checked ? refused.data() : nullptr, host_route_threads(), left_out.data(), out);
+  } catch (const std::exception& e) {
+    return fail(ZKHIP_ERR_STATE, e.what());
+  }
+  return ZKHIP_OK;
+}
+int zkhip_internal_nested_verify_all_finish_ms(const zkhip_nested_verifier* v, double* ms) {
+  if (!v || !ms) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *ms = v->finish_ms;
   return ZKHIP_OK;
 }
 

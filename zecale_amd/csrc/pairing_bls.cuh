@@ -12,7 +12,8 @@
 // the affine chain of g2_precompute) or from the host (the key's -beta, -delta and the negated generator).
 // Every body is a function of (lane index, operand arrays); none waits, spins or branches on data other than by selects - except
 // the one-lane-per-point bodies (g2_lines_lane, nested_acc_lane, the curve checks, the checked route's nested_point_check and
-// nested_inputs_check at the end of this file), which run in kernels without barriers.
+// nested_inputs_check, the combined batches' nested_rho_scale and nested_g1_strip_sum at the end of this file), which run in kernels
+// without barriers.
 //
 // LAZY BOUNDS ([k]: value < k p, limbs normalised).  fp29.cuh's contract: a b + c d < 2^10 R p; here R / p > 2^29, so any sum of
 // products of operands [k1] x [k2] with sum k1 k2 < 2^39 is inside it and its result is < p (1 + 2^-10): written [1+].
@@ -413,6 +414,129 @@ ZK_HD ZK_INL int nested_inputs_check(const uint64_t* inputs, size_t n) {
     bad = bad || borrow == 0;
   }
   return bad ? ZKHIP_VERIFY_ENCODING : ZKHIP_VERIFY_ACCEPT;
+}
+
+// ---- combined batches: prod_i f(rho_i A_i, B_i) and S_C = sum_i rho_i C_i for ONE random-combination check of a whole batch
+// (nested_combine_host.hpp states the equation).  k_nested_rho_scale runs nested_rho_scale on one lane per (proof, A or C), the existing
+// Miller loop runs with one pair, and two reduction trees (k_nested_gt_product on sixteen-lane groups, k_nested_g1_sum on single lanes)
+// take NESTED_STRIP values per strip and are relaunched on their partial results until one value is left.
+//
+// NESTED_STRIP = 8: a launch's dependent chain is seven Fq12 products (or seven point additions) - short against the 132 products
+// of the Miller loop in front - and a chunk of 8,192 values is down to one in five launches; a strip of 4 would need seven launches for
+// three dependent products each, a strip of 16 leaves 512 groups (64 workgroups) on the first and widest level, a quarter of the
+// device's compute units, for a chain twice as long.  The integer rules are constexpr so that the host driver and the tests read them.
+constexpr int NESTED_STRIP = 8;
+constexpr int NESTED_RHO_BITS = 128;        // bit length of a combination scalar
+// values one level of a reduction tree writes for the n it reads
+constexpr size_t nested_strips(size_t n) { return (n + NESTED_STRIP - 1) / NESTED_STRIP; }
+// launches of a reduction tree over n >= 1 values: level k reads n_k values (n_0 = n) and writes n_{k+1} = nested_strips(n_k); the last
+// level is the one that is left with one strip
+constexpr int nested_tree_levels(size_t n) {
+  int levels = 1;
+  for (; nested_strips(n) > 1; n = nested_strips(n)) levels++;
+  return levels;
+}
+
+template <class E> ZK_HD ZK_INL NestedXYZZ<E> nested_xyzz_infinity() {
+  NestedXYZZ<E> r;
+  nf_set(r.X, false); nf_set(r.Y, false); nf_set(r.ZZ, false); nf_set(r.ZZZ, false);
+  return r;
+}
+
+// rho (x, y) by double-and-add over the 128 bits of rho (two 64-bit words, little endian), most significant first, a fixed trip count;
+// the scalar is shifted through its four 32-bit words, so no word is picked by a run-time index.  x, y [2], a point of the nested G1's
+// curve (the formulas never use b).  A point of order 2 - (-1, 0) - goes to infinity in its first doubling behind a set bit and comes
+// back with the next set bit: the result is infinity for an even rho and the point for an odd one.
+// Bounds: those of nested_point_has_order_r - acc leaves the doubling with X [6], Y [4] and the addition with X [10], Y [4]: always
+// within the X [10], Y [4] both formulas take.
+ZK_HD ZK_INL NestedXYZZ<Fr> nested_rho_scale(const Fr& x, const Fr& y, const uint64_t* rho) {
+  uint32_t w[4] = {(uint32_t)rho[0], (uint32_t)(rho[0] >> 32), (uint32_t)rho[1], (uint32_t)(rho[1] >> 32)};
+  NestedXYZZ<Fr> acc = nested_xyzz_infinity<Fr>();
+#pragma unroll 1
+  for (int b = 0; b < NESTED_RHO_BITS; b++) {
+    acc = nested_xyzz_dbl(acc);                              // X [6], Y [4]
+    const bool bit = (w[3] >> 31) != 0;
+#pragma unroll
+    for (int j = 3; j >= 0; j--) w[j] = (w[j] << 1) | (j ? w[j - 1] >> 31 : 0u);
+    if (bit) nested_xyzz_madd(acc, x, y);                    // X [10], Y [4]
+  }
+  return acc;
+}
+
+// p (X [10], Y [4]; ZZ, ZZZ [1+], not infinity) -> affine (x, y) in device form [1+]: one inversion, as nested_acc_lane ends.
+// ZZ ZZZ is reduced to [2] in front of the inversion; every other product has operands [10] x [1+] at most.
+ZK_HD ZK_INL void nested_xyzz_to_affine(const NestedXYZZ<Fr>& p, Fr* out) {
+  const Fr zi = fp_inv<FrParams>(fr_red(fp_mul(p.ZZ, p.ZZZ)));   // 1 / (ZZ ZZZ), [2]
+  out[0] = fp_mul(p.X, fp_mul(zi, p.ZZZ));                       // X / ZZ
+  out[1] = fp_mul(p.Y, fp_mul(zi, p.ZZ));                        // Y / ZZZ
+}
+
+// acc += q, both in XYZZ (add-2008-s), COMPLETE: infinity on either side is neutral, equal summands double, P and -P give infinity.
+// acc and q: X [10], Y [4]; ZZ, ZZZ [1+] or exact zeros - what nested_rho_scale and this function leave.  The two comparisons are made
+// on PP and RR, results of products ([1+]; a square is zero exactly when its root is), never on P or R [4].
+template <class E> ZK_HD ZK_INL void nested_xyzz_add(NestedXYZZ<E>& acc, const NestedXYZZ<E>& q) {
+  if (nf_is_zero_2p(q.ZZ)) return;
+  if (nf_is_zero_2p(acc.ZZ)) { acc = q; return; }
+  const E U1 = nf_mul(acc.X, q.ZZ);                       // [1+]   ([10] x [1+])
+  const E U2 = nf_mul(q.X, acc.ZZ);                       // [1+]
+  const E S1 = nf_mul(acc.Y, q.ZZZ);                      // [1+]   ([4] x [1+])
+  const E S2 = nf_mul(q.Y, acc.ZZZ);                      // [1+]
+  const E P = nf_sub<2>(U2, U1);                          // [4]    (U1 is [1+] <= 2)
+  const E R = nf_sub<2>(S2, S1);                          // [4]
+  const E PP = nf_mul(P, P);                              // [1+]
+  const E RR = nf_mul(R, R);                              // [1+]
+  if (nf_is_zero_2p(PP)) {                                // same x: q = +-acc
+    if (nf_is_zero_2p(RR)) acc = nested_xyzz_dbl(acc);    // X [6], Y [4]
+    else acc = nested_xyzz_infinity<E>();
+    return;
+  }
+  const E PPP = nf_mul(P, PP);                            // [1+]
+  const E Q = nf_mul(U1, PP);                             // [1+]
+  const E X3 = nf_sub<4>(nf_sub<4>(RR, PPP), nf_add(Q, Q));   // [2 + 4 + 4 = 10]
+  const E t = nf_sub<16>(Q, X3);                          // [18]   (X3 is [10] <= 16)
+  const E Y3a = nf_mul(t, R);                             // [1+]   (the [18] factor first: the second operand stays <= [25])
+  const E Y3b = nf_mul(S1, PPP);                          // [1+]
+  acc.X = X3;
+  acc.Y = nf_sub<2>(Y3a, Y3b);                            // [4]
+  acc.ZZ = nf_mul(nf_mul(acc.ZZ, q.ZZ), PP);              // [1+]
+  acc.ZZZ = nf_mul(nf_mul(acc.ZZZ, q.ZZZ), PPP);          // [1+]
+}
+
+// coefficient k of value i of the strip that starts at `first`: in[first + i] while that lies inside the `count` values and `skip`
+// (null, or one byte per value: a proof that is left out) does not flag it, else of one - a select on the clamped index: nothing past
+// the arrays is read.  in: twelve coefficients [8] per value; one is [1].
+ZK_HD ZK_INL Fr nested_gt_strip_operand(int k, const Fr* in, size_t first, int i, size_t count, const uint8_t* skip) {
+  const size_t idx = first + (size_t)i;
+  const bool inside = idx < count;
+  const size_t at = inside ? idx : count - 1;
+  const bool take = inside && !(skip && skip[at]);
+  return fr_select(take, in[at * 12 + k], k == 0 ? fp_one<FrParams>() : fp_zero<FrParams>());
+}
+
+// the sum of the strip that starts at `first` (< count), at most NESTED_STRIP values.  nested_xyzz_add keeps X [10], Y [4] for summands
+// within the same bounds, which nested_rho_scale's results and earlier sums are.
+ZK_HD ZK_INL NestedXYZZ<Fr> nested_g1_strip_sum(const NestedXYZZ<Fr>* in, size_t first, size_t count) {
+  NestedXYZZ<Fr> acc = in[first];
+#pragma unroll 1
+  for (int i = 1; i < NESTED_STRIP; i++) {
+    if (first + (size_t)i >= count) break;
+    const NestedXYZZ<Fr> t = in[first + (size_t)i];
+    nested_xyzz_add(acc, t);                              // X [10], Y [4]
+  }
+  return acc;
+}
+
+// p as affine ABI limbs (x | y), all zero for the point at infinity (the nested FORMAT has no such point: this is the sum tree's own
+// result, read by the host finish alone).  fp_to_abi reduces the [1+] coordinates.
+ZK_HD ZK_INL void nested_xyzz_to_affine_abi(const NestedXYZZ<Fr>& p, uint64_t* o) {
+  if (nf_is_zero_2p(p.ZZ)) {
+    for (int k = 0; k < 12; k++) o[k] = 0;
+    return;
+  }
+  Fr xy[2];
+  nested_xyzz_to_affine(p, xy);
+  fp_to_abi<FrParams>(xy[0], o);
+  fp_to_abi<FrParams>(xy[1], o + 6);
 }
 
 }  // namespace zkhip

@@ -40,6 +40,16 @@ int nested_products(NestedCtx* c, const uint64_t* g1, const uint64_t* g2, int pa
 // it names a refusal status[i] is 0, where status[i] has NESTED_DEGENERATE ok[i] is undecided as before.
 int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, bool checked, uint8_t* ok, uint8_t* status,
                         char* errbuf, size_t errlen);
+// ONE random-combination check of the whole batch, the device's share (nested_combine_host.hpp states the equation and holds the host
+// finish).  rho: count x 2 words, none zero.  Per chunk of NESTED_CHUNK proofs (nested_verify_all_chunks of them): chunk_products gets
+// 72 ABI limbs, the UNREDUCED prod_i f(rho_i A_i, B_i) over the chunk's proofs that are not left out, and chunk_sums 12 ABI limbs, the
+// affine sum of their rho_i C_i (all zero: infinity).  left_out[i] (count bytes): 0, or the status bits of a proof that is left out -
+// NESTED_OFF_CURVE (a point off its curve; on the checked route a refused proof) or NESTED_DEGENERATE (the line schedule of its B).
+// A proof with rho_i A_i = O contributes one to the product and is NOT left out.  checked: k_nested_point_check runs in front and
+// refusal (count bytes, or null) gets the refusal byte of zkhip.h, 0 for a proof nothing refuses.
+int nested_verify_all(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                      uint64_t* chunk_products, uint64_t* chunk_sums, uint8_t* left_out, uint8_t* refusal, char* errbuf, size_t errlen);
+size_t nested_verify_all_chunks(size_t count);
 // op 0: a b, 1: a^2, 2: a (b0 + b1 w + b3 w^3 + b7 w^7 + b9 w^9) through the lane bodies of pairing_bls.cuh; a, b, out: n x 72 ABI limbs
 int nested_fq12_selftest(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char* errbuf, size_t errlen);
 

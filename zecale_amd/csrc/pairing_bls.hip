@@ -192,6 +192,79 @@ __global__ void __launch_bounds__(NESTED_BLOCK) k_nested_final_exp(const Fr* __r
   if (live && k < 12) fp_to_abi<FrParams>(sR[g][0][k], gt + slot * 72 + k * 6);       // [8] -> canonical
 }
 
+// ---- combined batches (nested_combine_host.hpp states the equation): rho_i A_i and rho_i C_i, then two reduction trees.
+// One lane per (proof, element): lanes 0 .. count - 1 scale A, the next count scale C, so a wave does one kind of work.  A's lane writes
+// rho A affine, in device form, over A in the proof's first G1 slot (the pair's point in the Miller loop) and the proof's skip byte:
+// set when the prep left a status (off its curve or refused, a degenerate line schedule) or when rho A is the point at infinity - the
+// pair then contributes one, the slot keeps A.  C's lane keeps XYZZ for k_nested_g1_sum: infinity for a proof with a status.
+__global__ void __launch_bounds__(64) k_nested_rho_scale(Fr* __restrict__ g1 /* count x 3 x 2 */, const uint64_t* __restrict__ rho, size_t count,
+                                                         const uint8_t* __restrict__ status, NestedXYZZ<Fr>* __restrict__ rc,
+                                                         uint8_t* __restrict__ skip) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * count) return;
+  const bool is_c = t >= count;
+  const size_t j = is_c ? t - count : t;
+  if (status[j] != 0) {
+    if (is_c) rc[j] = nested_xyzz_infinity<Fr>();
+    else skip[j] = 1;
+    return;
+  }
+  Fr* pt = g1 + j * 6 + (is_c ? 4 : 0);
+  const NestedXYZZ<Fr> v = nested_rho_scale(pt[0], pt[1], rho + j * 2);
+  if (is_c) { rc[j] = v; return; }
+  const bool inf = nf_is_zero_2p(v.ZZ);
+  skip[j] = inf ? 1 : 0;
+  if (!inf) nested_xyzz_to_affine(v, pt);
+}
+
+// `count` unreduced Miller values -> ceil(count / NESTED_STRIP) products.  A group of sixteen lanes owns a strip: twelve coefficient
+// lanes, the running product and the next operand twice in LDS (a product reads one copy of each and writes the other), ONE barrier per
+// product - the cut of k_nested_miller.  Groups past the last strip recompute it and store nothing, so every thread reaches every
+// barrier; a strip that runs past the end of the values, or a value that `skip` flags (first level only), multiplies by one.  abi (the
+// launch that is left with one strip): the product as ABI limbs.  in and out are different buffers.
+__global__ void __launch_bounds__(NESTED_BLOCK) k_nested_gt_product(const Fr* __restrict__ in, size_t count, const uint8_t* __restrict__ skip,
+                                                                    Fr* __restrict__ out, uint64_t* __restrict__ abi) {
+  __shared__ Fr sF[NESTED_WG][2][12];
+  __shared__ Fr sB[NESTED_WG][2][12];
+  const int g = threadIdx.x / NESTED_GROUP, k = threadIdx.x % NESTED_GROUP;
+  const size_t strips = nested_strips(count);
+  size_t strip = (size_t)blockIdx.x * NESTED_WG + g;
+  const bool live = strip < strips;
+  if (!live) strip = strips - 1;
+  const size_t first = strip * NESTED_STRIP;
+  if (k < 12) {
+    sF[g][0][k] = nested_gt_strip_operand(k, in, first, 0, count, skip);
+    sB[g][0][k] = nested_gt_strip_operand(k, in, first, 1, count, skip);
+  }
+  __syncthreads();
+  int cur = 0;
+#pragma unroll 1
+  for (int i = 1; i < NESTED_STRIP; i++) {
+    if (k < 12) {
+      sF[g][cur ^ 1][k] = fq12_mul_coeff(k, sF[g][cur], sB[g][cur]);        // [8] x [8] -> [8]
+      if (i + 1 < NESTED_STRIP) sB[g][cur ^ 1][k] = nested_gt_strip_operand(k, in, first, i + 1, count, skip);
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (live && k < 12) {
+    if (abi) fp_to_abi<FrParams>(sF[g][cur][k], abi + k * 6);               // [8] -> canonical
+    else out[strip * 12 + k] = sF[g][cur][k];
+  }
+}
+
+// `count` XYZZ values -> ceil(count / NESTED_STRIP) sums, one lane per strip (pairing_bls.cuh nested_g1_strip_sum).  abi (the launch
+// that is left with one strip): the sum as affine ABI limbs, all zero for infinity.  in and out are different buffers.
+__global__ void __launch_bounds__(64) k_nested_g1_sum(const NestedXYZZ<Fr>* __restrict__ in, size_t count, NestedXYZZ<Fr>* __restrict__ out,
+                                                      uint64_t* __restrict__ abi) {
+  const size_t strips = nested_strips(count);
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= strips) return;
+  const NestedXYZZ<Fr> acc = nested_g1_strip_sum(in, s * NESTED_STRIP, count);
+  if (abi) nested_xyzz_to_affine_abi(acc, abi);
+  else out[s] = acc;
+}
+
 // ---- the lane bodies on operands given as ABI limbs (zkhip_internal_fq12_selftest)
 __global__ void __launch_bounds__(NESTED_BLOCK) k_fq12_selftest(int op, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, size_t n,
                                                                 uint64_t* __restrict__ out) {
@@ -233,6 +306,11 @@ struct NestedCtx {
   DeviceBuffer<uint8_t> d_codes;              // checked batches: four codes per proof (k_nested_point_check), read as one word per proof behind it
   std::vector<uint64_t> h_gt;
   std::vector<uint8_t> h_status, h_codes;
+  // combined batches (nctx_reserve_comb: reserved only when nested_verify_all runs)
+  DeviceBuffer<uint64_t> d_rho, d_res;        // the chunk's scalars; its product (72 limbs) | its sum (12 limbs)
+  DeviceBuffer<NestedXYZZ<Fr>> d_rc, d_rc2;   // rho C, and the other buffer of the sum tree
+  DeviceBuffer<Fr> d_f2;                      // the other buffer of the product tree (d_f is the first)
+  DeviceBuffer<uint8_t> d_skip;               // one byte per proof: its pair contributes one
 };
 
 // work space for `count` products of four pairs (a proof is one): 4 G2 points of 24 limbs or a proof's 48; 16 inputs of 6 limbs at most;
@@ -246,6 +324,17 @@ static int nctx_reserve(NestedCtx* c, size_t count, bool checked, char* errbuf, 
   ZK_HIP_TRY("nested pairing", c->d_lines.reserve(count * 4 * NESTED_LINES));
   ZK_HIP_TRY("nested pairing", c->d_status.reserve(count * 4));
   if (checked) ZK_HIP_TRY("nested pairing", c->d_codes.reserve(count * 4));
+  return ZKHIP_OK;
+}
+
+// the combined route's extra work space for a chunk of `count` proofs: scalars, scaled points and the trees' second buffers
+static int nctx_reserve_comb(NestedCtx* c, size_t count, char* errbuf, size_t errlen) {
+  ZK_HIP_TRY("nested pairing", c->d_rho.reserve(count * 2));
+  ZK_HIP_TRY("nested pairing", c->d_res.reserve(72 + 12));
+  ZK_HIP_TRY("nested pairing", c->d_rc.reserve(count));
+  ZK_HIP_TRY("nested pairing", c->d_rc2.reserve(nested_strips(count)));
+  ZK_HIP_TRY("nested pairing", c->d_f2.reserve(nested_strips(count) * 12));
+  ZK_HIP_TRY("nested pairing", c->d_skip.reserve(count));
   return ZKHIP_OK;
 }
 
@@ -381,6 +470,83 @@ int nested_verify_batch(NestedCtx* c, const uint64_t* inputs, const uint64_t* pr
       status[lo + j] = refused ? 0 : s;
       ok[lo + j] = refused ? refused : (uint8_t)(is_one ? ZKHIP_VERIFY_ACCEPT : ZKHIP_VERIFY_REJECT);
     }
+    return ZKHIP_OK;
+  });
+}
+
+size_t nested_verify_all_chunks(size_t count) { return (count + NESTED_CHUNK - 1) / NESTED_CHUNK; }
+
+// One random-combination check of the whole batch, the device's share.  Per chunk: the staging and the prep kernel of the per-proof
+// route (k_nested_point_check in front when checked), k_nested_rho_scale, the existing Miller loop with ONE pair per proof on
+// (rho_i A_i, B_i), and the two trees, relaunched on their partial results - two buffers taking turns - until one value is left.  The
+// input accumulator (k_nested_acc, the key's chains) is not touched.  The host finish is the caller's (nested_combine_host.hpp).
+int nested_verify_all(NestedCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                      uint64_t* chunk_products, uint64_t* chunk_sums, uint8_t* left_out, uint8_t* refusal, char* errbuf, size_t errlen) {
+  if (!c->has_key) {
+    if (errbuf) snprintf(errbuf, errlen, "nested pairing: a context without a key");
+    return ZKHIP_ERR_STATE;
+  }
+  const size_t ni = c->n_inputs;
+  const NestedLine* key_lines = reinterpret_cast<const NestedLine*>(c->d_fr + NK_LINES);
+  return for_each_chunk(count, NESTED_CHUNK, [&](size_t lo, size_t m) -> int {
+    int rc = nctx_reserve(c, m, checked, errbuf, errlen);
+    if (rc == ZKHIP_OK) rc = nctx_reserve_comb(c, m, errbuf, errlen);
+    if (rc != ZKHIP_OK) return rc;
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_in1, proofs + lo * 48, m * 48 * 8, hipMemcpyHostToDevice, c->st));
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_rho, rho + lo * 2, m * 16, hipMemcpyHostToDevice, c->st));
+    if (checked) {
+      if (ni) ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->d_in2, inputs + lo * ni * 6, m * ni * 48, hipMemcpyHostToDevice, c->st));
+      hipLaunchKernelGGL(k_nested_point_check, dim3(blocks_for(4 * m, 64)), dim3(64), 0, c->st, c->d_in1.get(), c->d_in2.get(), ni, m, c->d_fr.get(),
+                         c->d_codes.get());
+      hipLaunchKernelGGL(k_nested_prep_checked, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1.get(), m,
+                         reinterpret_cast<const uint32_t*>(c->d_codes.get()), c->d_fr + NK_ALPHA, c->d_g1.get(), c->d_lines.get(), c->d_status.get());
+    } else {
+      hipLaunchKernelGGL(k_nested_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_in1.get(), m, c->d_fr.get(), c->d_g1.get(), c->d_lines.get(),
+                         c->d_status.get());
+    }
+    hipLaunchKernelGGL(k_nested_rho_scale, dim3(blocks_for(2 * m, 64)), dim3(64), 0, c->st, c->d_g1.get(), c->d_rho.get(), m, c->d_status.get(),
+                       c->d_rc.get(), c->d_skip.get());
+    NestedMillerArgs args = {};
+    args.g1[0] = c->d_g1; args.g1_stride[0] = 6; args.lines[0] = c->d_lines; args.line_stride[0] = NESTED_LINES;              // f(rho A, B)
+    args.standin = key_lines;
+    args.status = c->d_status;
+    hipLaunchKernelGGL(k_nested_miller, dim3(blocks_for(m, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, args, 1, m, c->d_f.get());
+    {
+      const Fr* in = c->d_f;
+      Fr* out = c->d_f2;
+      const uint8_t* skip = c->d_skip;
+      for (size_t n = m;;) {
+        const size_t strips = nested_strips(n);
+        hipLaunchKernelGGL(k_nested_gt_product, dim3(blocks_for(strips, NESTED_WG)), dim3(NESTED_BLOCK), 0, c->st, in, n, skip, out,
+                           strips == 1 ? c->d_res.get() : nullptr);
+        if (strips == 1) break;
+        n = strips;
+        skip = nullptr;
+        Fr* t = const_cast<Fr*>(in); in = out; out = t;       // the values of the level before are dead: their buffer takes the next level
+      }
+    }
+    {
+      const NestedXYZZ<Fr>* in = c->d_rc;
+      NestedXYZZ<Fr>* out = c->d_rc2;
+      for (size_t n = m;;) {
+        const size_t strips = nested_strips(n);
+        hipLaunchKernelGGL(k_nested_g1_sum, dim3(blocks_for(strips, 64)), dim3(64), 0, c->st, in, n, out, strips == 1 ? c->d_res + 72 : nullptr);
+        if (strips == 1) break;
+        n = strips;
+        NestedXYZZ<Fr>* t = const_cast<NestedXYZZ<Fr>*>(in); in = out; out = t;
+      }
+    }
+    ZK_HIP_TRY("nested pairing", hipGetLastError());
+    const size_t chunk = lo / NESTED_CHUNK;
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(chunk_products + chunk * 72, c->d_res, 72 * 8, hipMemcpyDeviceToHost, c->st));
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(chunk_sums + chunk * 12, c->d_res + 72, 12 * 8, hipMemcpyDeviceToHost, c->st));
+    ZK_HIP_TRY("nested pairing", hipMemcpyAsync(left_out + lo, c->d_status, m, hipMemcpyDeviceToHost, c->st));
+    if (checked) {
+      c->h_codes.resize(m * 4);
+      ZK_HIP_TRY("nested pairing", hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));
+    }
+    ZK_HIP_TRY("nested pairing", hipStreamSynchronize(c->st));
+    if (checked && refusal) for (size_t j = 0; j < m; j++) refusal[lo + j] = verify_refusal(&c->h_codes[j * 4]);
     return ZKHIP_OK;
   });
 }

@@ -8,15 +8,14 @@
 // Miller lines are scaled by Fq factors and vertical lines dropped (both die in the final exponentiation);
 // the four Miller loops share one accumulator (one Fq6 squaring per bit for the whole product).
 #pragma once
-#include <errno.h>
 #include <string.h>
-#include <sys/random.h>
 
 #include <array>
 #include <thread>
 #include <vector>
 
 #include "../../include/zkhip.h"
+#include "combine_scalars.hpp"
 #include "host_field.hpp"
 
 namespace zkhip {
@@ -170,21 +169,7 @@ struct CombineSums {
   }
 };
 
-// count x 16 bytes from the OS, each scalar redrawn while zero.  false: getrandom failed - there is no weaker generator behind it.
-inline bool draw_rho(uint64_t* rho, size_t count) {
-  for (size_t i = 0; i < count; i++) {
-    do {
-      size_t got = 0;
-      while (got < 16) {
-        const ssize_t n = getrandom(reinterpret_cast<char*>(rho + i * 2) + got, 16 - got, 0);
-        if (n < 0 && errno == EINTR) continue;
-        if (n <= 0) return false;
-        got += (size_t)n;
-      }
-    } while ((rho[i * 2] | rho[i * 2 + 1]) == 0);
-  }
-  return true;
-}
+// (draw_rho, the scalars of a combined batch, is combine_scalars.hpp's: the nested verifier's combined route draws them too)
 
 inline Fq6 fq6_from_limbs(const uint64_t* p) { Fq6 r; for (int k = 0; k < 6; k++) r.c[k] = HFq::from_limbs(p + k * 12); return r; }
 inline void fq6_to_limbs(const Fq6& f, uint64_t* p) { for (int k = 0; k < 6; k++) f.c[k].to_limbs(p + k * 12); }

@@ -271,10 +271,14 @@ class GpuProver:
     snark_name = "GROTH16"
 
     def __init__(self, keypair_file=None, device=0, gpu_slots=32, witness_workers=10, gpu_witness=False, devices=None, hybrid_witness=False,
-                 screen_nested=False):
+                 screen_nested=False, screen_combined=False):
         """screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier, the CHECKED route: every point's
         encoding, curve and order, every input's range) before a batch is popped, so that an invalid or malformed one costs no slot of
         a wrapping proof (`screen_status` / `screen`; off: the service never asks).
+        screen_combined (meaningful only with screen_nested; default off): `screen_status` first asks the checked handle ONE
+        random-combination check for the whole pool (NestedVerifier.verify_all with status) and runs the checked per-proof batch only
+        when that fails - pools are almost always all-valid.  The combined check answers the group law's statement (see
+        NestedVerifier.verify_all); DESIGN 9e says from which pool size it pays.
         devices: the GPUs of the node this ONE server process drives (the reference server is one process that owns its prover:
         aggregator_server.cpp:106-118, 390-416) - a resident copy of the key and a streaming pipeline on each, behind a dispatcher
         (zkhip_dispatcher_*); an index may repeat (two contexts on one GPU).  None / one entry: that GPU alone (`device`)."""
@@ -284,6 +288,7 @@ class GpuProver:
         device = devices[0]
         self.devices = devices
         self.screen_nested = bool(screen_nested)
+        self.screen_combined = bool(screen_combined)
         self._screens, self._screen_mu = {}, threading.Lock()      # nested key bytes -> (NestedVerifier or None, its lock)
         self.gpu_slots = gpu_slots * len(devices)        # (the handler pool is as deep as the node has proofs in flight)
         zkhip.init(device)
@@ -359,6 +364,8 @@ class GpuProver:
         if v is None:
             return [int(self.zk.bls12_377_groth16_verify_checked(nested_vk_limbs, i, p)) for p, i in zip(proofs, inputs)]
         with lock:
+            if getattr(self, "screen_combined", False) and v.verify_all(np.array(inputs), np.array(proofs), status=True)[0]:
+                return [0] * len(proofs)
             codes, masks = v.verify_batch_checked(np.array(inputs), np.array(proofs))
         return [int(c | m) for c, m in zip(codes, masks)]
 
@@ -644,9 +651,12 @@ def main(argv=None):
                                                                    "modes in host cores, up to the host mode's proofs/s")
     ap.add_argument("--screen-nested", action="store_true", help="verify the queued nested proofs in batches on the GPU before a batch is popped: "
                                                                  "an invalid one is dropped instead of taking a slot of a wrapping proof")
+    ap.add_argument("--screen-combined", action="store_true", help="with --screen-nested: first ONE random-combination check for the whole pool, "
+                                                                   "the per-proof batch only when it fails (pays where pools are mostly valid)")
     args = ap.parse_args(argv)
     print("[INFO] Init params of both curves")
     prover = GpuProver(args.keypair, device=args.device, gpu_witness=args.gpu_witness, hybrid_witness=args.hybrid_witness, screen_nested=args.screen_nested,
+                       screen_combined=args.screen_combined,
                        devices=[int(x) for x in args.devices.split(",")] if args.devices else None)
     print("[INFO] Circuit has %d constraints" % prover.agg.num_constraints)
     print("[INFO] Setup successful, starting the server...")

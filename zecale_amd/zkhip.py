@@ -47,6 +47,8 @@ EXPORTS = [
     "zkhip_nested_verifier_new_checked", "zkhip_nested_verifier_verify_batch_checked", "zkhip_bls12_377_point_check", "zkhip_bls12_377_groth16_verify_checked",
     "zkhip_internal_ntt_packed", "zkhip_internal_ntt_set_one_each_max",
     "zkhip_verifier_verify_all", "zkhip_groth16_verify_all", "zkhip_internal_verify_all_value", "zkhip_internal_verify_all_finish_ms",
+    "zkhip_nested_verifier_verify_all", "zkhip_nested_verifier_last_degenerate", "zkhip_bls12_377_groth16_verify_all",
+    "zkhip_internal_nested_verify_all_value", "zkhip_internal_nested_verify_all_finish_ms",
 ]
 
 
@@ -232,6 +234,12 @@ def load():
     lib.zkhip_bls12_377_groth16_verify_checked.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p, c_u64p, ctypes.c_void_p]
     lib.zkhip_internal_fq12_selftest.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, c_u64p]
     lib.zkhip_internal_nested_pairing_product.argtypes = [ctypes.c_int, c_u64p, c_u64p, ctypes.c_size_t, ctypes.c_size_t, c_u64p]
+    lib.zkhip_nested_verifier_verify_all.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+    lib.zkhip_nested_verifier_last_degenerate.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
+    lib.zkhip_bls12_377_groth16_verify_all.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p, ctypes.c_size_t, c_u64p,
+                                                       ctypes.POINTER(ctypes.c_int)]
+    lib.zkhip_internal_nested_verify_all_value.argtypes = [ctypes.c_int, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p]
+    lib.zkhip_internal_nested_verify_all_finish_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
     _lib = lib
     return lib
 
@@ -914,12 +922,31 @@ def bls12_377_groth16_verify_checked(nested_vk, inputs, proof):
     return int(st[0])
 
 
+def bls12_377_groth16_verify_all(nested_vk, inputs, proofs, rho=None):
+    """ONE random-combination check of a whole batch of nested proofs on the host (zkhip_bls12_377_groth16_verify_all; works without
+    a GPU): True iff prod_i e(rho_i A_i, B_i) e(S_acc, -g2) e(sigma alpha, -beta) e(S_C, -delta) is one and no proof has a point off
+    its curve.  nested_vk: 60 + 12 (k + 1) limbs; inputs: count x k x 6 limbs; proofs: count x 48 limbs; rho: None (drawn from the OS)
+    or count non-zero scalars below 2^128 - supplied scalars are for tests and reproducible measurements only."""
+    c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+    vk = c(nested_vk).reshape(-1)
+    k = (vk.size - 60) // 12 - 1
+    assert k >= 0 and vk.size == 60 + 12 * (k + 1)
+    pr = c(proofs).reshape(-1, 48)
+    inp = c(inputs).reshape(pr.shape[0], k, 6)
+    rl = _rho_limbs(rho, pr.shape[0])
+    ok = ctypes.c_int(0)
+    _check(load().zkhip_bls12_377_groth16_verify_all(_p(vk[:12]), _p(vk[12:36]), _p(vk[36:60]), _p(vk[60:]), k, _p(inp), _p(pr), pr.shape[0],
+                                                     None if rl is None else _p(rl), ctypes.byref(ok)))
+    return bool(ok.value)
+
+
 # the nested batch verifier's kernels (zecale_amd/csrc/pairing_bls.cuh / pairing_bls.hip): a verification owns sixteen lanes, so one
 # wave holds NESTED_VERIFIER_GROUP of them and one 128-thread workgroup NESTED_VERIFIER_WORKGROUP; a batch runs in chunks of
-# NESTED_VERIFIER_CHUNK proofs
+# NESTED_VERIFIER_CHUNK proofs; the reduction trees of a combined batch take NESTED_VERIFIER_STRIP values per strip
 NESTED_VERIFIER_GROUP = 4
 NESTED_VERIFIER_WORKGROUP = 8
 NESTED_VERIFIER_CHUNK = 8192
+NESTED_VERIFIER_STRIP = 8
 
 
 class NestedVerifier:
@@ -966,6 +993,52 @@ class NestedVerifier:
         _check(load().zkhip_nested_verifier_last_fallbacks(self.handle, ctypes.byref(n)))
         return int(n.value)
 
+    def verify_all(self, inputs, proofs, rho=None, status=False):
+        """ONE random-combination check of the whole batch (zkhip_nested_verifier_verify_all): True iff every proof is valid, up to a
+        chance of about 2^-128 - PROVIDED every point has order r, which an unchecked handle does not check: it is for proofs the
+        caller made.  rho: None (drawn from the OS) or count non-zero scalars below 2^128, for tests and reproducible measurements
+        only.  status=True (a handle made with checked=True): every proof point and input is validated first, a refused proof is left
+        out and fails the batch; returns (verdict, status bytes: the refusal byte of verify_batch_checked per proof, or 0).
+        This route answers the GROUP LAW's statement: it ACCEPTS the one kind of valid statement on which verify_batch, like the host
+        verifier whose affine accumulator chain it reproduces, says 0 - the accumulator meeting -2^j ABC_i at a clear bit j of input i
+        (tests/nested_verify_fixtures.degenerate_statement(8, negated=True)) - and hands no proof to the host (last_fallbacks() is not
+        touched).  A proof whose B has a degenerate line schedule fails the batch; last_degenerate() counts them."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 48)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        rl = _rho_limbs(rho, pr.shape[0])
+        st = np.zeros(max(pr.shape[0], 1), dtype=np.uint8) if status else None       # (never zero-length: its address says "status wanted")
+        ok = ctypes.c_int(0)
+        _check(load().zkhip_nested_verifier_verify_all(self.handle, _p(inp), _p(pr), pr.shape[0], None if rl is None else _p(rl), ctypes.byref(ok),
+                                                       None if st is None else st.ctypes.data))
+        return (bool(ok.value), st[:pr.shape[0]].tobytes()) if status else bool(ok.value)
+
+    def verify_batch_combined(self, inputs, proofs):
+        """Per-proof verdicts by way of the combined check: all ones when verify_all passes, and only otherwise the per-proof route -
+        verify_batch's bool array, or on a handle made with checked=True verify_batch_checked's (codes, masks), in front of which
+        verify_all runs with the point checks.  Where verify_all passes the answer is the group law's: a statement on which the
+        accumulator meets -2^j ABC_i at a clear bit gets 1 here and 0 from verify_batch (see verify_all).  A batch with an invalid
+        proof costs both routes; profiles/nested_verify_combined.txt and DESIGN 9e have the measurement."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 48)
+        if self.checked:
+            if self.verify_all(inputs, pr, status=True)[0]:
+                return np.zeros(pr.shape[0], dtype=np.uint8), np.zeros(pr.shape[0], dtype=np.uint8)
+            return self.verify_batch_checked(inputs, pr)
+        if self.verify_all(inputs, pr):
+            return np.ones(pr.shape[0], dtype=bool)
+        return self.verify_batch(inputs, pr)
+
+    def last_degenerate(self):
+        """How many proofs of the last verify_all had a B with a degenerate line schedule (left out; they fail the batch)."""
+        n = ctypes.c_size_t(0)
+        _check(load().zkhip_nested_verifier_last_degenerate(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def last_finish_ms(self):
+        """Host time of the last verify_all behind the device's work: the sums, S_acc, the three shared pairs, the final exponentiation."""
+        ms = ctypes.c_double(0)
+        _check(load().zkhip_internal_nested_verify_all_finish_ms(self.handle, ctypes.byref(ms)))
+        return ms.value
+
     def free(self):
         if self.handle:
             load().zkhip_nested_verifier_free(self.handle)
@@ -991,6 +1064,17 @@ def nested_pairing_product(route, g1, g2):
     assert x.ndim == 3 and y.ndim == 3 and x.shape[:2] == y.shape[:2] and x.shape[2] == 12 and y.shape[2] == 24
     out = np.zeros((x.shape[0], 12, 6), dtype=np.uint64)
     _check(load().zkhip_internal_nested_pairing_product({"host": 0, "gpu": 1}[route], _p(x), _p(y), x.shape[1], x.shape[0], _p(out)))
+    return out
+
+
+def nested_verify_all_value(route, verifier, inputs, proofs, rho):
+    """Test hook: the reduced GT value of the combined product of NestedVerifier.verify_all over the proofs that are not left out,
+    12 x 6 ABI limbs.  route "host" or "gpu"; on a checked handle both routes leave the proofs out that the point checks refuse."""
+    pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 48)
+    inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], verifier.n_inputs, 6)
+    rl = _rho_limbs(rho, pr.shape[0])
+    out = np.zeros((12, 6), dtype=np.uint64)
+    _check(load().zkhip_internal_nested_verify_all_value({"host": 0, "gpu": 1}[route], verifier.handle, _p(inp), _p(pr), pr.shape[0], _p(rl), _p(out)))
     return out
 
 
