@@ -751,6 +751,16 @@ int zkhip_internal_ntt_set_one_each_max(int log_d_max);   /* -1: the environment
  * receives n x { a b / R, a^2 / R, (a b + c d) / R } in the device's own form (R = 2^783 / 2^406).  Operands must respect the
  * bodies' contract (limbs below 2^29 except the top one, products below 2^10 R p). */
 int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out);
+/* Test hook (no counterpart): the rest of the device build's field layer (fp29.cuh, fp_inv.cuh) on raw limbs, one function per call
+ * and one GPU lane per case, 64 lanes a workgroup (case i is lane i % 64 of wave i / 64).  limbs_in holds n cases of three operands
+ * (a, b, c) of NL 32-bit words each (NL = 27 / 14); limbs_out receives n x (NL words, one flag word).  op:
+ *   0 fp_add(a, b)   1 fp_dbl(a)   2 .. 5 fp_sub<K>(a, b), K = 2, 4, 8, 16   6 fp_sub_sub2<8>(a, b, c)   7 fp_cond_sub_p(a)
+ *   8 .. 11 fp_cond_sub_kp<K>(a), K = 1, 2, 4, 8   12 fp_canon_4p(a)   13 fp_canon(a)   14 fp_is_zero_2p(a): a and, in the flag, 0 / 1
+ *   15 fp_unpack32 then fp_pack32: N32 words in a, N32 words out (N32 = 24 / 12)   16 fp_pack32 then fp_unpack32 of the limbs a
+ *   17 fp_to_abi then fp_from_abi   18 fp_abi_to_canonical_words: N32 words in a, N32 words out   19 fp_inv(a)
+ *   32 + log2 K: fp_sub_k<K>(a, b) for the K the library itself uses (Fq: 1, 32; Fr: 2, 4, 8, 16, 64, 128)
+ * An op the field does not have gives ZKHIP_ERR_ARG.  Operands must respect each function's documented contract. */
+int zkhip_internal_field_ops_selftest(int field, int op, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out);
 /* Test hooks of the Edwards accumulation's lockstep route (no counterpart).  A single MSM over a table in the Edwards model always
  * enqueues two accumulations, one bucket per lane (k_accumulate_edw_lock) and sliced (k_accumulate_edw); a word the device writes
  * per launch decides which of them runs.

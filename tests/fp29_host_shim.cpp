@@ -43,4 +43,52 @@ extern "C" {
     fp_to_abi<PR>(fp_sqr(t), r); }
 SHIM(fq, FqParams, 12)
 SHIM(fr, FrParams, 6)
+
+// One raw-limb entry per op of tests/field_ops_cases.py: three operands of NL words in, NL words and a flag word out - the layout of the
+// device hook zkhip_internal_field_ops_selftest, so that one case list and one reference serve both builds.
+#define OP_ENTRY(F, PR, NAME, BODY)                                                            \
+  void F##_op_##NAME(const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* r) {   \
+    constexpr int N = PR::NL, W = PR::N32;                                                     \
+    Fp<PR> x, y, z, o = fp_zero<PR>();                                                         \
+    uint32_t flag = 0, w[W];                                                                   \
+    uint64_t q[PR::N64];                                                                       \
+    (void)w; (void)q;                                                                          \
+    for (int i = 0; i < N; i++) { x.l[i] = a[i]; y.l[i] = b[i]; z.l[i] = c[i]; }               \
+    BODY;                                                                                      \
+    for (int i = 0; i < N; i++) r[i] = o.l[i];                                                 \
+    r[N] = flag; }
+#define OPS(F, PR)                                                                             \
+  OP_ENTRY(F, PR, add, o = fp_add(x, y))                                                       \
+  OP_ENTRY(F, PR, dbl, o = fp_dbl(x))                                                          \
+  OP_ENTRY(F, PR, sub_2, (o = fp_sub<PR, 2>(x, y)))                                            \
+  OP_ENTRY(F, PR, sub_4, (o = fp_sub<PR, 4>(x, y)))                                            \
+  OP_ENTRY(F, PR, sub_8, (o = fp_sub<PR, 8>(x, y)))                                            \
+  OP_ENTRY(F, PR, sub_16, (o = fp_sub<PR, 16>(x, y)))                                          \
+  OP_ENTRY(F, PR, sub_sub2_8, (o = fp_sub_sub2<PR, 8>(x, y, z)))                               \
+  OP_ENTRY(F, PR, cond_sub_p, o = fp_cond_sub_p(x))                                            \
+  OP_ENTRY(F, PR, cond_sub_kp_1, (o = fp_cond_sub_kp<PR, 1>(x)))                               \
+  OP_ENTRY(F, PR, cond_sub_kp_2, (o = fp_cond_sub_kp<PR, 2>(x)))                               \
+  OP_ENTRY(F, PR, cond_sub_kp_4, (o = fp_cond_sub_kp<PR, 4>(x)))                               \
+  OP_ENTRY(F, PR, cond_sub_kp_8, (o = fp_cond_sub_kp<PR, 8>(x)))                               \
+  /* fp_canon_4p lives in ec_affine.cuh, which only compiles for the device: its one line is spelled out here */ \
+  OP_ENTRY(F, PR, canon_4p, (o = fp_cond_sub_kp<PR, 1>(fp_cond_sub_kp<PR, 2>(x))))             \
+  OP_ENTRY(F, PR, canon, o = fp_canon(x))                                                      \
+  OP_ENTRY(F, PR, is_zero_2p, o = x; flag = fp_is_zero_2p(x) ? 1u : 0u)                        \
+  OP_ENTRY(F, PR, unpack_pack, for (int i = 0; i < W; i++) w[i] = a[i]; x = fp_unpack32<PR>(w); fp_pack32<PR>(x, w); for (int i = 0; i < W; i++) o.l[i] = w[i]) \
+  OP_ENTRY(F, PR, pack_unpack, fp_pack32<PR>(x, w); o = fp_unpack32<PR>(w))                    \
+  OP_ENTRY(F, PR, abi_roundtrip, fp_to_abi<PR>(x, q); o = fp_from_abi<PR>(q))                  \
+  OP_ENTRY(F, PR, abi_to_canonical_words, for (int i = 0; i < PR::N64; i++) q[i] = (uint64_t)a[2 * i] | ((uint64_t)a[2 * i + 1] << 32); \
+           fp_abi_to_canonical_words<PR>(q, w); for (int i = 0; i < W; i++) o.l[i] = w[i])     \
+  OP_ENTRY(F, PR, inv, o = fp_inv<PR>(x))
+OPS(fq, FqParams)
+OPS(fr, FrParams)
+// fp_sub_k<K> for the K the library instantiates per field (listed in tests/field_ops_cases.py)
+OP_ENTRY(fq, FqParams, sub_k_1, (o = fp_sub_k<FqParams, 1>(x, y)))
+OP_ENTRY(fq, FqParams, sub_k_32, (o = fp_sub_k<FqParams, 32>(x, y)))
+OP_ENTRY(fr, FrParams, sub_k_2, (o = fp_sub_k<FrParams, 2>(x, y)))
+OP_ENTRY(fr, FrParams, sub_k_4, (o = fp_sub_k<FrParams, 4>(x, y)))
+OP_ENTRY(fr, FrParams, sub_k_8, (o = fp_sub_k<FrParams, 8>(x, y)))
+OP_ENTRY(fr, FrParams, sub_k_16, (o = fp_sub_k<FrParams, 16>(x, y)))
+OP_ENTRY(fr, FrParams, sub_k_64, (o = fp_sub_k<FrParams, 64>(x, y)))
+OP_ENTRY(fr, FrParams, sub_k_128, (o = fp_sub_k<FrParams, 128>(x, y)))
 }

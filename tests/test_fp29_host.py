@@ -108,3 +108,28 @@ def test_dual_product_at_its_column_bound(shim, name, p, nl):
         assert all(v < (1 << 29) for v in list(out)[:-1])
         assert got % p == (val(a) * val(b) + val(c) * val(d)) * pow(Rdev, -1, p) % p
         assert got < (val(a) * val(b) + val(c) * val(d)) // Rdev + p + 1
+
+
+def _field_ops():
+    from tests import field_ops_cases as C
+    return [(name, op) for name, f in C.FIELDS.items() for op in C.ops_for(f)]
+
+
+@pytest.mark.parametrize("name,op", _field_ops())
+def test_field_ops_on_raw_limbs(shim, name, op):
+    """Every op of tests/field_ops_cases.py through the g++ build, raw limbs in and out, against the generator's exact expectations: the
+    same cases and the same reference that tests/test_field_ops_gpu.py gives the device build.  (On the host fp_inv leaves its loop as
+    soon as its own g is 0: the wave layout of the inversion cases matters on the device only.)"""
+    from tests import field_ops_cases as C
+    f = C.FIELDS[name]
+    cases = C.cases(name, op)
+    fn = getattr(shim, "%s_op_%s" % (name, op))
+    fn.restype = None
+    out = (ctypes.c_uint32 * (f.nl + 1))()
+    done = 0
+    for case in cases:
+        a, b, c = ((ctypes.c_uint32 * f.nl)(*x) for x in C.operands(f, op, case))
+        fn(a, b, c, out)
+        C.check(f, op, case, list(out))
+        done += 1
+    assert done == C.n_cases(name, op) and done >= 300

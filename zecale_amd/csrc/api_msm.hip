@@ -546,6 +546,13 @@ int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n,
   return msm_field_selftest(field, limbs_in, n, limbs_out, t_err, sizeof t_err);
 }
 
+int zkhip_internal_field_ops_selftest(int field, int op, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out) {
+  BIND_CUR();
+  if ((field != 0 && field != 1) || (n && (!limbs_in || !limbs_out)) || n > (1u << 20)) return fail(ZKHIP_ERR_ARG, "field 0 (Fq) or 1 (Fr), at most 2^20 cases");
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return msm_field_ops_selftest(field, op, limbs_in, n, limbs_out, t_err, sizeof t_err);
+}
+
 // Test hook of the bucket reduction's tail (msm.hip enqueue_tail)
 int zkhip_internal_msm_tail(int edw, const uint64_t* items_affine, int W, unsigned N, int lo_bits, int total, uint64_t* out_jac) {
   BIND_CUR();

@@ -147,6 +147,9 @@ static inline const EdwPacked* msm_edw_at(const EdwPacked* t, size_t i) {
 
 // Fq multiplications per second of the whole device, measured now: dependent fp_mul chains at two waves per SIMD (~25 ms)
 int msm_field_selftest(int field, const uint32_t* in_host, size_t n, uint32_t* out_host, char* errbuf, size_t errlen);
+// test hook: one function of the field layer (fp29.cuh, fp_inv.cuh) per launch on n cases of three raw-limb operands; out: n x (NL words
+// and a flag word).  ZKHIP_ERR_ARG for an op the field does not have (msm.hip FieldOp)
+int msm_field_ops_selftest(int field, int op, const uint32_t* in_host, size_t n, uint32_t* out_host, char* errbuf, size_t errlen);
 int msm_measure_fqmul_rate(double* fq_mul_per_s, char* errbuf, size_t errlen);
 // test hook: the tail of the bucket reduction (bit planes, R * hi + lo) on 2W groups of N affine ABI points given on the host;
 // an Edwards run (edw != 0) returns twice the sums.  out_jac: W points (+ W plain totals of the lo groups if total), 36 limbs each

@@ -1546,6 +1546,109 @@ int msm_field_selftest(int field, const uint32_t* in_host, size_t n, uint32_t* o
   return ZKHIP_OK;
 }
 
+// The rest of the field layer of the DEVICE build on raw limbs (tests/test_field_ops_gpu.py; cases and exact expectations from
+// tests/field_ops_cases.py): the lazy linear operations, the range folds and the zero test, the packing, and fp_inv with its wave
+// vote.  One lane per case, 64 lanes a workgroup: case i runs in wave i / 64 as lane i % 64, which is what the inversion cases are laid
+// out by.  One op per launch (the switch is uniform).  in: n x (a, b, c), NL words each; out: n x (NL words, one flag word).
+// fp_sub_k<K> is instantiated for the K its call sites use: Fq 1 (ec_edw.cuh) and 32 (pairing.cuh); Fr 16, 64, 128 and, through
+// fr2_sub<K> / nf_sub<K>, 2, 4, 8, 16 (pairing_bls.cuh).
+enum FieldOp : int {
+  FO_ADD = 0, FO_DBL, FO_SUB2, FO_SUB4, FO_SUB8, FO_SUB16, FO_SUB_SUB2_8, FO_COND_SUB_P, FO_COND_SUB_KP1, FO_COND_SUB_KP2, FO_COND_SUB_KP4,
+  FO_COND_SUB_KP8, FO_CANON_4P, FO_CANON, FO_IS_ZERO_2P, FO_UNPACK_PACK, FO_PACK_UNPACK, FO_ABI_ROUNDTRIP, FO_ABI_TO_CANONICAL_WORDS, FO_INV,
+  FO_SUB_K = 32   // + log2 K
+};
+template <class PR>
+constexpr bool field_op_known(int op) {
+  if (op >= FO_ADD && op <= FO_INV) return true;
+  const int K = (op >= FO_SUB_K && op < FO_SUB_K + 8) ? 1 << (op - FO_SUB_K) : 0;
+  return PR::NL == FqParams::NL ? (K == 1 || K == 32) : (K == 2 || K == 4 || K == 8 || K == 16 || K == 64 || K == 128);
+}
+template <class PR, int K>
+__device__ __forceinline__ Fp<PR> field_op_sub_k(const Fp<PR>& a, const Fp<PR>& b) {
+  if constexpr (field_op_known<PR>(FO_SUB_K + __builtin_ctz(K))) return fp_sub_k<PR, K>(a, b);
+  else return fp_zero<PR>();
+}
+template <class PR>
+__global__ void __launch_bounds__(64) k_field_ops_selftest(int op, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr int N = PR::NL, W = PR::N32;
+  static_assert(W <= N && 2 * PR::N64 == W, "");
+  Fp<PR> a, b, c;
+  for (int k = 0; k < N; k++) { a.l[k] = in[(i * 3 + 0) * N + k]; b.l[k] = in[(i * 3 + 1) * N + k]; c.l[k] = in[(i * 3 + 2) * N + k]; }
+  Fp<PR> r = fp_zero<PR>();
+  uint32_t flag = 0;
+  uint32_t w[W];
+  uint64_t x[PR::N64];
+  switch (op) {
+    case FO_ADD: r = fp_add(a, b); break;
+    case FO_DBL: r = fp_dbl(a); break;
+    case FO_SUB2: r = fp_sub<PR, 2>(a, b); break;
+    case FO_SUB4: r = fp_sub<PR, 4>(a, b); break;
+    case FO_SUB8: r = fp_sub<PR, 8>(a, b); break;
+    case FO_SUB16: r = fp_sub<PR, 16>(a, b); break;
+    case FO_SUB_SUB2_8: r = fp_sub_sub2<PR, 8>(a, b, c); break;
+    case FO_COND_SUB_P: r = fp_cond_sub_p(a); break;
+    case FO_COND_SUB_KP1: r = fp_cond_sub_kp<PR, 1>(a); break;
+    case FO_COND_SUB_KP2: r = fp_cond_sub_kp<PR, 2>(a); break;
+    case FO_COND_SUB_KP4: r = fp_cond_sub_kp<PR, 4>(a); break;
+    case FO_COND_SUB_KP8: r = fp_cond_sub_kp<PR, 8>(a); break;
+    case FO_CANON_4P: r = fp_canon_4p(a); break;
+    case FO_CANON: r = fp_canon(a); break;
+    case FO_IS_ZERO_2P: r = a; flag = fp_is_zero_2p(a) ? 1u : 0u; break;
+    case FO_UNPACK_PACK:                              // a holds N32 packed words
+      for (int k = 0; k < W; k++) w[k] = a.l[k];
+      a = fp_unpack32<PR>(w);
+      fp_pack32<PR>(a, w);
+      for (int k = 0; k < W; k++) r.l[k] = w[k];
+      break;
+    case FO_PACK_UNPACK: fp_pack32<PR>(a, w); r = fp_unpack32<PR>(w); break;
+    case FO_ABI_ROUNDTRIP: fp_to_abi<PR>(a, x); r = fp_from_abi<PR>(x); break;
+    case FO_ABI_TO_CANONICAL_WORDS:                   // a holds the N64 ABI limbs as N32 words
+      for (int k = 0; k < PR::N64; k++) x[k] = (uint64_t)a.l[2 * k] | ((uint64_t)a.l[2 * k + 1] << 32);
+      fp_abi_to_canonical_words<PR>(x, w);
+      for (int k = 0; k < W; k++) r.l[k] = w[k];
+      break;
+    case FO_INV: r = fp_inv<PR>(a); break;
+    case FO_SUB_K + 0: r = field_op_sub_k<PR, 1>(a, b); break;
+    case FO_SUB_K + 1: r = field_op_sub_k<PR, 2>(a, b); break;
+    case FO_SUB_K + 2: r = field_op_sub_k<PR, 4>(a, b); break;
+    case FO_SUB_K + 3: r = field_op_sub_k<PR, 8>(a, b); break;
+    case FO_SUB_K + 4: r = field_op_sub_k<PR, 16>(a, b); break;
+    case FO_SUB_K + 5: r = field_op_sub_k<PR, 32>(a, b); break;
+    case FO_SUB_K + 6: r = field_op_sub_k<PR, 64>(a, b); break;
+    case FO_SUB_K + 7: r = field_op_sub_k<PR, 128>(a, b); break;
+    default: break;
+  }
+  for (int k = 0; k < N; k++) out[i * (N + 1) + k] = r.l[k];
+  out[i * (N + 1) + N] = flag;
+}
+
+int msm_field_ops_selftest(int field, int op, const uint32_t* in_host, size_t n, uint32_t* out_host, char* errbuf, size_t errlen) {
+  if (!(field == 0 ? field_op_known<FqParams>(op) : field_op_known<FrParams>(op))) {
+    if (errbuf) snprintf(errbuf, errlen, "msm_field_ops_selftest: op %d is not one of field %d's", op, field);
+    return ZKHIP_ERR_ARG;
+  }
+  const size_t N = field == 0 ? FqParams::NL : FrParams::NL;
+  uint32_t *in = nullptr, *out = nullptr;
+  hipError_t e = hipMalloc(&in, n * 3 * N * 4 + 4);
+  if (e == hipSuccess) e = hipMalloc(&out, n * (N + 1) * 4 + 4);
+  if (e == hipSuccess) e = hipMemcpy(in, in_host, n * 3 * N * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) {
+    if (field == 0) hipLaunchKernelGGL(k_field_ops_selftest<FqParams>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, op, in, out, n);
+    else hipLaunchKernelGGL(k_field_ops_selftest<FrParams>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, op, in, out, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out_host, out, n * (N + 1) * 4, hipMemcpyDeviceToHost);
+  if (in) (void)hipFree(in);
+  if (out) (void)hipFree(out);
+  if (e != hipSuccess) {
+    if (errbuf) snprintf(errbuf, errlen, "msm_field_ops_selftest: %s", hipGetErrorString(e));
+    return ZKHIP_ERR_HIP;
+  }
+  return ZKHIP_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // host orchestration
 // ------------------------------------------------------------------------------------------

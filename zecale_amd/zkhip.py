@@ -31,7 +31,7 @@ EXPORTS = [
     "zkhip_groth16_setup", "zkhip_groth16_setup_slice", "zkhip_keypair_crs_desc", "zkhip_keypair_vk", "zkhip_keypair_free", "zkhip_keypair_write", "zkhip_keypair_read",
     "zkhip_jac_to_affine", "zkhip_jac_add", "zkhip_to_canonical",
     "zkhip_last_accumulate_interval", "zkhip_crs_upload_ex", "zkhip_crs_upload_slice_ex", "zkhip_bases_precompute_ex", "zkhip_crs_table_kind", "zkhip_crs_finite_terms",
-    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_pipeline_witness_sizing", "zkhip_internal_witness_run_program", "zkhip_internal_witness_run_program_wide", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_internal_gpu_witness_run_wide", "zkhip_gpu_witness_set_waves", "zkhip_gpu_witness_plan", "zkhip_gpu_witness_last_ms", "zkhip_device_memory", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
+    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_field_ops_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_pipeline_witness_sizing", "zkhip_internal_witness_run_program", "zkhip_internal_witness_run_program_wide", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_internal_gpu_witness_run_wide", "zkhip_gpu_witness_set_waves", "zkhip_gpu_witness_plan", "zkhip_gpu_witness_last_ms", "zkhip_device_memory", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
     "zkhip_msm_stream_new", "zkhip_msm_stream_submit", "zkhip_msm_stream_submit_host", "zkhip_msm_stream_collect", "zkhip_msm_stream_last_accumulate_ms",
     "zkhip_msm_stream_last_accumulate_interval", "zkhip_msm_stream_free", "zkhip_prover_new_slice", "zkhip_prover_prove_partial",
     "zkhip_dispatcher_new", "zkhip_dispatcher_size", "zkhip_dispatcher_submit", "zkhip_dispatcher_wait", "zkhip_dispatcher_stats", "zkhip_dispatcher_free",
@@ -1790,6 +1790,19 @@ def field_selftest(field, limbs_in):
     lib = load()
     lib.zkhip_internal_field_selftest.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     _check(lib.zkhip_internal_field_selftest(int(field), x.ctypes.data, x.shape[0], out.ctypes.data))
+    return out
+
+
+def field_ops_selftest(field, op, operands):
+    """Test hook: one function of the device's field layer on raw limbs (zkhip_internal_field_ops_selftest; the op codes are listed in
+    include/zkhip.h).  field 0 = Fq (27 limbs), 1 = Fr (14); operands: uint32 [n][3][NL] = cases of (a, b, c), one GPU lane per case in
+    order; returns uint32 [n][NL + 1]: the result and a flag word."""
+    nl = 27 if field == 0 else 14
+    x = np.ascontiguousarray(operands, dtype=np.uint32).reshape(-1, 3, nl)
+    out = np.zeros((x.shape[0], nl + 1), dtype=np.uint32)
+    lib = load()
+    lib.zkhip_internal_field_ops_selftest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    _check(lib.zkhip_internal_field_ops_selftest(int(field), int(op), x.ctypes.data, x.shape[0], out.ctypes.data))
     return out
 
 
