@@ -74,7 +74,8 @@ struct extended_proof {
 
 class keypair {                            // wsnarkT::keypair: pk (HBM-resident) + vk
  public:
-  // opts: the key's own table / launch options (a server that proves a stream asks for table_naf = 1); nullptr = the defaults
+  // opts: the key's own table / launch options (a server that proves a stream asks for table_naf = 1, or for table_model = 1: Edwards
+  // tables for the G1 query vectors); nullptr = the defaults
   explicit keypair(zkhip_keypair* kp, const zkhip_key_opts* opts = nullptr) : kp_(kp) {
     zkhip_crs_desc d;
     zk_check(zkhip_keypair_crs_desc(kp_, &d), "zkhip_keypair_crs_desc");
@@ -84,6 +85,7 @@ class keypair {                            // wsnarkT::keypair: pk (HBM-resident
   keypair& operator=(const keypair&) = delete;
   ~keypair() { zkhip_crs_free(crs_); zkhip_keypair_free(kp_); }
   const zkhip_crs* pk() const { return crs_; }
+  int table_model() const { return zkhip_crs_table_model(crs_); }      // 1: the key is on the Edwards model (opts->table_model = 1 took effect)
   // points of the evaluation domain the key was generated on (its H query has one fewer): a prover follows the key
   size_t domain_size() const { zkhip_crs_desc d; zk_check(zkhip_keypair_crs_desc(kp_, &d), "zkhip_keypair_crs_desc"); return d.domain_size; }
   const zkhip_keypair* host() const { return kp_; }      // the key in host memory (what a multi-GPU stream uploads to every GPU)

@@ -45,7 +45,8 @@ struct csr_matrix {
 // (libzecale/circuits/aggregator_circuit.hpp:95-97).
 class hip_proving_key {
  public:
-  // opts: this key's own table / launch options (zkhip_key_opts travel with the handle; nullptr = the defaults)
+  // opts: this key's own table / launch options (zkhip_key_opts travel with the handle; nullptr = the defaults; table_model = 1:
+  // the G1 MSMs of its proofs add on G1's 2-isogenous Edwards curve - table_model() tells whether the key could take it)
   // The KEY names the QAP's evaluation domain (crs.domain_size): a key from the reference's generate_setup - libzeth forces a power
   // of two, 65,536 points for the wrapping circuit (aggregator_circuit.tcc:108) - proves as it is; so does a key generated here on
   // libfqfft's unforced step domain.  The constraint system is uploaded on the key's domain.
@@ -71,6 +72,8 @@ class hip_proving_key {
   ~hip_proving_key() { zkhip_multi_prover_free(multi_); zkhip_crs_free(crs_); zkhip_r1cs_free(r1cs_); }
   size_t num_devices() const { return multi_ ? (size_t)zkhip_multi_prover_size(multi_) : 1; }
 
+  // 1: the key is on the Edwards model (zkhip_key_opts.table_model = 1 took effect); 0: XYZZ, and always for a key held in slices
+  int table_model() const { return crs_ ? zkhip_crs_table_model(crs_) : 0; }
   size_t num_variables() const { return n_vars_; }
   size_t domain_size() const { return zkhip_r1cs_domain_size(r1cs_); }          // the key's: 2^k (a reference key), or 2^k + 2^r
   unsigned log_domain_size() const { return zkhip_r1cs_log_domain(r1cs_); }      // ceil(log2 domain_size())

@@ -65,6 +65,17 @@ typedef struct {
                        non-adjacent form (378 levels: within ZKHIP_NAF_TABLE_GB, default 48 GB per key, else one level per window) */
   int window;       /*  0: automatic from the length;  else the window c of the table, in [4, 22] */
   int batch_msms;   /* -1: default (on);  0: one launch sequence per MSM;  1: the five MSMs of a proof in one launch sequence */
+  int table_model;  /*  0: default, XYZZ;  1: the key's four G1 query vectors (A, B-G1, H, L) also get their tables in precomputed form
+                       on G1's 2-isogenous twisted Edwards curve (1.5 x the tables' memory on top), and the G1 MSMs of a proof add in
+                       that model: with batch_msms all four in ONE launch sequence, B-G2 (no such curve: XYZZ) in a second one beside
+                       it.  Proofs are identical.  The LAST field, 0 its default: ZKHIP_KEY_OPTS_DEFAULT and every initialiser of the
+                       four fields above leave it 0.  Rules (any other value, or a rule broken: ZKHIP_ERR_ARG at upload):
+                         - needs tables: with precompute = 0 (given, or the resolved process-wide default) it is an error;
+                         - Edwards tables have one level per window: with table_naf = 1 it is an error; with table_naf = -1 the key
+                           gets one level per window whatever the process-wide default (zkhip_set_table_naf, ZKHIP_TABLE_NAF) says;
+                         - the key is on the Edwards model only if ALL four G1 vectors got their Edwards form: a point that is not
+                           of order r, or the memory guard of zkhip_set_table_model, leaves an ordinary XYZZ key (the forms already
+                           built are freed) and the upload succeeds: zkhip_crs_table_model tells.  The XYZZ tables always stay. */
 } zkhip_key_opts;
 #define ZKHIP_KEY_OPTS_DEFAULT {-1, -1, 0, -1}
 
@@ -236,6 +247,7 @@ int zkhip_crs_upload(const zkhip_crs_desc* d, zkhip_crs** out);
 int zkhip_crs_upload_ex(const zkhip_crs_desc* d, const zkhip_key_opts* opts, zkhip_crs** out);
 void zkhip_crs_free(zkhip_crs* c);
 int zkhip_crs_table_kind(const zkhip_crs* c);            /* 0: no tables, 1: one level per window, 2: every bit position (NAF scalars) */
+int zkhip_crs_table_model(const zkhip_crs* c);           /* 1: the key's G1 MSMs add on the Edwards curve (zkhip_key_opts.table_model took effect), 0: XYZZ */
 /* bases of the five query vectors (A, B-G2, B-G1, H, L) that are not the point at infinity: the terms an MSM over the key can
  * actually have (a base at infinity produces no bucket entry) */
 int zkhip_crs_finite_terms(const zkhip_crs* c, size_t out[5]);
@@ -301,6 +313,14 @@ int zkhip_prover_timings_chained(zkhip_prover* p);
  * for the plain entry points
  * (zkhip_groth16_prove[_partial|_app]) on the calling thread's device: */
 int zkhip_last_prove_split(void);
+/* *out = 1: the G1 MSMs of p's last proof accumulated on the Edwards curve (a key with zkhip_key_opts.table_model = 1 that took
+ * effect: four G1 MSMs in one launch sequence and B-G2 in a second, or with batch_msms = 0 one sequence per MSM), 0: XYZZ - an
+ * XYZZ key, or a strategy that fell back.  Read from the launches themselves, not from the key.  With such a key the five MSM slots
+ * of zkhip_prover_timings all hold the time from the first launch to the collection of BOTH sequences, zkhip_prover_last_accumulate_ms
+ * the sum of the two accumulation launches and zkhip_prover_last_accumulate_entries the entries of both.
+ * zkhip_last_prove_table_model: the same for the plain entry points on the calling thread's device. */
+int zkhip_prover_last_table_model(zkhip_prover* p, int* out);
+int zkhip_last_prove_table_model(void);
 /* the option itself, process-wide (provers that are NOT streaming): 0 one launch sequence (default), 1 two sequences with the H
  * accumulation gated behind the first, 2 not gated.  Proofs are bit-identical in every mode. */
 int zkhip_set_prove_split(int mode);
@@ -770,6 +790,13 @@ int zkhip_internal_field_ops_selftest(int field, int op, const uint32_t* limbs_i
  * otherwise: 1 lockstep, 0 sliced, -1 not an Edwards launch. */
 int zkhip_internal_set_lockstep(int mode, int min_buckets);
 int zkhip_internal_last_acc_path(int* out);
+/* Test hook of the merged launch (no counterpart; otherwise reachable through whole proofs only): K <= 4 MSMs, job k over the first
+ * n[k] bases of sets[k] with the host scalars scalars[k] (n[k] x 6 limbs), through ONE launch sequence.  The sets are table-backed,
+ * one level per window, all of one window (zkhip_bases_precompute).  model 0: XYZZ; 1: the Edwards accumulation
+ * (k_accumulate_edw_multi for K > 1) - a set with terms but without an Edwards form (a G2 set) gives ZKHIP_ERR_STATE before anything is
+ * enqueued.  *acc_path as zkhip_internal_last_acc_path for this launch; out_jac: K x 36 limbs. */
+int zkhip_internal_msm_multi(const zkhip_bases* const* sets, const uint64_t* const* scalars, const size_t* n, int K, int montgomery, int model,
+                             int* acc_path, uint64_t* out_jac);
 /* Test / A-B hook (no counterpart; results never depend on it).
  * set_msm_stream_layout: how the zkhip_msm_streams made from now on place their contexts' HIP streams:
  * 0 = every context creates its pair at its first submit, 1 = all primaries, then all secondaries, when the stream is made,

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """VGPRs, spills, LDS and scratch of every kernel in zecale_amd/libzkhip.so (or another library / object given as argument): reads the
-code objects embedded in .hip_fatbin (clang offload bundles) and prints their AMDGPU metadata.  Works without a GPU."""
+code objects embedded in .hip_fatbin (clang offload bundles) and prints their AMDGPU metadata.  Works without a GPU.
+A second argument keeps the kernels whose name contains it: `kernel_resources.py zecale_amd/libzkhip.so k_accumulate` lists the bucket
+accumulations DESIGN.md section 6 quotes - k_accumulate<1>, k_accumulate<5>, k_accumulate_edw, k_accumulate_edw_lock and
+k_accumulate_edw_multi (78 KiB of LDS each: two workgroups per CU)."""
 import os, re, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 path = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zecale_amd", "libzkhip.so")

@@ -44,6 +44,7 @@ struct zkhip_crs {
   uint64_t alpha_g1[24], beta_g1[24], beta_g2[24], delta_g1[24], delta_g2[24];
   int device;
   int batch_msms = 1;     // the five MSMs of a proof in one launch sequence (zkhip_key_opts; the key carries its own choice)
+  int table_model = 0;    // 1: A, B1, H and L all have their Edwards tables (zkhip_key_opts.table_model): the G1 MSMs of a proof add in that model
   mutable std::once_flag tail_once;               // built by the key's first proof (~0.2 s of host time)
   mutable std::unique_ptr<TailTables> tail;
 };
@@ -65,6 +66,7 @@ struct ProveState {
   hipEvent_t ev_st = nullptr;      // blocking-sync event for waits on st (the waiting host thread sleeps)
   hipEvent_t ev_up = nullptr, ev_qap = nullptr;   // split proofs: the assignment is on the device / the QAP map has finished (stream-to-stream)
   bool split_last = false;         // the last proof ran as two launch sequences (A, B-G2, B-G1, L beside the QAP map; then H)
+  bool edw_last = false;           // the G1 MSMs of the last proof accumulated on the Edwards curve (read from their launches: MsmCtx::win_edw)
   MsmCtx* last_acc_ctx2 = nullptr; // ... whose second accumulation launch ran on this plan
   uint64_t* dz = nullptr;
   size_t dz_cap = 0;

@@ -16,14 +16,27 @@ struct zkhip_keypair {
 
 // The options of a key, resolved once at upload against the process-wide defaults (zkhip_set_*), then carried by the handle:
 // two threads loading keys with different options never see each other's choice.
-struct ResolvedOpts { int precompute, naf, window, batch; };
+struct ResolvedOpts { int precompute, naf, window, batch, model; };
 static ResolvedOpts resolve_opts(const zkhip_key_opts* o) {
   ResolvedOpts r;
   r.precompute = (o && o->precompute >= 0) ? (o->precompute ? 1 : 0) : g.crs_tables.load();
   r.naf = (o && o->table_naf >= 0) ? (o->table_naf ? 1 : 0) : -1;                  // -1: naf_tables_wanted() decides
   r.window = (o && o->window > 0) ? o->window : g.forced_c.load();
   r.batch = (o && o->batch_msms >= 0) ? (o->batch_msms ? 1 : 0) : g.batch_msms.load();
+  r.model = (o && o->table_model == 1) ? 1 : 0;
+  if (r.model && r.naf < 0) r.naf = 0;      // Edwards tables have one level per window, whatever the process-wide default says
   return r;
+}
+// what an upload refuses before it allocates anything (zkhip.h: the rules of zkhip_key_opts)
+static int check_opts(const zkhip_key_opts* o) {
+  if (!o) return ZKHIP_OK;
+  if (o->window < 0 || (o->window > 0 && (o->window < 4 || o->window > 22)))
+    return fail(ZKHIP_ERR_ARG, "zkhip_key_opts.window must be 0 (automatic) or in [4, 22]");
+  if (o->table_model != 0 && o->table_model != 1) return fail(ZKHIP_ERR_ARG, "zkhip_key_opts.table_model must be 0 (XYZZ) or 1 (Edwards)");
+  if (o->table_model == 1 && !resolve_opts(o).precompute) return fail(ZKHIP_ERR_ARG, "zkhip_key_opts.table_model = 1 needs window tables (precompute)");
+  if (o->table_model == 1 && o->table_naf > 0)
+    return fail(ZKHIP_ERR_ARG, "zkhip_key_opts.table_model = 1 with table_naf = 1: Edwards tables have one level per window");
+  return ZKHIP_OK;
 }
 
 // one window size for the whole key (the prover's MSM contexts are shared by the five query vectors)
@@ -49,17 +62,26 @@ static int crs_build_tables(zkhip_crs* c, const ResolvedOpts& o) {
     if (tc < 9) tc = 9;
     if (tc > 20) tc = 20;
   }
+  // the Edwards form for the four G1 vectors of a key that asks for it, never for B-G2 (its curve has no rational 2-torsion)
+  const bool edw = o.model == 1 && !naf;
   for (zkhip_bases* b : all) {
-    int rc = bases_precompute_mode(b, tc, naf);
+    int rc = bases_precompute_mode(b, tc, naf, edw && b != c->B2);
     if (rc != ZKHIP_OK) return rc;
+  }
+  if (edw) {
+    // all four or none: a vector that was refused (a point not of order r, the memory guard) leaves an ordinary XYZZ key
+    zkhip_bases* g1[4] = {c->A, c->B1, c->H, c->L};
+    bool all_edw = true, any = false;
+    for (zkhip_bases* b : g1) { if (b->len && !b->d_edw) all_edw = false; if (b->d_edw) any = true; }
+    if (all_edw && any) c->table_model = 1;
+    else for (zkhip_bases* b : g1) if (b->d_edw) { (void)hipFree(b->d_edw); b->d_edw = nullptr; }
   }
   return ZKHIP_OK;
 }
 
 static int crs_upload_impl(const zkhip_crs_desc* d, size_t a_lo, size_t a_len, size_t h_lo, size_t h_len, size_t l_lo, size_t l_len,
                            const zkhip_key_opts* opts, zkhip_crs** out) {
-  if (opts && (opts->window < 0 || (opts->window > 0 && (opts->window < 4 || opts->window > 22))))
-    return fail(ZKHIP_ERR_ARG, "zkhip_key_opts.window must be 0 (automatic) or in [4, 22]");
+  { int rc_ = check_opts(opts); if (rc_ != ZKHIP_OK) return rc_; }
   zkhip_crs* c = new zkhip_crs();
   c->device = cur_dev();
   c->n_vars = d->n_vars; c->n_primary = d->n_primary; c->domain_size = d->domain_size;
@@ -180,6 +202,7 @@ int zkhip_crs_upload_slice(const zkhip_crs_desc* d, size_t a_lo, size_t a_len, s
 int zkhip_crs_table_window(const zkhip_crs* c) { return (c && c->A) ? c->A->table_c : 0; }
 int zkhip_crs_device(const zkhip_crs* c) { return c ? c->device : -1; }
 int zkhip_crs_table_kind(const zkhip_crs* c) { return (c && c->A && c->A->table_c) ? (c->A->table_naf ? 2 : 1) : 0; }
+int zkhip_crs_table_model(const zkhip_crs* c) { return c ? c->table_model : 0; }
 int zkhip_crs_finite_terms(const zkhip_crs* c, size_t out[5]) {
   if (!c || !out) return fail(ZKHIP_ERR_ARG, "null pointer");
   const zkhip_bases* all[5] = {c->A, c->B2, c->B1, c->H, c->L};
@@ -244,8 +267,7 @@ int zkhip_groth16_setup_slice(const zkhip_r1cs_desc* cs, const uint64_t tau_m[6]
   BIND_CUR();
   if (!cs || !tau_m || !alpha_m || !beta_m || !delta_m || !slice_out || !ranges) return fail(ZKHIP_ERR_ARG, "null pointer");
   if (parts < 1 || parts > 64 || part < 0 || part >= parts) return fail(ZKHIP_ERR_ARG, "setup_slice: part must be in [0, parts), parts in [1, 64]");
-  if (opts && (opts->window < 0 || (opts->window > 0 && (opts->window < 4 || opts->window > 22))))
-    return fail(ZKHIP_ERR_ARG, "zkhip_key_opts.window must be 0 (automatic) or in [4, 22]");
+  { int rc_ = check_opts(opts); if (rc_ != ZKHIP_OK) return rc_; }
   SetupScalars sc;
   int rc = setup_scalars(cs, tau_m, alpha_m, beta_m, delta_m, domain_size, sc);
   if (rc != ZKHIP_OK) return rc;

@@ -63,6 +63,7 @@ int ensure_ctx(MsmCtx* cx, MsmLane& lane, size_t n, int table_c, int K, int naf,
 // the last accumulation launch of ps ran on cx (zkhip_last_accumulate_ms / _interval / _entries read it back)
 void note_last_acc(ProveState& ps, MsmCtx* cx) {
   ps.last_acc_ctx = cx; ps.last_accumulate_ms = cx->last_accumulate_ms;
+  ps.last_acc_ctx2 = nullptr;      // (a proof of two sequences names its second plan after this call)
   ps.last_acc_interval[0] = cx->last_acc_begin_ms; ps.last_acc_interval[1] = cx->last_acc_end_ms;
 }
 
@@ -537,6 +538,48 @@ int zkhip_internal_last_acc_path(int* out) {
   if (!cx) return ZKHIP_OK;
   const int rc = msm_last_acc_path(cx, out);
   return rc == ZKHIP_OK ? rc : ctx_fail(rc, cx);
+}
+
+// Test hook of the merged launch (msm.hip msm_launch_multi): up to four table-backed sets of one window through ONE launch sequence
+int zkhip_internal_msm_multi(const zkhip_bases* const* sets, const uint64_t* const* scalars, const size_t* n, int K, int montgomery, int model,
+                             int* acc_path, uint64_t* out_jac) {
+  if (!sets || !scalars || !n || !acc_path || !out_jac) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (K < 1 || K > 4 || (model != 0 && model != 1)) return fail(ZKHIP_ERR_ARG, "K in 1 .. 4, model 0 (XYZZ) or 1 (Edwards)");
+  for (int k = 0; k < K; k++) if (!sets[k] || (n[k] && !scalars[k])) return fail(ZKHIP_ERR_ARG, "null pointer");
+  const int dev = sets[0]->device, tc = sets[0]->table_c;
+  size_t max_n = 1, total = 0;
+  for (int k = 0; k < K; k++) {
+    const zkhip_bases* b = sets[k];
+    if (b->device != dev) return fail(ZKHIP_ERR_ARG, "the sets live on different devices");
+    if (!b->table_c || b->table_c != tc || b->table_naf) return fail(ZKHIP_ERR_ARG, "the sets must have one-level-per-window tables of one window");
+    if (n[k] > b->len) return fail(ZKHIP_ERR_ARG, "more terms than the set has bases");
+    if (model == 1 && n[k] && !b->d_edw) return fail(ZKHIP_ERR_STATE, "a set without an Edwards form cannot join an Edwards launch");
+    if (n[k] > max_n) max_n = n[k];
+    total += n[k];
+  }
+  BIND(sets[0]);
+  ProveState& ps = g.dev[dev].ps;
+  std::lock_guard<std::mutex> lk(g.dev[dev].mu);
+  Scratch sc;
+  MsmJob jobs[4];
+  for (int k = 0; k < K; k++) {
+    void* d = nullptr;
+    if (n[k]) {
+      API_HIP(sc.alloc(&d, n[k] * 48));
+      API_HIP(hipMemcpy(d, scalars[k], n[k] * 48, hipMemcpyHostToDevice));
+    }
+    jobs[k] = single_job(sets[k], 0, d, n[k], montgomery);
+    if (model == 0) jobs[k].edw = nullptr;
+  }
+  API_HIP(hipStreamSynchronize(0));     // the MSM streams are not ordered against the null stream
+  MsmCtx* cx = &ps.ctx[ZK_CTX_Z];
+  int rc = ensure_ctx(cx, ps.lane[ZK_CTX_Z], max_n, tc, K, 0, total ? total : 1);
+  if (rc != ZKHIP_OK) return rc;
+  if ((rc = msm_launch_multi(cx, K, jobs)) == ZKHIP_OK) rc = msm_finish_multi(cx, K, out_jac);
+  if (rc == ZKHIP_OK) rc = msm_last_acc_path(cx, acc_path);
+  if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+  note_last_acc(ps, cx); t_prove_dev = dev;
+  return ZKHIP_OK;
 }
 
 int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out) {

@@ -102,6 +102,15 @@ static void proof_jobs(const zkhip_crs* crs, const R1csDev* rd, const uint64_t* 
   const uint64_t *za = dz + a_lo * 6, *zl = dz + (rd->n_primary + 1 + l_lo) * 6, *h = (const uint64_t*)rd->bufA + h_lo * 6;
   jobs[0] = query_job(crs->A, za, crs->A->len, 1); jobs[1] = query_job(crs->B2, za, crs->A->len, 1); jobs[2] = query_job(crs->B1, za, crs->A->len, 1);
   jobs[3] = query_job(crs->H, h, crs->H->len, 2); jobs[4] = query_job(crs->L, zl, crs->L->len, 1);    // (h: the QAP map's output, packed device form)
+  // a key on the Edwards model: its four G1 jobs bring their Edwards tables (B-G2 has none)
+  if (crs->table_model) { jobs[0].edw = crs->A->d_edw; jobs[2].edw = crs->B1->d_edw; jobs[3].edw = crs->H->d_edw; jobs[4].edw = crs->L->d_edw; }
+}
+// a key on the Edwards model (prove_edwards): the four G1 jobs A, B-G1, H, L of one launch sequence; maxlen of their plan
+static void g1_jobs(const MsmJob jobs[5], MsmJob g1[4]) { g1[0] = jobs[0]; g1[1] = jobs[2]; g1[2] = jobs[3]; g1[3] = jobs[4]; }
+static size_t jobs_maxlen(const MsmJob* jobs, int K) {
+  size_t m = 1;
+  for (int k = 0; k < K; k++) if (jobs[k].n > m) m = jobs[k].n;
+  return m;
 }
 static size_t jobs_terms(const MsmJob* jobs, int K) {
   size_t t = 0;
@@ -213,10 +222,67 @@ static int prove_batched(ProofRun& p, size_t maxlen, bool chain) {
   note_last_acc(ps, cx);
   return ZKHIP_OK;
 }
+// A key on the Edwards model (zkhip_key_opts.table_model = 1): the four G1 MSMs - A, B-G1, H, L - are ONE launch sequence that adds on
+// G1's 2-isogenous Edwards curve (a K = 4 plan on the context of the batched proofs: k_accumulate_edw_multi), and B-G2, whose curve has no
+// such model, is a K = 1 XYZZ sequence on a context and lane of its own.  B-G2 needs only the assignment: it is enqueued behind the
+// upload (a chained proof: behind an event on the stream that carries it) and runs beside the QAP map; the G1 sequence follows the
+// map.  Two plans in one proof as in prove_split, and its rules: whatever was enqueued is collected on every exit, the first error is
+// reported.  Timings: ms[0] / ms[1] as in the other strategies (enqueueing times when chained; ms[1] includes enqueueing B-G2), the five
+// MSM slots the time from B-G2's launch to the collection of both sequences.
+static int prove_edwards(ProofRun& p, bool chain) {
+  ProveState& ps = p.ps;
+  MsmJob jg[4];
+  g1_jobs(p.jobs, jg);
+  const MsmJob& jb = p.jobs[1];
+  MsmCtx *cg = &ps.ctx[ZK_MSM_SLOTS], *cb = &ps.ctx[ZK_CTX_H];
+  int rc = ensure_ctx(cg, ps.lane[ZK_MSM_SLOTS], jobs_maxlen(jg, 4), p.tc, 4, 0, jobs_terms(jg, 4));
+  if (rc == ZKHIP_OK) rc = ensure_ctx(cb, ps.lane[ZK_CTX_H], jb.n ? jb.n : 1, p.tc, 1, 0, jobs_terms(&jb, 1), 0, ps.quad_below ? 1 : -1);
+  if (rc != ZKHIP_OK) return rc == ZKHIP_ERR_ARG ? ZK_PLAN_UNFIT : rc;
+  if (ps.quad_below) for (MsmCtx* cx : {cg, cb}) { cx->quad_below = ps.quad_below; cx->one_stream = 1; }
+  if (!ps.ev_up) API_HIP(hipEventCreateWithFlags(&ps.ev_up, hipEventDisableTiming));
+  hipStream_t qst = chain ? ps.lane[ZK_MSM_SLOTS].main : ps.st;
+  if (p.z_host) API_HIP(hipMemcpyAsync(ps.dz, p.z_host, p.rd->n_vars * 48, hipMemcpyHostToDevice, qst));
+  if (chain) {      // B-G2's stream follows the upload; the host does not wait
+    API_HIP(hipEventRecord(ps.ev_up, qst));
+    API_HIP(hipStreamWaitEvent(ps.lane[ZK_CTX_H].main, ps.ev_up, 0));
+  } else if (p.z_host) { API_HIP(hipEventRecord(ps.ev_st, qst)); API_HIP(zk_event_wait(ps.ev_st)); }
+  ps.ms[0] = ms_since(p.t0);
+  const auto tl0 = p.t0 = clk::now();
+  if ((rc = msm_launch_multi(cb, 1, &jb)) != ZKHIP_OK) return ctx_fail(rc, cb);
+  // from here on B-G2 is in flight: every exit collects it
+  bool g1_launched = false;
+  if ((rc = qap_h_dev(p.rd, p.dz, qst, t_err, sizeof t_err, p.d_z_app)) == ZKHIP_OK && !chain) {
+    hipError_t e = hipEventRecord(ps.ev_st, qst);
+    if (e == hipSuccess) e = zk_event_wait(ps.ev_st);
+    if (e != hipSuccess) { snprintf(t_err, sizeof t_err, "Edwards proof: %s", hipGetErrorString(e)); rc = ZKHIP_ERR_HIP; }
+  }
+  ps.ms[1] = ms_since(p.t0);
+  if (rc == ZKHIP_OK) {
+    if ((rc = msm_launch_multi(cg, 4, jg)) != ZKHIP_OK) (void)ctx_fail(rc, cg);
+    else g1_launched = true;
+  }
+  const bool g1_edw = g1_launched && cg->win_edw;      // (what the launch itself decided: a silent XYZZ launch reads 0)
+  uint64_t sg[4 * 36];
+  const int rc_b = msm_finish_multi(cb, 1, p.sums + 36);
+  const int rc_g = g1_launched ? msm_finish_multi(cg, 4, sg) : ZKHIP_OK;
+  if (rc == ZKHIP_OK && rc_g != ZKHIP_OK) {
+    snprintf(t_err, sizeof t_err, "%s%s", cg->errbuf, chain ? " [chained proof: this stream also carried the upload of the assignment and the QAP map]" : "");
+    rc = rc_g;
+  }
+  if (rc == ZKHIP_OK && rc_b != ZKHIP_OK) rc = ctx_fail(rc_b, cb);
+  if (rc != ZKHIP_OK) { (void)hipStreamSynchronize(qst); return rc; }
+  memcpy(p.sums, sg, 36 * 8); memcpy(p.sums + 72, sg + 36, 3 * 36 * 8);      // A | (B-G2) | B-G1, H, L
+  for (int j = 0; j < 5; j++) ps.ms[2 + j] = ms_since(tl0);
+  note_last_acc(ps, cg);                          // (two accumulation launches: the sum of their times, the entries of both)
+  ps.last_accumulate_ms += cb->last_accumulate_ms; ps.last_acc_ctx2 = cb;
+  ps.edw_last = g1_edw;
+  return ZKHIP_OK;
+}
 // One launch sequence per MSM, several in flight: while MSM j reduces its buckets (latency-bound, few lanes), MSM j+1 accumulates.
 // Large circuits keep two contexts (each holds ~1.3 GB of work space at 2^20); small ones (every phase is latency-bound and the
-// chip is mostly idle) run all five MSMs side by side.  These launches take only the geometry of a job: plans of K = 1 without a
-// bound on the terms, no finite-bases bound and no Edwards table (msm_launch's defaults).
+// chip is mostly idle) run all five MSMs side by side.  These launches take only the geometry of a job - plans of K = 1 without a
+// bound on the terms, no finite-bases bound - and the job's Edwards table, which only a key on the Edwards model brings: its G1 MSMs
+// then go through the single-MSM Edwards kernels, B-G2 as ever.
 static int prove_separate(ProofRun& p, size_t maxlen) {
   ProveState& ps = p.ps;
   const int nctx = (maxlen <= ((size_t)1 << 18)) ? 5 : 2;
@@ -225,6 +291,7 @@ static int prove_separate(ProofRun& p, size_t maxlen) {
     if (ps.quad_below) { ps.ctx[k].quad_below = ps.quad_below; ps.ctx[k].one_stream = 1; }
   }
   clk::time_point tl[5];
+  bool g1_edw = p.jobs[0].edw || p.jobs[2].edw || p.jobs[3].edw || p.jobs[4].edw;      // then: every G1 launch that had terms accumulated on the Edwards curve
   for (int j = 0; j < 5 + nctx; j++) {          // launch j, after collecting launch j - nctx from the same context
     MsmCtx* cx = &ps.ctx[j % nctx];
     int rc;
@@ -236,9 +303,11 @@ static int prove_separate(ProofRun& p, size_t maxlen) {
     if (j >= 5) continue;
     const MsmJob& job = p.jobs[j];
     tl[j] = clk::now();
-    rc = msm_launch(cx, job.bases, job.inf_flags, job.scalars, job.n, job.scalars_mode, job.table_stride);
+    rc = msm_launch(cx, job.bases, job.inf_flags, job.scalars, job.n, job.scalars_mode, job.table_stride, job.edw);
     if (rc != ZKHIP_OK) return ctx_fail(rc, cx);
+    if (j != 1 && job.n && !cx->win_edw) g1_edw = false;
   }
+  ps.edw_last = g1_edw;
   note_last_acc(ps, &ps.ctx[4 % nctx]);
   return ZKHIP_OK;
 }
@@ -278,14 +347,23 @@ static int prove_partial(ProveState& ps, const zkhip_crs* crs, R1csDev* rd, cons
   // enqueueing, not execution.
   // (only when the launch sequence's context will be used as it stands: its lane outlives a plan made again, so the clause guards no stream - it decides which proofs report enqueueing times, never a prover's first)
   static const int chain_env = getenv("ZKHIP_STREAM_CHAIN") ? atoi(getenv("ZKHIP_STREAM_CHAIN")) : 1;
-  const bool chain = chain_env && (ps.quad_below || chain_env == 2) && tc > 0 && crs->batch_msms &&
-                     ctx_reusable(&ps.ctx[ZK_MSM_SLOTS], maxlen, tc, 5, naf, jobs_terms(p.jobs, 5));
+  // (a key on the Edwards model: BOTH contexts of prove_edwards as they stand)
+  const bool edw_key = crs->table_model == 1 && tc > 0;
+  MsmJob jg[4];
+  g1_jobs(p.jobs, jg);
+  const bool ctx_ready = !edw_key ? ctx_reusable(&ps.ctx[ZK_MSM_SLOTS], maxlen, tc, 5, naf, jobs_terms(p.jobs, 5))
+                                  : ctx_reusable(&ps.ctx[ZK_MSM_SLOTS], jobs_maxlen(jg, 4), tc, 4, 0, jobs_terms(jg, 4)) &&
+                                        ctx_reusable(&ps.ctx[ZK_CTX_H], a_len ? a_len : 1, tc, 1, 0, jobs_terms(&p.jobs[1], 1));
+  const bool chain = chain_env && (ps.quad_below || chain_env == 2) && tc > 0 && crs->batch_msms && ctx_ready;
   ps.chained_last = chain;
   ps.split_last = false;
+  ps.edw_last = false;
   ps.last_acc_ctx2 = nullptr;
   int rc;
+  if (edw_key && crs->batch_msms)      // (ZK_PLAN_UNFIT: nothing enqueued, never a chained proof - the XYZZ strategies decide)
+    if ((rc = prove_edwards(p, chain)) != ZK_PLAN_UNFIT) return rc;
   const int split_env = g_prove_split.load();
-  if (split_env && !chain && !ps.quad_below && tc > 0 && crs->batch_msms && h_len > 0 && a_len > 0)
+  if (split_env && !edw_key && !chain && !ps.quad_below && tc > 0 && crs->batch_msms && h_len > 0 && a_len > 0)
     if ((rc = prove_split(p, split_env != 2)) != ZK_PLAN_UNFIT) return rc;
   if ((rc = prove_upload_and_map(p, chain ? ps.lane[ZK_MSM_SLOTS].main : ps.st, chain)) != ZKHIP_OK) return rc;
   if (tc > 0 && crs->batch_msms)
@@ -605,6 +683,7 @@ int zkhip_prover_create_streams(zkhip_prover* p, int which) {
   else {
     API_HIP(msm_lane_create_side(&ps.lane[ZK_MSM_SLOTS]));
     if (!ps.st) API_HIP(hipStreamCreateWithFlags(&ps.st, hipStreamNonBlocking));
+    if (p->crs->table_model) API_HIP(msm_lane_create_main(&ps.lane[ZK_CTX_H]));      // (a key on the Edwards model: B-G2's sequence, behind every instance's G1 stream)
   }
   return ZKHIP_OK;
 }
@@ -652,6 +731,19 @@ int zkhip_last_prove_split(void) {
   if (dev < 0) return 0;
   std::lock_guard<std::mutex> lk(g.dev[dev].mu);
   return g.dev[dev].ps.split_last ? 1 : 0;
+}
+
+int zkhip_prover_last_table_model(zkhip_prover* p, int* out) {
+  if (!p || !out) return fail(ZKHIP_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(p->mu);
+  *out = p->ps.edw_last ? 1 : 0;
+  return ZKHIP_OK;
+}
+int zkhip_last_prove_table_model(void) {
+  const int dev = t_prove_dev >= 0 ? t_prove_dev : cur_dev();
+  if (dev < 0) return 0;
+  std::lock_guard<std::mutex> lk(g.dev[dev].mu);
+  return g.dev[dev].ps.edw_last ? 1 : 0;
 }
 
 // Host only (no device needed): the prover's tail on the paths a healthy proof never takes.

@@ -23,7 +23,8 @@ struct MsmJob {
   size_t n_finite;               // upper bound on the bases of this job that are not the point at infinity (0: unknown, use n):
                                  // sizes the slices of the accumulation to the entries that can actually occur
   const EdwPacked* edw = nullptr;  // the same table in precomputed Edwards form (msm_table_edw), or null: a single MSM over a one-level-
-                                   // per-window table then accumulates on G1's 2-isogenous Edwards curve (ec_edw.cuh)
+                                   // per-window table then accumulates on G1's 2-isogenous Edwards curve (ec_edw.cuh), and so do up to
+                                   // four MSMs of a merged plan when every job that has terms brings one (msm_launch_multi)
 };
 // the terms of a job that can produce an entry: a base at infinity never does (plans are sized by this, launches counted by it)
 static inline size_t msm_job_terms(const MsmJob& j) { return (j.n_finite && j.n_finite < j.n) ? j.n_finite : j.n; }
@@ -66,8 +67,8 @@ struct MsmCtx {      // all zeros: no plan
   size_t hist_len;
   uint32_t *counts, *offsets, *block_tot, *entries;
   uint32_t* goff;       // slice weights in front of every bucket (nb + 1 values): see k_accumulate
-  uint32_t *order, *ord_hist;   // Edwards launches (k_bucket_order): the bucket indices by count, descending (nb values), and the
-                                // counting sort's histogram [ZK_LOCK_KEYS][blocks]; null in plans that never serve one
+  uint32_t *order, *ord_hist;   // single Edwards launches (k_bucket_order): the bucket indices by count, descending (nb values), and the
+                                // counting sort's histogram [ZK_LOCK_KEYS][blocks]; null in plans of K > 1 (their Edwards launches are sliced only)
   uint32_t lock_min_live;       // non-empty buckets a launch needs for the lockstep route: two waves for every SIMD of the chip
   uint2* fix_list;      // (first, last) F slot of the buckets cut into more than four F pieces (k_accumulate -> k_fixup_fold)
   uint2* fix_short;     // (first F slot, number of F pieces) of the buckets with two to four (k_accumulate -> k_fixup_fold)
@@ -106,7 +107,8 @@ int msm_forced_aff_levels();
 // A/B and test knob of the lockstep route of the Edwards accumulation: mode 0 off, 1 on, -1 the environment (ZKHIP_LOCKSTEP);
 // min_buckets: the non-empty buckets a launch needs to take it (-1: the chip's own figure)
 void msm_force_lockstep(int mode, int min_buckets);
-// the route the plan's last launch took, read back from the device: 1 lockstep, 0 sliced, -1 not an Edwards launch
+// the route the plan's last launch took, read back from the device: 1 lockstep, 0 sliced (always, for a merged Edwards launch of
+// several jobs), -1 not an Edwards launch
 int msm_last_acc_path(MsmCtx* ctx, int* out);
 // total_terms: upper bound on the terms (finite bases) of all K jobs of one launch together; 0 = K * max_n
 // lane: the caller's, with its main stream and its events made; the plan refers to it and never creates or destroys a part of it

@@ -460,7 +460,9 @@ __device__ __forceinline__ uint32_t slice_weight(uint32_t G, uint32_t T, uint32_
 // entry k is point k, never negated; a point may be the level encoding of infinity (skipped).
 // EDW: bp.p[0] is a table of precomputed Edwards points (ec_edw.cuh) and the slots receive Edwards points (X | Y | Z | T in the
 // X | Y | ZZ | ZZZ words; the stitching and the reduction go on in that model): every run starts at the identity, so every entry is one addition.
-// Single MSMs only (NJ = 1), never dense.  Two kernels share this body: k_accumulate<NJ> (XYZZ) and k_accumulate_edw.
+// Never dense.  NJ = 1: a single MSM; NJ = 4: the four G1 MSMs of a proof in one launch - bp.p[k] is job k's Edwards table, and a run
+// takes its table from its bucket's window where it is opened (lanes of one wave are in different jobs: the lane carries the table
+// until its next run).  Three kernels share this body: k_accumulate<NJ> (XYZZ), k_accumulate_edw and k_accumulate_edw_multi.
 #define ZK_ACC_PARAMS                                                                                                                   \
   BasePtrs bp, int bshift, const uint32_t* __restrict__ entries, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,   \
       const uint32_t* __restrict__ goff, uint32_t nb, uint32_t S_host, int tight, uint32_t T, uint32_t* __restrict__ slots, uint32_t stride,      \
@@ -469,7 +471,7 @@ __device__ __forceinline__ uint32_t slice_weight(uint32_t G, uint32_t T, uint32_
       uint32_t* prio_board /* null, or one word per hardware wave slot */, uint32_t prio_tag
 template <int NJ, bool EDW>
 __device__ __forceinline__ void accumulate_impl(ZK_ACC_PARAMS) {
-  static_assert(!EDW || NJ == 1, "the Edwards accumulation serves single MSMs");
+  static_assert(!EDW || NJ == 1 || NJ == 4, "the Edwards accumulation serves single MSMs and the four G1 MSMs of a proof");
   constexpr uint32_t wf = EDW ? ZK_W_NEXT : ZK_W_FIRST;
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t dbg_t0 = dbg_times ? wall_clock64() : 0;
@@ -577,6 +579,7 @@ __device__ __forceinline__ void accumulate_impl(ZK_ACC_PARAMS) {
         bend = offsets[b] + counts[b];
         const bool starts = (k == offsets[b]), ends = (bend <= pos1);
         acc.voff = ((starts && ends) ? b : (!starts ? nb + t : nb + T + t)) * ZK_SLOT_PITCH;
+        if constexpr (NJ > 1) etab = reinterpret_cast<const EdwPacked*>(base_of<NJ>(bp, b >> bshift));
         edw_set_identity(xs, zz, zzz, ty);
         inf = false;
       }
@@ -654,6 +657,12 @@ __global__ void __launch_bounds__(256, 2) k_accumulate(ZK_ACC_PARAMS) {
 __global__ void __launch_bounds__(256, 2) k_accumulate_edw(ZK_ACC_PARAMS) {
   if (fix_cnt[2] == 1u) return;
   accumulate_impl<1, true>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
+                           dbg_times, prio_mode, prio_board, prio_tag);
+}
+// Merged Edwards launches (msm_launch_multi: up to four G1 jobs, a bucket window each) take the sliced route only - a proof's scalars
+// are boolean-heavy and never pass the lockstep cap -, so nothing writes lock_ok there but the launch's memset: it reads 0.
+__global__ void __launch_bounds__(256, 2) k_accumulate_edw_multi(ZK_ACC_PARAMS) {
+  accumulate_impl<4, true>(bp, bshift, entries, offsets, counts, goff, nb, S_host, tight, T, slots, stride, fix_cnt, fix_short, fix_long,
                            dbg_times, prio_mode, prio_board, prio_tag);
 }
 
@@ -1691,7 +1700,7 @@ static int lockstep_mode() {
 // back here and nowhere else: a test hook, synchronises the device
 int msm_last_acc_path(MsmCtx* ctx, int* out) {
   *out = -1;
-  if (!ctx->planned || !ctx->win_edw || !ctx->order) return ZKHIP_OK;
+  if (!ctx->planned || !ctx->win_edw) return ZKHIP_OK;      // (a merged Edwards launch has no lockstep route: its word reads 0)
   uint32_t v = 0;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(&v, ctx->block_tot + 2, 4, hipMemcpyDeviceToHost));
@@ -2005,7 +2014,8 @@ static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
   // slice weights: goff = exclusive scan of (8 count - 7) over the non-empty buckets of the list k_accumulate sums (nb + 1 values)
   hipLaunchKernelGGL(k_slice_weights, dim3(nblk(nb + 1, 256)), dim3(256), 0, st, lp.cur_cnt, ctx->goff, nb, lp.wf);
   enqueue_scan(st, ctx->goff, ctx->goff, ctx->block_tot, nb + 1);
-  if (lp.edw) {      // the lockstep route's bucket order and its go / no-go word, block_tot[2]
+  const bool lock_route = lp.edw && ctx->K == 1;      // (merged Edwards launches, K > 1, are sliced only: no order, lock_ok = 0)
+  if (lock_route) {      // the lockstep route's bucket order and its go / no-go word, block_tot[2]
     const unsigned ob = nblk(nb, 1024);
     const int lock_on = lockstep_mode();
     const uint32_t min_live = g_lock_min_live >= 0 ? (uint32_t)g_lock_min_live : ctx->lock_min_live;
@@ -2013,7 +2023,8 @@ static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
     enqueue_scan(st, ctx->ord_hist, ctx->ord_hist, ctx->block_tot, (size_t)ZK_LOCK_KEYS * ob);
     hipLaunchKernelGGL(k_bucket_order<1>, dim3(ob), dim3(256), 0, st, lp.cur_cnt, (uint32_t)nb, ctx->ord_hist, ctx->order, ctx->block_tot + 2, min_live, lock_on);
   }
-  HIP_TRY(hipMemsetAsync(ctx->block_tot, 0, 8, st));   // the lengths of the two stitching lists: the launch's scans are done (enqueue_scan)
+  // the lengths of the two stitching lists: the launch's scans are done (enqueue_scan); an Edwards launch without the lockstep route clears lock_ok too
+  HIP_TRY(hipMemsetAsync(ctx->block_tot, 0, (lp.edw && !lock_route) ? 12 : 8, st));
   size_t n_jobs = 0;
   for (int k = 0; k < lp.K; k++) n_jobs += lp.jobs[k].n ? 1 : 0;
   lp.S_run = (uint32_t)plan::slice_run(lp.m_cur, slice_target(), ctx->one_stream ? (size_t)env_int("ZKHIP_STREAM_SLICE_MULT", 2, 1, 16) : 1, ctx->merged ? ctx->B * (n_jobs ? n_jobs : 1) : nb, ctx->T);
@@ -2033,9 +2044,9 @@ static int stage_accumulate(MsmCtx* ctx, Launch& lp) {
   if (!dense) HIP_TRY(hipEventRecord(ctx->lane->ev_acc0, st));
   static const int acc_prio = env_int("ZKHIP_ACC_PRIO", 1, 0, 2);      // 2: by quarters of the slice only (no board)
   const uint32_t prio_tag = (++ctx->prio_seq & 0x7fffu) + 1u;     // (see k_accumulate: the wave that is behind asks for priority; 0 = the arbiter's own order)
-  if (lp.edw)
+  if (lock_route)
     hipLaunchKernelGGL(k_accumulate_edw_lock, dim3(nblk(nb, 256)), dim3(256), 0, st, lp.jobs[0].edw, ctx->entries, lp.cur_off, lp.cur_cnt, ctx->order, (uint32_t)nb, ctx->buckets, ctx->slot_stride, ctx->block_tot + 2);
-  const auto accumulate = lp.edw ? k_accumulate_edw : (ctx->K == 1 || dense) ? k_accumulate<1> : k_accumulate<MSM_MAX_JOBS>;
+  const auto accumulate = lp.edw ? (lock_route ? k_accumulate_edw : k_accumulate_edw_multi) : (ctx->K == 1 || dense) ? k_accumulate<1> : k_accumulate<MSM_MAX_JOBS>;
   hipLaunchKernelGGL(accumulate, dim3(nblk(lp.T_run, 256)), dim3(256), 0, st, lp.bp, lp.bshift, dense ? (const uint32_t*)nullptr : ctx->entries, lp.cur_off, lp.cur_cnt, ctx->goff, (uint32_t)nb,
                      lp.S_run, lp.tight, lp.T_run, ctx->buckets, ctx->slot_stride, ctx->block_tot + 0, ctx->fix_short, ctx->fix_list, ctx->dbg_times, acc_prio, (acc_prio == 1 && !ctx->one_stream) ? ctx->prio_board : (uint32_t*)nullptr, prio_tag);
   HIP_TRY(hipEventRecord(ctx->lane->ev_acc1, st));
@@ -2155,16 +2166,18 @@ int msm_launch_multi(MsmCtx* ctx, int K, const MsmJob* jobs) {
   ctx->pending_n = n_tot;
   ctx->win_edw = false;
   if (n_tot == 0) { ctx->pending = true; return ZKHIP_OK; }
-  // the Edwards accumulation (ec_edw.cuh): a single MSM over a one-level-per-window table that has its Edwards form, no batched-affine
-  // levels in front.  The digits are XYZZ's (the table holds chi of the HALVED points); the slots, the stitching and the bucket
+  // the Edwards accumulation (ec_edw.cuh): MSMs over one-level-per-window tables that have their Edwards form, no batched-affine
+  // levels in front - a single MSM, or up to four in a merged plan when EVERY job that has terms brings its Edwards table (a mixed
+  // set of jobs runs as XYZZ).  The digits are XYZZ's (the table holds chi of the HALVED points); the slots, the stitching and the bucket
   // reduction hold Edwards points (the k_..._edw kernels), and the host maps the window results back (win_edw: edw_abi_to_jac).
-  lp.edw = merged == 1 && K == 1 && ctx->K == 1 && ctx->aff_levels == 0 && jobs[0].edw != nullptr;
+  lp.edw = merged == 1 && ctx->K <= 4 && ctx->aff_levels == 0;
+  for (int k = 0; k < K; k++) if (jobs[k].n && !jobs[k].edw) lp.edw = false;
   lp.wf = lp.edw ? ZK_W_NEXT : ZK_W_FIRST;
   lp.red = red_kernels(lp.edw);
   lp.nb = ctx->B * ctx->W;
   lp.bshift = merged ? c - 1 : 31;
   for (int k = 0; k < MSM_MAX_JOBS; k++) lp.bp.p[k] = jobs[k < K ? k : 0].bases;
-  if (lp.edw) lp.bp.p[0] = reinterpret_cast<const AffPacked*>(jobs[0].edw);     // (k_accumulate_edw reads it as EdwPacked)
+  if (lp.edw) for (int k = 0; k < K; k++) lp.bp.p[k] = reinterpret_cast<const AffPacked*>(jobs[k].edw);     // (k_accumulate_edw[_multi] read them as EdwPacked)
   lp.cur_off = ctx->offsets;
   lp.cur_cnt = ctx->counts;
   lp.m_cur = (size_t)Wd * (n_eff ? n_eff : 1);       // entries that can occur: a base at infinity never produces one
@@ -2216,7 +2229,7 @@ int msm_finish_multi(MsmCtx* ctx, int K, uint64_t* out_jac) {
   }
   for (int k = 0; k < K; k++) {
     HJac q = HJac::infinity();
-    if (ctx->pending_n && ctx->win_edw) edw_abi_to_jac(ctx->win_host + (size_t)k * 48, q);      // (an Edwards launch: K = 1, merged = 1)
+    if (ctx->pending_n && ctx->win_edw) edw_abi_to_jac(ctx->win_host + (size_t)k * 48, q);      // (an Edwards launch: merged = 1, psi once per job)
     else if (ctx->pending_n) xyzz_abi_to_jac(ctx->win_host + (size_t)k * 48, q);    // one bucket window per job: nothing to combine
     if (ctx->pending_n && ctx->merged == 2) {                                  // odd digits: sum (2 b + 1) S_b = 2 F - sum S_b
       HJac tot;

@@ -266,13 +266,26 @@ def is_transient_failure(e):
     return getattr(e, "code", None) in (-2, -3, -4)                # ZKHIP_ERR_NO_DEVICE, ZKHIP_ERR_HIP, ZKHIP_ERR_STATE
 
 
+def server_key_opts(key_table_model="xyzz"):
+    """The options of the server's key (zkhip_key_opts).  xyzz (default): every-bit-position tables with NAF scalars - a server proves a
+    stream of batches, the larger kind of window table pays - unless ZKHIP_TABLE_NAF is set, which then decides.
+    edwards: one-level tables that also have their Edwards form; the G1 MSMs of a proof add on G1's 2-isogenous Edwards curve."""
+    from . import zkhip
+    if key_table_model == "edwards":
+        return zkhip.key_opts(table_naf=False, table_model="edwards")
+    if key_table_model != "xyzz":
+        raise ValueError("key table model: xyzz or edwards")
+    return zkhip.key_opts(table_naf=True if os.environ.get("ZKHIP_TABLE_NAF") is None else None)
+
+
 class GpuProver:
     """The wrapping prover behind the service: circuit, keypair (file or fresh setup), HBM-resident key, streaming pipeline."""
     snark_name = "GROTH16"
 
     def __init__(self, keypair_file=None, device=0, gpu_slots=32, witness_workers=10, gpu_witness=False, devices=None, hybrid_witness=False,
-                 screen_nested=False, screen_combined=False):
-        """screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier, the CHECKED route: every point's
+                 screen_nested=False, screen_combined=False, key_table_model="xyzz"):
+        """key_table_model: "xyzz" (default) or "edwards" - the kind of tables the key gets (server_key_opts).
+        screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier, the CHECKED route: every point's
         encoding, curve and order, every input's range) before a batch is popped, so that an invalid or malformed one costs no slot of
         a wrapping proof (`screen_status` / `screen`; off: the service never asks).
         screen_combined (meaningful only with screen_nested; default off): `screen_status` first asks the checked handle ONE
@@ -305,9 +318,8 @@ class GpuProver:
         self.vk = self.kp.vk()
         if self.vk["ABC"].shape[0] != self.agg.num_primary_inputs() + 1:      # the server's "invalid VK" check (:490, :504)
             raise ValueError("invalid VK")
-        # a server proves a stream of batches: the larger kind of window table pays.  The option travels with
-        # THIS key (zkhip_key_opts), not with the process: another key loaded on another thread keeps its own.
-        opts = zkhip.key_opts(table_naf=True if os.environ.get("ZKHIP_TABLE_NAF") is None else None)
+        # The options travel with THIS key (zkhip_key_opts), not with the process: another key loaded on another thread keeps its own.
+        opts = server_key_opts(key_table_model)
         if len(devices) > 1:
             self.crs = None                               # (the dispatcher uploads a copy of the key to every entry of the list)
             self.pipe = zkhip.AggregatorDispatcher(self.agg, self.kp, devices, opts, gpu_slots=gpu_slots, witness_workers=witness_workers,
@@ -636,7 +648,8 @@ class AggregatorClient:
                 "nested_parameters": [bytes(p).hex() for p in a.nested_parameters]}
 
 
-def main(argv=None):
+def main(argv=None, parse_only=False):
+    """parse_only: return the parsed arguments without starting anything (no device needed)"""
     import argparse
     ap = argparse.ArgumentParser(description="aggregator_server on an MI355X (reference aggregator_server.cpp:418-527)")
     ap.add_argument("--keypair", "-k", default=os.path.join(os.environ.get("ZETH_SETUP_DIR", os.path.expanduser("~/zeth_setup")), "zecale_keypair.bin"),
@@ -653,10 +666,15 @@ def main(argv=None):
                                                                  "an invalid one is dropped instead of taking a slot of a wrapping proof")
     ap.add_argument("--screen-combined", action="store_true", help="with --screen-nested: first ONE random-combination check for the whole pool, "
                                                                    "the per-proof batch only when it fails (pays where pools are mostly valid)")
+    ap.add_argument("--key-table-model", choices=("xyzz", "edwards"), default="xyzz",
+                    help="xyzz (default): every-bit-position tables, NAF scalars; edwards: one-level tables with their Edwards form - the G1 MSMs "
+                         "of a proof add on G1's 2-isogenous Edwards curve (1.5 x the one-level tables' memory on top)")
     args = ap.parse_args(argv)
+    if parse_only:
+        return args
     print("[INFO] Init params of both curves")
     prover = GpuProver(args.keypair, device=args.device, gpu_witness=args.gpu_witness, hybrid_witness=args.hybrid_witness, screen_nested=args.screen_nested,
-                       screen_combined=args.screen_combined,
+                       screen_combined=args.screen_combined, key_table_model=args.key_table_model,
                        devices=[int(x) for x in args.devices.split(",")] if args.devices else None)
     print("[INFO] Circuit has %d constraints" % prover.agg.num_constraints)
     print("[INFO] Setup successful, starting the server...")

@@ -41,6 +41,7 @@ EXPORTS = [
     "zkhip_aggregator_pipeline_register_app", "zkhip_aggregator_pipeline_app_hits", "zkhip_dispatcher_register_app", "zkhip_device_copy_out", "zkhip_measure_ntt", "zkhip_key_partition", "zkhip_prover_timings_chained",
     "zkhip_verifier_new", "zkhip_verifier_num_inputs", "zkhip_verifier_verify_batch", "zkhip_verifier_free", "zkhip_internal_fq6_selftest", "zkhip_internal_pairing_product", "zkhip_internal_set_lockstep", "zkhip_internal_last_acc_path", "zkhip_internal_msm_tail",
     "zkhip_internal_set_msm_stream_layout",
+    "zkhip_crs_table_model", "zkhip_prover_last_table_model", "zkhip_last_prove_table_model", "zkhip_internal_msm_multi",
     "zkhip_verifier_new_checked", "zkhip_verifier_verify_batch_checked", "zkhip_bw6_761_point_check", "zkhip_groth16_verify_checked",
     "zkhip_nested_verifier_new", "zkhip_nested_verifier_num_inputs", "zkhip_nested_verifier_verify_batch", "zkhip_nested_verifier_last_fallbacks",
     "zkhip_nested_verifier_free", "zkhip_internal_fq12_selftest", "zkhip_internal_nested_pairing_product",
@@ -70,13 +71,20 @@ class R1csDesc(ctypes.Structure):
 
 class KeyOpts(ctypes.Structure):
     """zkhip_key_opts: the options of a proving key / base set, carried by the handle (include/zkhip.h)."""
-    _fields_ = [("precompute", ctypes.c_int), ("table_naf", ctypes.c_int), ("window", ctypes.c_int), ("batch_msms", ctypes.c_int)]
+    _fields_ = [("precompute", ctypes.c_int), ("table_naf", ctypes.c_int), ("window", ctypes.c_int), ("batch_msms", ctypes.c_int),
+                ("table_model", ctypes.c_int)]
 
 
-def key_opts(precompute=None, table_naf=None, window=0, batch_msms=None):
-    """None = the process-wide default (the deprecated zkhip_set_* switches), True / False = this key's own choice."""
+TABLE_MODELS = {"xyzz": 0, "edwards": 1}
+
+
+def key_opts(precompute=None, table_naf=None, window=0, batch_msms=None, table_model=None):
+    """None = the process-wide default (the deprecated zkhip_set_* switches), True / False = this key's own choice.
+    table_model: None / 0 / "xyzz" = XYZZ (default); 1 / "edwards" = the key's G1 query vectors also get Edwards tables and the G1 MSMs
+    of its proofs add in that model (needs tables, one level per window: include/zkhip.h)."""
     t = lambda v: -1 if v is None else int(bool(v))
-    return KeyOpts(t(precompute), t(table_naf), int(window or 0), t(batch_msms))
+    model = 0 if table_model is None else TABLE_MODELS[table_model] if isinstance(table_model, str) else int(table_model)
+    return KeyOpts(t(precompute), t(table_naf), int(window or 0), t(batch_msms), model)
 
 
 class CrsDesc(ctypes.Structure):
@@ -596,6 +604,13 @@ class Crs:
     def table_kind(self):
         """0: plain key, 1: one table level per window, 2: every bit position (scalars in non-adjacent form)."""
         return load().zkhip_crs_table_kind(self.handle)
+
+    @property
+    def table_model(self):
+        """1: the key's G1 MSMs add on G1's 2-isogenous Edwards curve (key_opts(table_model=1) took effect), 0: XYZZ."""
+        lib = load()
+        lib.zkhip_crs_table_model.argtypes = [ctypes.c_void_p]
+        return lib.zkhip_crs_table_model(self.handle)
 
     def finite_terms(self):
         """Bases of A, B-G2, B-G1, H, L that are not the point at infinity (the terms an MSM over the key can have)."""
@@ -1425,6 +1440,14 @@ class Prover:
         _check(load().zkhip_prover_last_accumulate_entries(self.handle, ctypes.byref(out)))
         return int(out.value)
 
+    def last_table_model(self):
+        """1: the G1 MSMs of this instance's last proof accumulated on the Edwards curve, 0: in XYZZ (zkhip_prover_last_table_model)."""
+        out = ctypes.c_int(0)
+        lib = load()
+        lib.zkhip_prover_last_table_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+        _check(lib.zkhip_prover_last_table_model(self.handle, ctypes.byref(out)))
+        return int(out.value)
+
     def timings(self):
         t = (ctypes.c_double * 8)()
         _check(load().zkhip_prover_timings(self.handle, t))
@@ -1726,6 +1749,11 @@ def last_prove_split():
     return bool(load().zkhip_last_prove_split())
 
 
+def last_prove_table_model():
+    """1: the G1 MSMs of the last proof of the plain entry points accumulated on the Edwards curve (zkhip_last_prove_table_model)."""
+    return int(load().zkhip_last_prove_table_model())
+
+
 def jac_to_affine(jac):
     j = np.ascontiguousarray(jac, dtype=np.uint64)
     out = np.zeros(24, dtype=np.uint64)
@@ -1767,6 +1795,24 @@ def last_acc_path():
     out = ctypes.c_int(-1)
     _check(load().zkhip_internal_last_acc_path(ctypes.byref(out)))
     return int(out.value)
+
+
+def msm_multi(sets, scalars, model, montgomery=False):
+    """Test hook zkhip_internal_msm_multi: len(sets) <= 4 table-backed Bases of one window, job k over the first len(scalars[k]) bases of
+    sets[k], through ONE launch sequence.  model 0 XYZZ, 1 Edwards.  Returns (K x 36 Jacobian limbs, acc_path)."""
+    K = len(sets)
+    sc = [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 6) for s in scalars]
+    assert len(sc) == K
+    hs = (ctypes.c_void_p * K)(*[b.handle for b in sets])
+    ps = (ctypes.c_void_p * K)(*[s.ctypes.data if s.size else None for s in sc])
+    ns = (ctypes.c_size_t * K)(*[s.shape[0] for s in sc])
+    out = np.zeros((K, 36), dtype=np.uint64)
+    path = ctypes.c_int(-2)
+    lib = load()
+    lib.zkhip_internal_msm_multi.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), c_u64p_t]
+    _check(lib.zkhip_internal_msm_multi(hs, ps, ns, K, int(montgomery), int(model), ctypes.byref(path), _p(out)))
+    return out, int(path.value)
 
 
 def msm_tail(items_affine, W, lo_bits, edw=False, total=False):
