@@ -30,6 +30,42 @@ inline void zk_check(int rc, const char* what) {
     throw std::runtime_error(std::string(what) + ": " + zkhip_strerror(rc) + " (" + zkhip_last_error() + ")");
 }
 
+// zkhip_crs_check on a key as it comes through the seam - a libsnark key from libzeth's setup or an MPC, turned into limb arrays -
+// BEFORE hip_proving_key uploads it: every point's encoding, curve and order, the pair relations (beta, delta, the B queries) and,
+// with cs, the key's structure against that constraint system.  The verdict is report.ok; key_report_message names what was refused.
+// Throws only when the check could not run.  host: zkhip_crs_check_host, no device.
+inline zkhip_key_report check_key(const zkhip_crs_desc& pk, const zkhip_r1cs_desc* cs = nullptr, const uint64_t* vk_abc = nullptr, bool host = false) {
+  zkhip_key_report rep;
+  if (host) zk_check(zkhip_crs_check_host(&pk, vk_abc, cs, nullptr, &rep), "zkhip_crs_check_host");
+  else zk_check(zkhip_crs_check(&pk, vk_abc, cs, nullptr, &rep), "zkhip_crs_check");
+  return rep;
+}
+inline zkhip_key_report check_key(const zkhip_crs_desc& pk, const zkhip_r1cs_desc& cs, const uint64_t* vk_abc = nullptr, bool host = false) {
+  return check_key(pk, &cs, vk_abc, host);
+}
+inline std::string key_report_message(const zkhip_key_report& rep) {
+  static const char* const element[ZKHIP_KEY_ELEMENTS] = {"alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2", "a_query", "b_g2_query",
+                                                          "b_g1_query", "h_query", "l_query", "vk_abc"};
+  static const char* const code[5] = {"fine", "rejected", "ENCODING", "OFF_CURVE", "NOT_ORDER_R"};
+  static const char* const pair[3] = {"beta_g1/beta_g2", "delta_g1/delta_g2", "b_g1_query/b_g2_query"};
+  if (rep.ok) return "key check: ok";
+  std::string out = "key check:";
+  for (int k = 0; k < ZKHIP_KEY_ELEMENTS; k++) {
+    const int c = rep.e[k].first_code;
+    if (rep.e[k].first_refused != (size_t)-1)
+      out += std::string(" ") + element[k] + "[" + std::to_string(rep.e[k].first_refused) + "]: " + code[c >= 0 && c <= 4 ? c : 0] + ";";
+  }
+  for (int b = 0; b < 3; b++) {
+    if (rep.pairs >> b & 1) out += std::string(" ") + pair[b] + ": not the same multiple of their generators;";
+    else if (!(rep.pairs_evaluated >> b & 1)) out += std::string(" ") + pair[b] + ": not evaluated (a point was refused);";
+  }
+  if (rep.b_infinity_mismatch != (size_t)-1) out += " b_g1_query / b_g2_query[" + std::to_string(rep.b_infinity_mismatch) + "]: exactly one is the point at infinity;";
+  if (rep.structure)
+    out += std::string(" ") + element[rep.structure] + (rep.structure_first == (size_t)-1 ? ": its length" : ": index " + std::to_string(rep.structure_first)) +
+           " disagrees with the constraint system;";
+  return out;
+}
+
 // A Groth16 proof over BW6-761 in the ABI's affine Montgomery limbs: A in G1, B in G2, C in G1.
 struct groth16_proof {
   std::array<uint64_t, 24> a, b, c;

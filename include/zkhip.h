@@ -41,6 +41,7 @@ extern "C" {
 #define ZKHIP_ERR_STATE (-4)      /* library not initialised / handle invalid */
 #define ZKHIP_ERR_NO_TICKET (-5)  /* pipeline / dispatcher wait: this ticket was never issued or has been collected already
                                      (ZKHIP_ERR_ARG from a wait means the BATCH failed: malformed or degenerate nested proofs) */
+#define ZKHIP_ERR_REFUSED (-6)    /* a checked prover refused its input; zkhip_prover_last_refusal says why */
 
 typedef struct zkhip_bases zkhip_bases; /* opaque: a base-point set resident in HBM */
 
@@ -254,6 +255,57 @@ int zkhip_crs_finite_terms(const zkhip_crs* c, size_t out[5]);
 int zkhip_crs_table_window(const zkhip_crs* c);          /* window of the key's tables, 0: none */
 int zkhip_crs_device(const zkhip_crs* c);                /* the GPU that holds the key */
 
+/* ---- key check: validate a proving key before it is uploaded ------------------------------------------------------------------
+ * stands beside: r1cs_gg_ppzksnark_proving_key read from a file or an MPC (aggregator_server/aggregator_server.cpp:483-514); the
+ * reference trusts what it loads.  zkhip_crs_upload[_ex] checks nothing either: a key with an unreduced limb, a point off its curve or
+ * outside the group of order r, a G1 point in the B-G2 vector, or B-G1 / B-G2 queries that do not belong together uploads without
+ * complaint and every proof made from it fails to verify later, somewhere else.  zkhip_crs_check says what is wrong and where:
+ *   1. POINTS.  Every point of the key is fully reduced and either all zero (the point at infinity, which passes) or on its curve and
+ *      of order r: the checks and codes of the checked verifier (ZKHIP_VERIFY_ENCODING / _OFF_CURVE / _NOT_ORDER_R, the first that
+ *      applies).  beta_g2, delta_g2 and b_g2_query are checked on y^2 = x^3 + 4, everything else on y^2 = x^3 - 1.  On the device: one
+ *      lane per point of a staged chunk of one element (csrc/key_check.hip k_key_point_check, the lane body of the checked verifier).
+ *   2. PAIRS.  t(beta_g1, g2) t(-g1, beta_g2) == 1 and the same for delta, on the host.  For the B queries ONE random combination:
+ *      S1 = sum rho_i B-G1[i], S2 = sum rho_i B-G2[i] with the SAME 128-bit scalars (two MSMs on the device), then
+ *      t(S1, g2) t(-g1, S2) == 1 on the host.  A relation is only evaluated when none of its points was refused in step 1: GT has prime
+ *      order r, and WHEN EVERY B POINT HAS ORDER r a pair of vectors with B-G1[i] != s_i g1 for B-G2[i] = s_i g2 passes with probability
+ *      about 2^-128 over the rho_i - with a point of small order in a vector the error term can have small order and be cancelled by its
+ *      scalar with noticeable probability, which is why the relation is left unevaluated then (the precondition zkhip_verifier_verify_all
+ *      documents, for the same reason).  The infinity patterns of the two B vectors must agree index by index.
+ *   3. STRUCTURE (only with cs).  n_vars and n_primary are the system's and domain_size is a domain that holds it (n + l + 1 points);
+ *      a query base is at infinity exactly where the setup's polynomial for that variable is identically zero: A[i] iff i > n_primary
+ *      and column i of A holds no non-zero coefficient (variables 0 .. n_primary carry the input-consistency rows of the QAP instance
+ *      map), B-G1[i] and B-G2[i] iff column i of B holds none, L[i - n_primary - 1] iff columns i of A, B and C hold none; H and vk_abc
+ *      have no base at infinity.  A host loop over column occupancy; this is the check that catches "the key of another circuit".
+ * vk_abc: the (n_primary + 1) x 24 limbs of the verification key's ABC, checked as the eleventh element, or NULL.
+ * rho: n_vars x 2 words (little endian, 128 bits each, none zero: ZKHIP_ERR_ARG) for tests and reproducible runs only - scalars that
+ * somebody who made the key knows or can predict prove nothing -, or NULL to draw them from the OS (getrandom; ZKHIP_ERR_STATE if that
+ * fails, as zkhip_verifier_verify_all).
+ * Returns ZKHIP_OK whenever the check RAN: the verdict is out->ok and the report.  ZKHIP_ERR_ARG: null arguments, implausible sizes
+ * (n_vars < n_primary + 1, no valid domain, a vector of 2^30 points or more).
+ * zkhip_crs_check runs on the calling thread's library device (zkhip_set_device) on a stream and work space of its own.
+ * zkhip_crs_check_host: the same report on the host alone (no device, no zkhip_init; the point checks on up to 16 threads, the sums by
+ * host scalar multiplications): the reference the device route is pinned on. */
+enum { ZKHIP_KEY_ALPHA_G1, ZKHIP_KEY_BETA_G1, ZKHIP_KEY_BETA_G2, ZKHIP_KEY_DELTA_G1, ZKHIP_KEY_DELTA_G2,
+       ZKHIP_KEY_A, ZKHIP_KEY_B_G2, ZKHIP_KEY_B_G1, ZKHIP_KEY_H, ZKHIP_KEY_L, ZKHIP_KEY_VK_ABC, ZKHIP_KEY_ELEMENTS };   /* elements of a key, in report order */
+typedef struct {
+  size_t points, infinity;   /* points of the element; those at infinity (all zero) */
+  size_t refused[3];         /* points refused as ENCODING, OFF_CURVE, NOT_ORDER_R */
+  size_t first_refused;      /* the smallest refused index, (size_t)-1: none */
+  int first_code;            /* its code (ZKHIP_VERIFY_*), 0: none */
+} zkhip_key_element_report;
+typedef struct {
+  zkhip_key_element_report e[ZKHIP_KEY_ELEMENTS];
+  int pairs;                  /* bit 0 beta_g1/beta_g2, bit 1 delta_g1/delta_g2, bit 2 B-G1/B-G2: set = the relation FAILS */
+  int pairs_evaluated;        /* same bits: set = the relation was evaluated (it is not when one of its points was refused) */
+  size_t b_infinity_mismatch; /* first i with exactly one of B-G1[i], B-G2[i] at infinity, (size_t)-1: none */
+  int structure;              /* 0 fine / not asked; else the element (ZKHIP_KEY_A ..) whose length or infinity pattern disagrees with the
+                                 system: a wrong n_vars is reported at ZKHIP_KEY_A, n_primary at ZKHIP_KEY_L, the domain at ZKHIP_KEY_H */
+  size_t structure_first;     /* the first index that disagrees ((size_t)-1 for a length) */
+  int ok;                     /* 1 iff nothing above is refused, failing, unevaluated or disagreeing */
+} zkhip_key_report;
+int zkhip_crs_check(const zkhip_crs_desc* key, const uint64_t* vk_abc, const zkhip_r1cs_desc* cs, const uint64_t* rho, zkhip_key_report* out);
+int zkhip_crs_check_host(const zkhip_crs_desc* key, const uint64_t* vk_abc, const zkhip_r1cs_desc* cs, const uint64_t* rho, zkhip_key_report* out);
+
 /* replaces: wsnarkT::generate_proof(pk, pb) = libsnark::r1cs_gg_ppzksnark_prover (called at
  * libzecale/circuits/aggregator_circuit.tcc:168), with the randomisers (r, s) injected so that
  * results can be compared bit for bit.  z: n_vars x 6 limbs.  proof_affine: A (G1), B (G2), C (G1). */
@@ -303,6 +355,27 @@ int zkhip_prover_create_streams(zkhip_prover* p, int which);
 int zkhip_prover_prove(zkhip_prover* p, const uint64_t* z, const uint64_t r[6], const uint64_t s[6], uint64_t proof_affine[72]);
 /* the same with the assignment already in device memory (n_vars x 6 limbs, e.g. from zkhip_gpu_witness_run; must be complete) */
 int zkhip_prover_prove_dev(zkhip_prover* p, const void* d_z, const uint64_t r[6], const uint64_t s[6], uint64_t proof_affine[72]);
+/* Checked proving (stands beside: _pb.is_satisfied() under DEBUG, aggregator_circuit.tcc:159-164).  zkhip_prover_prove* turns an
+ * unsatisfying or unreduced assignment into an unverifiable proof and returns ZKHIP_OK, and zkhip_prover_prove_app_dev ORs an unmasked
+ * device assignment into the application's constants.  With zkhip_prover_set_checked(p, 1) the four entry points zkhip_prover_prove,
+ * _prove_dev, _prove_app and _prove_app_dev write NO proof for such input and return ZKHIP_ERR_REFUSED; zkhip_prover_last_refusal gives
+ * the kind and the index.  If several kinds apply the smallest kind is reported, and the smallest index of that kind.  For acceptable
+ * input the proof is limb-identical to the unchecked prover's.
+ * The flags are written by checking variants of the kernels that touch the data anyway - the conversion of the assignment compares the
+ * raw limbs with r, entry 0 with ONE and, for prove_app[_dev], the two operands of the merge; a first-failing-row form of the
+ * satisfiability check reads <A,z>, <B,z>, <C,z> where the QAP map leaves them before any transform - and they reach the host in the
+ * synchronisation the proof has anyway: no additional host wait, in every strategy (one launch sequence, Edwards key, split, chained).
+ * The MSMs of a refused proof run; their result is dropped.  A checked zkhip_prover_prove_app reports an unmasked HOST assignment as
+ * ZKHIP_REFUSAL_APP_MASK too (unchecked: ZKHIP_ERR_ARG from the host's own look at the positions, as before).
+ * Default 0: every kernel and launch sequence is the unchecked prover's.  Not for provers over a slice of the key (ZKHIP_ERR_STATE);
+ * the streaming pipeline and the dispatcher generate their own assignments and have no checked form.
+ * last_refusal: *kind = 0 when p's last proof was not refused. */
+#define ZKHIP_REFUSAL_ENCODING 1 /* an assignment entry >= r            (index: the variable) */
+#define ZKHIP_REFUSAL_ONE 2      /* z[0] is not the constant ONE */
+#define ZKHIP_REFUSAL_UNSAT 3    /* <A_i,z><B_i,z> != <C_i,z>          (index: the FIRST such constraint) */
+#define ZKHIP_REFUSAL_APP_MASK 4 /* prove_app[_dev]: masked assignment non-zero at a constant's position (index: the variable) */
+int zkhip_prover_set_checked(zkhip_prover* p, int on);          /* default 0 */
+int zkhip_prover_last_refusal(zkhip_prover* p, int* kind, size_t* index);
 int zkhip_prover_timings(zkhip_prover* p, double out_ms[8]);   /* as zkhip_last_prove_timings, for p's last proof */
 /* 1 if p's last proof was chained (streaming mode, see zkhip_prover_set_streaming): slots [0] and [1] above are then the time it took
  * to ENQUEUE the upload and the QAP map, and the five MSM slots hold the whole device time of the proof */
@@ -824,6 +897,13 @@ int zkhip_internal_pairing_product(int route, const uint64_t* g1, const uint64_t
  * shared pairs and the final exponentiation). */
 int zkhip_internal_verify_all_value(int route, zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
                                     const uint64_t* rho, uint64_t out[72]);
+/* key_check_set_chunk: points per launch of zkhip_crs_check's point kernel, process-wide; 0: the rule (csrc/pairing.cuh
+ * key_check_chunk, 2^17).  Lets tests cross chunk boundaries at a few hundred points.
+ * key_check_last_ms: of the calling thread's last zkhip_crs_check[_host]: [0] the device time of its longest single point-check launch
+ * (0 on the host route), [1] the wall time of all its point checks (staging included), [2] of the two sums of the B relation, [3] of
+ * the host's pairings, [4 + e] of the point checks of element e, milliseconds. */
+int zkhip_internal_key_check_set_chunk(size_t points);
+int zkhip_internal_key_check_last_ms(double out_ms[4 + ZKHIP_KEY_ELEMENTS]);
 int zkhip_internal_verify_all_finish_ms(const zkhip_verifier* v, double* ms);
 /* Test hooks of the nested pairing kernels (no counterpart).
  * fq12_selftest: n independent operand sets through the per-lane bodies of pairing_bls.cuh inside a real kernel, sixteen lanes per

@@ -74,6 +74,7 @@ const char* zkhip_strerror(int code) {
     case ZKHIP_ERR_HIP: return "HIP runtime error";
     case ZKHIP_ERR_STATE: return "library not initialised";
     case ZKHIP_ERR_NO_TICKET: return "no such ticket";
+    case ZKHIP_ERR_REFUSED: return "input refused by a checked prover";
     default: return "unknown error";
   }
 }

@@ -121,6 +121,8 @@ int bases_precompute_mode(zkhip_bases* b, int c, int naf, bool edw) {
       rc = msm_table_edw(tab, tinf, b->len, c, &et, e_err, sizeof e_err);
       if (rc == ZKHIP_OK) b->d_edw = et;
       else if (rc == ZKHIP_ERR_HIP) { snprintf(t_err, sizeof t_err, "Edwards table: %s", e_err); return rc; }
+      // (not an error: the set stays XYZZ and the call succeeds - but zkhip_last_error() says where to look)
+      else snprintf(t_err, sizeof t_err, "Edwards table not built, the set keeps its XYZZ tables: %s - zkhip_crs_check reports which point of a key is not of order r", e_err);
     }
     (void)hipGetLastError();
   }

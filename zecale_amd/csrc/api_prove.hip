@@ -25,7 +25,27 @@ struct zkhip_prover {
   std::mutex mu;
   bool slice = false;                    // crs is a slice of the key (zkhip_prover_new_slice): partial sums only
   size_t a_lo = 0, h_lo = 0, l_lo = 0;   // where the slice starts in the A / B, H and L queries
+  bool checked = false;                  // zkhip_prover_set_checked: rd runs the checking variants, a refused input gets no proof
+  int refusal_kind = 0;                  // of the last proof: 0 none, else ZKHIP_REFUSAL_*
+  size_t refusal_index = 0;
 };
+
+// a checked prover after prove_partial: the flag words the QAP map's stream left on the host (qap.h) -> the smallest kind that applies
+// and its smallest index.  The words are complete: every strategy has waited for that stream's part of the proof.
+static int prover_refusal(zkhip_prover* p) {
+  static const char* const what[ZK_CHK_WORDS] = {"an assignment entry is not below r", "z[0] is not the constant ONE",
+                                                 "the assignment does not satisfy a constraint",
+                                                 "the masked assignment is non-zero at one of the application's constant positions"};
+  for (int k = 0; k < ZK_CHK_WORDS; k++) {
+    const uint32_t w = p->rd->chk_host[k];
+    if (w == ZK_CHK_NONE) continue;
+    p->refusal_kind = k + 1;               // ZKHIP_REFUSAL_ENCODING .. _APP_MASK, in the order of the words
+    p->refusal_index = w;
+    snprintf(t_err, sizeof t_err, "checked prover: %s (index %u); no proof was written", what[k], w);
+    return ZKHIP_ERR_REFUSED;
+  }
+  return ZKHIP_OK;
+}
 
 // the proof's key and (for a host assignment) its masking
 static int app_check(const zkhip_aggregator_app* app, const zkhip_crs* crs, const uint64_t* z_host) {
@@ -532,11 +552,13 @@ static int prover_prove_impl(zkhip_prover* p, const uint64_t* z, const uint64_t*
   uint64_t sums[180];
   const zkhip_crs* c = p->crs;
   { int rc_ = prove_check(c, p->rd, 0, 0, 0); if (rc_ != ZKHIP_OK) return rc_; }
-  if (app) { int rc_ = app_check(app, c, z); if (rc_ != ZKHIP_OK) return rc_; }
+  p->refusal_kind = 0; p->refusal_index = 0;
+  if (app) { int rc_ = app_check(app, c, p->checked ? nullptr : z); if (rc_ != ZKHIP_OK) return rc_; }   // (checked: the device reports the mask, with its index)
   TailPre pre;
   tail_begin(pre, c->delta_g1, c->delta_g2, r_m, s_m, crs_tail_tables(c));             // the key-only part of the tail runs under the device work
   int rc = prove_partial(p->ps, p->crs, p->rd, z, 0, 0, 0, sums, d_z, app ? app->d_z_app : nullptr);
   if (rc != ZKHIP_OK) return rc;
+  if (p->checked && (rc = prover_refusal(p)) != ZKHIP_OK) return rc;      // (the MSMs of a refused proof ran; their sums are dropped)
   if (app) app_add_points(app, sums);
   return finish_impl(c->alpha_g1, c->beta_g1, c->beta_g2, c->delta_g1, c->delta_g2, sums, r_m, s_m, proof_affine, &p->ps.ms[7], &pre);
 }
@@ -695,6 +717,23 @@ int zkhip_prover_set_streaming(zkhip_prover* p, int on) {
   p->ps.quad_below = on ? 1024u : 0u;
   p->rd->spmv_log_lanes = on ? (p->rd->spmv_log_lanes_alone < 2 ? p->rd->spmv_log_lanes_alone : 2) : p->rd->spmv_log_lanes_alone;
   for (int k = 0; k < ZK_CTX_TOTAL; k++) if (p->ps.ctx[k].planned) { p->ps.ctx[k].quad_below = on ? 1024u : 65536u; p->ps.ctx[k].one_stream = on ? 1 : 0; }
+  return ZKHIP_OK;
+}
+
+int zkhip_prover_set_checked(zkhip_prover* p, int on) {
+  if (!p) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (p->slice) return fail(ZKHIP_ERR_STATE, "a prover over a slice of the key has no checked form");
+  BIND(p);
+  std::lock_guard<std::mutex> lk(p->mu);
+  const int rc = r1cs_set_checked(p->rd, on, t_err, sizeof t_err);
+  if (rc == ZKHIP_OK) p->checked = on != 0;
+  return rc;
+}
+int zkhip_prover_last_refusal(zkhip_prover* p, int* kind, size_t* index) {
+  if (!p || !kind || !index) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::lock_guard<std::mutex> lk(p->mu);
+  *kind = p->refusal_kind;
+  *index = p->refusal_index;
   return ZKHIP_OK;
 }
 

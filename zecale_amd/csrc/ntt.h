@@ -22,4 +22,10 @@ int ntt_set_one_each_max(int log_d_max);   // -1: the environment / default; whi
 void fr_abi_to_dev(const uint64_t* d_in, uint32_t* d_out, size_t n, hipStream_t st);
 void fr_abi_to_dev_merge(const uint64_t* d_in, const uint64_t* d_in2, uint32_t* d_out, size_t n, hipStream_t st);   // limb-wise OR of two disjoint parts
 void fr_dev_to_abi(const uint32_t* d_in, uint64_t* d_out, size_t n, hipStream_t st);
+// The flag words of a checked prover (zkhip.h: zkhip_prover_set_checked), in the order of the ZKHIP_REFUSAL_* kinds: each holds the
+// smallest index that fails its check, 0xFFFFFFFF = none.  fr_abi_to_dev_checked converts as the two above (d_in2 null: the plain
+// form) and writes ENCODING, ONE and - merged form - APP_MASK; qap.hip's k_check_sat_first writes UNSAT.
+constexpr int ZK_CHK_ENCODING = 0, ZK_CHK_ONE = 1, ZK_CHK_UNSAT = 2, ZK_CHK_APP_MASK = 3, ZK_CHK_WORDS = 4;
+constexpr uint32_t ZK_CHK_NONE = 0xFFFFFFFFu;
+void fr_abi_to_dev_checked(const uint64_t* d_in, const uint64_t* d_in2, uint32_t* d_out, size_t n, uint32_t* d_chk, hipStream_t st);
 }  // namespace zkhip

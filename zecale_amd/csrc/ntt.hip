@@ -84,6 +84,42 @@ __global__ void __launch_bounds__(256) k_fr_abi_to_dev_merge(const uint64_t* __r
   for (int k = 0; k < 6; k++) x[k] = in[i * 6 + k] | in2[i * 6 + k];
   fr_store12(out + i * 12, fp_from_abi<FrParams>(x));
 }
+// ---- the CHECKING variants of the two kernels above (a checked prover: zkhip_prover_set_checked).  Kernels of their own, so that the
+// unchecked ones stay what they were.  They convert exactly as above and, on the raw limbs they have in hand anyway, write the flag
+// words of qap.h (ZK_CHK_*; each the smallest index that fails, by atomicMin, 0xFFFFFFFF = none): the caller's entry i is not below r
+// (the borrow of in[i] - r, no branches); entry 0 of the whole assignment is not the constant ONE; in the merged form, `in` is non-zero
+// where the application holds a constant (both operands non-zero: the OR would be neither).  n < 2^32 (a key has at most 2^23 variables).
+__device__ __forceinline__ bool fr_abi_geq_r(const uint64_t* x) {
+  uint64_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const uint64_t a = x[i], m = FrParams::P64[i], d = a - m;
+    borrow = (uint64_t)(a < m) | (uint64_t)(d < borrow);
+  }
+  return borrow == 0;
+}
+template <bool MERGE>
+__global__ void __launch_bounds__(256) k_fr_abi_to_dev_checked(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint32_t* __restrict__ out,
+                                                                size_t n, uint32_t* __restrict__ chk) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t x[6], nz = 0, nz2 = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) { x[k] = in[i * 6 + k]; nz |= x[k]; }
+  if (fr_abi_geq_r(x)) atomicMin(chk + ZK_CHK_ENCODING, (uint32_t)i);
+  if (MERGE) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) { const uint64_t c = in2[i * 6 + k]; nz2 |= c; x[k] |= c; }
+    if (nz && nz2) atomicMin(chk + ZK_CHK_APP_MASK, (uint32_t)i);
+  }
+  if (i == 0) {
+    uint64_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) diff |= x[k] ^ FrParams::ONE64[k];
+    if (diff) atomicMin(chk + ZK_CHK_ONE, 0u);
+  }
+  fr_store12(out + i * 12, fp_from_abi<FrParams>(x));
+}
 // (log_k != 0: `in` is in transposed order, element i at (i mod 2^log_k) * 2^log_n2 + (i >> log_k))
 __global__ void __launch_bounds__(256) k_fr_dev_to_abi(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, size_t n, int log_k, int log_n2) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -594,6 +630,11 @@ void fr_abi_to_dev(const uint64_t* d_in, uint32_t* d_out, size_t n, hipStream_t 
 }
 void fr_abi_to_dev_merge(const uint64_t* d_in, const uint64_t* d_in2, uint32_t* d_out, size_t n, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_fr_abi_to_dev_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_in, d_in2, d_out, n);
+}
+void fr_abi_to_dev_checked(const uint64_t* d_in, const uint64_t* d_in2, uint32_t* d_out, size_t n, uint32_t* d_chk, hipStream_t st) {
+  if (!n) return;
+  if (d_in2) hipLaunchKernelGGL(k_fr_abi_to_dev_checked<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_in, d_in2, d_out, n, d_chk);
+  else hipLaunchKernelGGL(k_fr_abi_to_dev_checked<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_in, d_in2, d_out, n, d_chk);
 }
 void fr_dev_to_abi(const uint32_t* d_in, uint64_t* d_out, size_t n, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_fr_dev_to_abi, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_in, d_out, n, 0, 0);

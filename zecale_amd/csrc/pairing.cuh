@@ -40,6 +40,11 @@ constexpr size_t pairing_batch_chunk(size_t n_inputs) {
   if (n_inputs == 0 || PAIRING_CHUNK * n_inputs <= PAIRING_MAX_TERMS) return PAIRING_CHUNK;
   return PAIRING_MAX_TERMS / n_inputs ? PAIRING_MAX_TERMS / n_inputs : 1;
 }
+// points per launch of the key check (key_check.hip k_key_point_check, one lane per point, 5.1 k Fq products each): a launch at one
+// wave per SIMD holds 65,536 lanes, so 2^17 points are two rounds of the whole chip and a 2^22-point query vector is 32 launches -
+// no single launch is long on a device that others share.  `hook`: zkhip_internal_key_check_set_chunk, 0 = this rule.
+constexpr size_t KEY_CHECK_CHUNK = (size_t)1 << 17;
+constexpr size_t key_check_chunk(size_t hook) { return hook ? hook : KEY_CHECK_CHUNK; }
 // values one level of a reduction tree writes for the n it reads
 constexpr size_t pairing_strips(size_t n) { return (n + PAIRING_STRIP - 1) / PAIRING_STRIP; }
 // launches of a reduction tree over n >= 1 values: level k reads n_k values (n_0 = n) and writes n_{k+1} = pairing_strips(n_k); the last

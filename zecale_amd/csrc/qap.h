@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/zkhip.h"
+#include "ntt.h"
 
 namespace zkhip {
 
@@ -30,6 +31,10 @@ struct R1csDev {
                               // big / small classes on its big part (by i mod (big / small)) and one more for its small part
   // step domains: powers in packed device form - w^i (i < big), w^-i (i < small), g^i and g^-i (i < d) - and 1/2 (14 limbs)
   uint32_t *pw_w = nullptr, *pw_winv = nullptr, *pw_g = nullptr, *pw_ginv = nullptr, *half = nullptr;
+  // a checked prover (r1cs_set_checked): the flag words of ntt.h (ZK_CHK_*) on the device, and the pinned host words qap_h_dev copies
+  // them to on its own stream - complete when that stream's work of the proof is, which every strategy of a proof waits for anyway
+  bool checked = false;
+  uint32_t *chk = nullptr, *chk_host = nullptr;
 };
 
 // domain_size: 0 = the reference's forced power of two for n + l + 1 points (default); (size_t)-1 = libfqfft's unforced choice
@@ -42,6 +47,10 @@ void r1cs_free(R1csDev* r);
 // d_z_app != null: d_z_abi is MASKED (zeros at an application's constant positions) and d_z_app (n_vars x 6, zeros everywhere else)
 // holds those constants: the map runs on their union
 int qap_h_dev(R1csDev* r, const uint64_t* d_z_abi, hipStream_t st, char* err, size_t errlen, const uint64_t* d_z_app = nullptr);
+// on != 0: qap_h_dev runs the CHECKING variants of its first kernels (the conversion compares the assignment with r, with ONE and with
+// the application's mask; a first-failing-row form of the satisfiability check reads the three sparse products) and leaves the flag
+// words in r->chk_host.  Off (the default): the launch sequence is what it always was.  Nothing may be in flight on the handle.
+int r1cs_set_checked(R1csDev* r, int on, char* err, size_t errlen);
 // satisfiability check <A_i,z><B_i,z> = <C_i,z> for all i (reference: _pb.is_satisfied(), aggregator_circuit.tcc:159-164)
 int r1cs_is_satisfied_dev(R1csDev* r, const uint64_t* d_z_abi, hipStream_t st, int* ok, char* err, size_t errlen);
 

@@ -238,6 +238,21 @@ __global__ void __launch_bounds__(256) k_check_sat(const uint32_t* __restrict__ 
   if (!fp_is_zero_2p(t)) atomicOr(flag, 1u);
 }
 
+// a checked prover: the FIRST row i < n with <A_i,z><B_i,z> != <C_i,z>, by atomicMin into *first.  One lane per LOCATION of the three
+// vectors, which are in the order their first transform reads (part_index gives the row a location holds).
+__global__ void __launch_bounds__(256) k_check_sat_first(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B,
+                                                          const uint32_t* __restrict__ C, uint32_t n, uint32_t d, PartLayout lay,
+                                                          uint32_t* __restrict__ first) {
+  uint32_t loc = blockIdx.x * blockDim.x + threadIdx.x;
+  if (loc >= d) return;
+  const uint32_t i = part_index(lay, loc);
+  if (i >= n) return;
+  FrD ab = fp_mul(q_load12(A + (size_t)loc * 12), q_load12(B + (size_t)loc * 12));
+  FrD c = fp_mul(q_load12(C + (size_t)loc * 12), fp_one<FrParams>());
+  FrD t = fp_mul(fp_sub<FrParams, 2>(ab, c), fp_one<FrParams>());     // < 2r
+  if (!fp_is_zero_2p(t)) atomicMin(first, i);
+}
+
 // ------------------------------------------------------------------------------------------
 #define Q_HIP(x)                                                                                   \
   do {                                                                                             \
@@ -396,8 +411,9 @@ static int r1cs_upload_impl(const zkhip_r1cs_desc* d, size_t domain_size, R1csDe
 void r1cs_free(R1csDev* r) {
   if (!r) return;
   void* ptrs[] = {r->A.row_ptr, r->A.col, r->A.val, r->B.row_ptr, r->B.col, r->B.val, r->C.row_ptr, r->C.col, r->C.val,
-                  r->bufA, r->bufB, r->bufC, r->tmp, r->z, r->zinv, r->pw_w, r->pw_winv, r->pw_g, r->pw_ginv, r->half};
+                  r->bufA, r->bufB, r->bufC, r->tmp, r->z, r->zinv, r->pw_w, r->pw_winv, r->pw_g, r->pw_ginv, r->half, r->chk};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  if (r->chk_host) (void)hipHostFree(r->chk_host);
   delete r;
 }
 
@@ -442,12 +458,22 @@ int qap_h_dev(R1csDev* r, const uint64_t* d_z_abi, hipStream_t st, char* err, si
   }
   const int lg = r->log_d;
   const uint32_t d = (uint32_t)r->d;
-  if (d_z_app) fr_abi_to_dev_merge(d_z_abi, d_z_app, r->z, r->n_vars, st);       // masked assignment | the application's constants
-  else fr_abi_to_dev(d_z_abi, r->z, r->n_vars, st);
-  spmv3(r, st);
+  const PartLayout lay = part_layout(r);
+  if (r->checked) {
+    // the checking variants write the flag words; they are on their way to the host before the first transform starts
+    Q_HIP(hipMemsetAsync(r->chk, 0xFF, ZK_CHK_WORDS * 4, st));
+    fr_abi_to_dev_checked(d_z_abi, d_z_app, r->z, r->n_vars, r->chk, st);
+    spmv3(r, st);
+    hipLaunchKernelGGL(k_check_sat_first, dim3((d + 255) / 256), dim3(256), 0, st, r->bufA, r->bufB, r->bufC, (uint32_t)r->n_constraints, d, lay,
+                       r->chk + ZK_CHK_UNSAT);
+    Q_HIP(hipMemcpyAsync(r->chk_host, r->chk, ZK_CHK_WORDS * 4, hipMemcpyDeviceToHost, st));
+  } else {
+    if (d_z_app) fr_abi_to_dev_merge(d_z_abi, d_z_app, r->z, r->n_vars, st);       // masked assignment | the application's constants
+    else fr_abi_to_dev(d_z_abi, r->z, r->n_vars, st);
+    spmv3(r, st);
+  }
   int rc;
   uint32_t* bufs[3] = {r->bufA, r->bufB, r->bufC};
-  const PartLayout lay = part_layout(r);
   if (!r->small) {
     if ((rc = ntt_dev_packed_batch(bufs, 3, lg, 1, 0, 1, st, err, errlen)) != ZKHIP_OK) return rc;   // iFFT of A, B, C: transposed -> natural
     if ((rc = ntt_dev_packed_batch(bufs, 3, lg, 0, 1, 0, st, err, errlen)) != ZKHIP_OK) return rc;   // cosetFFT: natural -> transposed
@@ -472,6 +498,16 @@ int qap_h_dev(R1csDev* r, const uint64_t* d_z_abi, hipStream_t st, char* err, si
   if ((rc = step_ntts(r, bufs, 1, 1, 1, st, err, errlen)) != ZKHIP_OK) return rc;                     // icosetFFT of H: transposed -> natural
   hipLaunchKernelGGL(k_step_half<true>, dim3(sblocks, 1), dim3(256), 0, st, sa);                       // ... element-wise half, x g^-i
   Q_HIP(hipGetLastError());
+  return ZKHIP_OK;
+}
+
+int r1cs_set_checked(R1csDev* r, int on, char* err, size_t errlen) {
+  if (on && !r->chk) Q_HIP(hipMalloc(&r->chk, ZK_CHK_WORDS * 4));
+  if (on && !r->chk_host) {
+    Q_HIP(hipHostMalloc(&r->chk_host, ZK_CHK_WORDS * 4));
+    for (int k = 0; k < ZK_CHK_WORDS; k++) r->chk_host[k] = ZK_CHK_NONE;
+  }
+  r->checked = on != 0;
   return ZKHIP_OK;
 }
 

@@ -283,8 +283,11 @@ class GpuProver:
     snark_name = "GROTH16"
 
     def __init__(self, keypair_file=None, device=0, gpu_slots=32, witness_workers=10, gpu_witness=False, devices=None, hybrid_witness=False,
-                 screen_nested=False, screen_combined=False, key_table_model="xyzz"):
-        """key_table_model: "xyzz" (default) or "edwards" - the kind of tables the key gets (server_key_opts).
+                 screen_nested=False, screen_combined=False, key_table_model="xyzz", check_key=False):
+        """check_key (default off): run zkhip_crs_check on the keypair - every point's encoding, curve and order, the pair relations, and
+        the key's structure against the aggregator circuit's own constraint system - before the key is uploaded; a key that fails is
+        refused (ValueError naming element, index and code) and nothing is uploaded.
+        key_table_model: "xyzz" (default) or "edwards" - the kind of tables the key gets (server_key_opts).
         screen_nested: verify the queued nested proofs in batches on the GPU (zkhip_nested_verifier, the CHECKED route: every point's
         encoding, curve and order, every input's range) before a batch is popped, so that an invalid or malformed one costs no slot of
         a wrapping proof (`screen_status` / `screen`; off: the service never asks).
@@ -318,6 +321,10 @@ class GpuProver:
         self.vk = self.kp.vk()
         if self.vk["ABC"].shape[0] != self.agg.num_primary_inputs() + 1:      # the server's "invalid VK" check (:490, :504)
             raise ValueError("invalid VK")
+        if check_key:
+            report = zkhip.check_key(self.kp, r1cs=desc)
+            if not report.ok:
+                raise ValueError("the keypair was refused: " + report.describe())
         # The options travel with THIS key (zkhip_key_opts), not with the process: another key loaded on another thread keeps its own.
         opts = server_key_opts(key_table_model)
         if len(devices) > 1:
@@ -669,12 +676,15 @@ def main(argv=None, parse_only=False):
     ap.add_argument("--key-table-model", choices=("xyzz", "edwards"), default="xyzz",
                     help="xyzz (default): every-bit-position tables, NAF scalars; edwards: one-level tables with their Edwards form - the G1 MSMs "
                          "of a proof add on G1's 2-isogenous Edwards curve (1.5 x the one-level tables' memory on top)")
+    ap.add_argument("--check-key", action="store_true", help="validate the loaded keypair on the GPU before it is uploaded (every point's encoding, "
+                                                             "curve and order, the pair relations, the structure against the aggregator circuit): "
+                                                             "a key that fails is refused, naming element, index and code")
     args = ap.parse_args(argv)
     if parse_only:
         return args
     print("[INFO] Init params of both curves")
     prover = GpuProver(args.keypair, device=args.device, gpu_witness=args.gpu_witness, hybrid_witness=args.hybrid_witness, screen_nested=args.screen_nested,
-                       screen_combined=args.screen_combined, key_table_model=args.key_table_model,
+                       screen_combined=args.screen_combined, key_table_model=args.key_table_model, check_key=args.check_key,
                        devices=[int(x) for x in args.devices.split(",")] if args.devices else None)
     print("[INFO] Circuit has %d constraints" % prover.agg.num_constraints)
     print("[INFO] Setup successful, starting the server...")

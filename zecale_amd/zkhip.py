@@ -50,6 +50,7 @@ EXPORTS = [
     "zkhip_verifier_verify_all", "zkhip_groth16_verify_all", "zkhip_internal_verify_all_value", "zkhip_internal_verify_all_finish_ms",
     "zkhip_nested_verifier_verify_all", "zkhip_nested_verifier_last_degenerate", "zkhip_bls12_377_groth16_verify_all",
     "zkhip_internal_nested_verify_all_value", "zkhip_internal_nested_verify_all_finish_ms",
+    "zkhip_prover_set_checked", "zkhip_prover_last_refusal", "zkhip_crs_check", "zkhip_crs_check_host", "zkhip_internal_key_check_set_chunk", "zkhip_internal_key_check_last_ms",
 ]
 
 
@@ -62,6 +63,8 @@ class ZkhipError(RuntimeError):
 
 
 c_u64p_t = ctypes.POINTER(ctypes.c_uint64)
+ERR_REFUSED = -6                  # ZKHIP_ERR_REFUSED: a checked prover refused its input (Prover.set_checked)
+REFUSAL_ENCODING, REFUSAL_ONE, REFUSAL_UNSAT, REFUSAL_APP_MASK = 1, 2, 3, 4
 
 
 class R1csDesc(ctypes.Structure):
@@ -91,6 +94,55 @@ class CrsDesc(ctypes.Structure):
     _fields_ = [("n_vars", ctypes.c_size_t), ("n_primary", ctypes.c_size_t), ("domain_size", ctypes.c_size_t)] + [
         (k, ctypes.c_void_p) for k in ("alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2",
                                        "a_query", "b_g2_query", "b_g1_query", "h_query", "l_query")]
+
+
+KEY_ELEMENTS = ("alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2", "a_query", "b_g2_query", "b_g1_query", "h_query", "l_query", "vk_abc")
+KEY_PAIRS = ("beta_g1/beta_g2", "delta_g1/delta_g2", "b_g1_query/b_g2_query")
+VERIFY_CODES = {0: "fine", 2: "ENCODING", 3: "OFF_CURVE", 4: "NOT_ORDER_R"}
+NONE_INDEX = (1 << (8 * ctypes.sizeof(ctypes.c_size_t))) - 1      # (size_t)-1: "none" in a key report
+
+
+class KeyElementReport(ctypes.Structure):
+    """zkhip_key_element_report: points, those at infinity, refusals by code (ENCODING, OFF_CURVE, NOT_ORDER_R), the first refused index."""
+    _fields_ = [("points", ctypes.c_size_t), ("infinity", ctypes.c_size_t), ("refused", ctypes.c_size_t * 3), ("first_refused", ctypes.c_size_t),
+                ("first_code", ctypes.c_int)]
+
+    def fields(self):
+        return (int(self.points), int(self.infinity), tuple(int(v) for v in self.refused),
+                None if self.first_refused == NONE_INDEX else int(self.first_refused), int(self.first_code))
+
+
+class KeyReport(ctypes.Structure):
+    """zkhip_key_report (include/zkhip.h: zkhip_crs_check).  `ok` is the verdict; fields() is the whole report as plain Python values
+    ((size_t)-1 as None), describe() names what was refused: element, index and code."""
+    _fields_ = [("e", KeyElementReport * len(KEY_ELEMENTS)), ("pairs", ctypes.c_int), ("pairs_evaluated", ctypes.c_int),
+                ("b_infinity_mismatch", ctypes.c_size_t), ("structure", ctypes.c_int), ("structure_first", ctypes.c_size_t), ("ok", ctypes.c_int)]
+
+    def fields(self):
+        none = lambda v: None if v == NONE_INDEX else int(v)
+        return dict(elements={name: self.e[k].fields() for k, name in enumerate(KEY_ELEMENTS)}, pairs=int(self.pairs),
+                    pairs_evaluated=int(self.pairs_evaluated), b_infinity_mismatch=none(self.b_infinity_mismatch), structure=int(self.structure),
+                    structure_first=none(self.structure_first), ok=int(self.ok))
+
+    def describe(self):
+        if self.ok:
+            return "key check: ok"
+        out = []
+        for k, name in enumerate(KEY_ELEMENTS):
+            if self.e[k].first_refused != NONE_INDEX:
+                out.append("%s[%d]: %s (%d of %d points refused)" % (name, self.e[k].first_refused, VERIFY_CODES[self.e[k].first_code],
+                                                                     sum(self.e[k].refused), self.e[k].points))
+        for b, name in enumerate(KEY_PAIRS):
+            if self.pairs >> b & 1:
+                out.append("%s: the two are not the same multiple of their generators" % name)
+            elif not self.pairs_evaluated >> b & 1:
+                out.append("%s: not evaluated (a point was refused)" % name)
+        if self.b_infinity_mismatch != NONE_INDEX:
+            out.append("b_g1_query[%d] / b_g2_query[%d]: exactly one is the point at infinity" % ((self.b_infinity_mismatch,) * 2))
+        if self.structure:
+            where = "its length" if self.structure_first == NONE_INDEX else "index %d" % self.structure_first
+            out.append("%s: %s disagrees with the constraint system" % (KEY_ELEMENTS[self.structure], where))
+        return "key check: " + "; ".join(out)
 
 
 class WitnessProgram(ctypes.Structure):
@@ -248,6 +300,13 @@ def load():
                                                        ctypes.POINTER(ctypes.c_int)]
     lib.zkhip_internal_nested_verify_all_value.argtypes = [ctypes.c_int, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p]
     lib.zkhip_internal_nested_verify_all_finish_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    if hasattr(lib, "zkhip_crs_check"):      # (ZKHIP_LIB may name an older build of the library: tools/key_check_ab.py measures against one)
+        for f in (lib.zkhip_crs_check, lib.zkhip_crs_check_host):
+            f.argtypes = [ctypes.POINTER(CrsDesc), c_u64p, ctypes.POINTER(R1csDesc), c_u64p, ctypes.POINTER(KeyReport)]
+        lib.zkhip_prover_set_checked.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.zkhip_prover_last_refusal.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]
+        lib.zkhip_internal_key_check_set_chunk.argtypes = [ctypes.c_size_t]
+        lib.zkhip_internal_key_check_last_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
     _lib = lib
     return lib
 
@@ -1432,6 +1491,19 @@ class Prover:
         """this instance shares the GPU with others: total work over single-proof latency (zkhip_prover_set_streaming)"""
         _check(load().zkhip_prover_set_streaming(self.handle, int(bool(on))))
 
+    def set_checked(self, on=True):
+        """zkhip_prover_set_checked: prove / prove_dev / prove_app / prove_app_dev refuse an assignment that is not reduced, does not
+        start with ONE, does not satisfy the system or is not masked: ZkhipError with code ERR_REFUSED (-6), no proof; last_refusal()
+        says why.  Proofs of acceptable input are unchanged."""
+        _check(load().zkhip_prover_set_checked(self.handle, int(bool(on))))
+
+    def last_refusal(self):
+        """(kind, index) of this instance's last proof: kind 0 = not refused, else REFUSAL_ENCODING / _ONE / _UNSAT / _APP_MASK
+        (include/zkhip.h); index: the variable, or the first constraint that fails."""
+        kind, index = ctypes.c_int(0), ctypes.c_size_t(0)
+        _check(load().zkhip_prover_last_refusal(self.handle, ctypes.byref(kind), ctypes.byref(index)))
+        return int(kind.value), int(index.value)
+
     def last_accumulate_ms(self):
         return float(load().zkhip_prover_last_accumulate_ms(self.handle))
 
@@ -1694,6 +1766,67 @@ class Keypair:
         if self.handle:
             load().zkhip_keypair_free(self.handle)
             self.handle = None
+
+
+def make_crs_desc(pk, n_vars, n_primary, domain_size):
+    """zkhip_crs_desc over a key's arrays (the dict Crs takes).  Returns (desc, keep): `keep` holds the arrays the descriptor points
+    into and must stay alive while the descriptor is used."""
+    d = CrsDesc()
+    d.n_vars, d.n_primary, d.domain_size = n_vars, n_primary, domain_size
+    keep = []
+    for field, key in (("alpha_g1", "alpha_g1"), ("beta_g1", "beta_g1"), ("beta_g2", "beta_g2"), ("delta_g1", "delta_g1"), ("delta_g2", "delta_g2"),
+                       ("a_query", "A"), ("b_g2_query", "B2"), ("b_g1_query", "B1"), ("h_query", "H"), ("l_query", "L")):
+        a = np.ascontiguousarray(pk[key], dtype=np.uint64).reshape(-1, 24)
+        keep.append(a)
+        setattr(d, field, a.ctypes.data if a.size else None)
+    return d, keep
+
+
+def check_key(key, vk_abc=None, r1cs=None, rho=None, host=False):
+    """zkhip_crs_check / zkhip_crs_check_host (host=True: no device): validate a proving key BEFORE it is uploaded -> KeyReport.
+    key: a Keypair (its own ABC is checked as vk_abc unless one is given), a CrsDesc, or (pk dict, n_vars, n_primary, domain_size) as
+    Crs takes them.  vk_abc: (n_primary + 1) x 24 limbs or None.  r1cs: an R1csDesc, or the (desc, keep) of make_r1cs_desc, for the
+    structure check; None: no structure check.  rho: n_vars 128-bit scalars (ints, or n_vars x 2 words) for tests and reproducible
+    runs; None: drawn from the OS."""
+    lib = load()
+    keep = None
+    if isinstance(key, Keypair):
+        d = CrsDesc()
+        _check(lib.zkhip_keypair_crs_desc(key.handle, ctypes.byref(d)))
+        if d.n_vars and not d.a_query:
+            raise ZkhipError("this keypair holds no query vectors (Keypair.setup_slice): there is nothing to check")
+        if vk_abc is None:
+            vk_abc = key.vk()["ABC"]
+    elif isinstance(key, CrsDesc):
+        d = key
+    else:
+        d, keep = make_crs_desc(*key)
+    abc = None
+    if vk_abc is not None:
+        abc = np.ascontiguousarray(vk_abc, dtype=np.uint64).reshape(-1, 24)
+        if abc.shape[0] != d.n_primary + 1:
+            raise ZkhipError("vk_abc must hold n_primary + 1 points", -1)
+    cs = r1cs[0] if isinstance(r1cs, tuple) else r1cs
+    rl = _rho_limbs(rho, d.n_vars) if rho is not None else None
+    rep = KeyReport()
+    _check((lib.zkhip_crs_check_host if host else lib.zkhip_crs_check)(ctypes.byref(d), _p(abc) if abc is not None else None,
+                                                                       ctypes.byref(cs) if cs is not None else None,
+                                                                       _p(rl) if rl is not None else None, ctypes.byref(rep)))
+    del keep
+    return rep
+
+
+def key_check_set_chunk(points):
+    """Test hook: points per launch of the key check's point kernel (0: the library's rule)."""
+    _check(load().zkhip_internal_key_check_set_chunk(int(points)))
+
+
+def key_check_last_ms():
+    """Of this thread's last check_key: longest single point-check launch (device time), all point checks, the B relation's two sums,
+    the host's pairings (wall time), then the point checks of each of the eleven elements, milliseconds."""
+    out = (ctypes.c_double * (4 + len(KEY_ELEMENTS)))()
+    _check(load().zkhip_internal_key_check_last_ms(out))
+    return [float(v) for v in out]
 
 
 def r1cs_desc_from_aggregator(agg):
