@@ -494,7 +494,8 @@ int zkhip_groth16_verify_checked(const uint64_t vk_alpha_g1[24], const uint64_t 
  * status: NULL, or count bytes on a handle of zkhip_verifier_new_checked: the point checks of zkhip_verifier_verify_batch_checked run
  * in front, status[i] is that route's refusal byte (ENCODING / OFF_CURVE / NOT_ORDER_R with its mask) or 0; a refused proof is left
  * out of the product and the sums and makes all_ok 0.  status != NULL on an unchecked handle: ZKHIP_ERR_STATE.
- * count == 0: all_ok = 1.  A failed batch does not say which proof is at fault: zkhip_verifier_verify_batch does.
+ * count == 0: all_ok = 1.  A failed batch does not say which proof is at fault: zkhip_verifier_verify_batch does, and
+ * zkhip_verifier_verify_batch_located (below) finds it from this check's own intermediate values.
  * zkhip_groth16_verify_all: the same check on the host alone (no device, no zkhip_init; the per-proof work on up to 16 threads), the
  * route the device one is pinned on; like zkhip_groth16_verify it first fails a batch with a point off its curve. */
 int zkhip_verifier_verify_all(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
@@ -502,6 +503,38 @@ int zkhip_verifier_verify_all(zkhip_verifier* v, const uint64_t* inputs, const u
 int zkhip_groth16_verify_all(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
                              const uint64_t* vk_abc, size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs_affine,
                              size_t count, const uint64_t* rho, int* all_ok);
+
+/* ---- located batches: per-proof verdicts by way of the combined check ------------------------------------------------------------
+ * The combined check reduces the proofs' Miller values and the rho_i C_i in trees of arity 8, chunk by chunk of 16,384 proofs.  A
+ * tree node is the product and the sum over a contiguous range of proofs; with the sums of rho_i and rho_i x_ij over the same range it
+ * is a complete combined check of that sub-batch under the same scalars, with the same 2^-128 bound.  This route keeps every level
+ * of the trees on the device until the call returns (1.2 KB per proof) and, when the batch fails, searches them from the chunk roots down: a round fetches
+ * the children of the nodes that failed (one small kernel, one copy) and the host finishes each as it finishes a batch, up to 16 in
+ * parallel.  A node that passes clears its range, a leaf that fails is an invalid proof.  Before every round a cost rule
+ * (csrc/locate.hpp) compares the rounds that are left with the per-proof route on the proofs still in doubt, and hands those to
+ * zkhip_verifier_verify_batch's kernels when that is cheaper (many invalid proofs spread wide).  An all-valid batch costs what
+ * zkhip_verifier_verify_all costs.  A batch above 2^20 proofs is cut into consecutive located batches.
+ * verdict: count bytes.  On a handle of zkhip_verifier_new: 1 / 0 as zkhip_verifier_verify_batch.  On a handle of
+ * zkhip_verifier_new_checked: the status byte of zkhip_verifier_verify_batch_checked - the point checks run in front, a refused proof
+ * is left out of every node and every sum and gets its refusal byte.
+ * rho: as zkhip_verifier_verify_all (count x 2 words, none zero, or NULL to draw them from the OS).
+ * PRECONDITIONS on an unchecked handle: those of zkhip_verifier_verify_all, for the same reason and for every node: the argument
+ * rests on GT elements of order r, so every point must be fully reduced, on its curve and of order r (or infinity).  Proofs
+ * somebody else made go through a checked handle.
+ * stats (may be NULL): what the call did - chunks whose root failed, rounds and node tests of the descent (the chunk round included),
+ * proofs handed to the per-proof route, proofs found invalid (REJECT / 0), and the host clock time of the descent and of that route.
+ * zkhip_groth16_verify_batch_located: the same route on the host alone (no device, no zkhip_init), the one the device route is
+ * pinned on: the nodes' values come from the host's Miller loops, the descent is the same code.  Like zkhip_groth16_verify_all it
+ * looks at the curve first: a proof with a point off its curve gets 0 and is left out, a key with one fails every proof.  ok: 1 / 0. */
+typedef struct {
+  uint32_t chunks_failed, rounds, node_tests, finish_proofs, invalid;
+  double descent_ms, finish_ms;
+} zkhip_locate_stats;
+int zkhip_verifier_verify_batch_located(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                                        const uint64_t* rho, uint8_t* verdict, zkhip_locate_stats* stats);
+int zkhip_groth16_verify_batch_located(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24],
+                                       const uint64_t* vk_abc, size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs_affine,
+                                       size_t count, const uint64_t* rho, uint8_t* ok, zkhip_locate_stats* stats);
 
 /* ---- the wrapping (aggregator) circuit: host code, no device needed ------------------------------- */
 /* Nested objects are over BLS12-377, whose base field is Fr of BW6-761: coordinates are 6-limb Montgomery
@@ -905,6 +938,21 @@ int zkhip_internal_verify_all_value(int route, zkhip_verifier* v, const uint64_t
 int zkhip_internal_key_check_set_chunk(size_t points);
 int zkhip_internal_key_check_last_ms(double out_ms[4 + ZKHIP_KEY_ELEMENTS]);
 int zkhip_internal_verify_all_finish_ms(const zkhip_verifier* v, double* ms);
+/* verify_batch_located: zkhip_verifier_verify_batch_located by route - 1: the device route; 0: the host route of
+ * zkhip_groth16_verify_batch_located under the handle's key, without its curve check, and on a checked handle behind the host's point
+ * checks, with the handle's kind of verdict bytes.  rho is required.  value (may be NULL): the REDUCED GT value of the batch's combined
+ * check, 72 ABI limbs - what zkhip_internal_verify_all_value gives under the same rho (of the last located batch of a call that was cut).
+ * locate_trace: every node the last located call on this handle tested (either route; the last located batch of a call that was cut),
+ * in the order of the rounds: chunk, level (0: a single proof), index within the level, passed, and the REDUCED value of the node's
+ * combined check (6 x 12 ABI limbs; one iff passed).  *count gets the number of nodes; at most cap are written to out (may be NULL). */
+typedef struct {
+  uint32_t chunk, level, passed, reserved;
+  uint64_t index;
+  uint64_t value[72];
+} zkhip_locate_node;
+int zkhip_internal_verify_batch_located(int route, zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                                        const uint64_t* rho, uint8_t* verdict, zkhip_locate_stats* stats, uint64_t* value);
+int zkhip_internal_locate_trace(const zkhip_verifier* v, zkhip_locate_node* out, size_t cap, size_t* count);
 /* Test hooks of the nested pairing kernels (no counterpart).
  * fq12_selftest: n independent operand sets through the per-lane bodies of pairing_bls.cuh inside a real kernel, sixteen lanes per
  * set: op 0 = a b, 1 = a^2, 2 = a (b_0 + b_1 w + b_3 w^3 + b_7 w^7 + b_9 w^9) (the sparse line product; b's other coefficients are

@@ -12,7 +12,11 @@ on all-valid batches of 1 .. 65,536 proofs, the routes taking turns in one run, 
 combined time; and the host route (groth16_verify_all, 16 threads) once per batch.  CONDITIONS: the per-proof route equals the parent's
 within the spread of its own repeats (no kernel of it changed); the combined batch at 16,384 proofs takes at most half the per-proof
 batch's time.
-Usage: python tools/verify_ab.py [--out FILE] [--stream N] [--gpu-slots K] [--combined [--parent-lib libzkhip.so]]"""
+--located writes profiles/verify_locate.txt: per-proof verdicts by way of the combined check (Verifier.verify_batch_located) beside
+Verifier.verify_all, the per-proof route and today's fallback (verify_batch_combined: combined, then per-proof) on batches of 1,024 /
+16,384 / 65,536 proofs with 0, 1, 2, 16 and 1 % invalid statements at seeded positions, the routes taking turns, medians of five with
+their spreads, the parent build's verify_all and per-proof route beside them with --parent-lib; and the cost rule's constants.
+Usage: python tools/verify_ab.py [--out FILE] [--stream N] [--gpu-slots K] [--combined | --located] [--parent-lib libzkhip.so]"""
 import argparse
 import os
 import sys
@@ -55,6 +59,14 @@ class ParentVerifier:
         ok = np.zeros(prf.shape[0], dtype=np.uint8)
         assert self.lib.zkhip_verifier_verify_batch(self.handle, self.p(inp), self.p(prf), prf.shape[0], ok.ctypes.data) == 0
         return ok.astype(bool)
+
+    def verify_all(self, inp, prf):
+        import ctypes
+        ok = ctypes.c_int(0)
+        self.lib.zkhip_verifier_verify_all.argtypes = [ctypes.c_void_p, type(self.p(inp)), type(self.p(inp)), ctypes.c_size_t, ctypes.c_void_p,
+                                                       ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+        assert self.lib.zkhip_verifier_verify_all(self.handle, self.p(inp), self.p(prf), prf.shape[0], None, ctypes.byref(ok), None) == 0
+        return bool(ok.value)
 
     def free(self):
         self.lib.zkhip_verifier_free(self.handle)
@@ -121,6 +133,116 @@ def combined_table(say, zkhip, vk, pool, pool_in, parent_lib):
     return gate and same
 
 
+LOCATED_COUNTS = (1024, 16384, 65536)
+LOCATED_BAD = (0, 1, 2, 16, "1 %")
+LOCATED_ROUNDS = 5
+
+
+def located_table(say, zkhip, vk, pool, pool_in, bad_proof, bad_in, parent_lib, counts=LOCATED_COUNTS):
+    """the located route beside the combined check, the per-proof route and today's fallback (combined, then per-proof), taking turns
+    on the same batches with 0, 1, 2, 16 and 1 % invalid statements at seeded positions; the parent build's two routes beside them"""
+    n_pool = len(pool)
+    ver = zkhip.Verifier(vk)
+    parent = ParentVerifier(parent_lib, vk) if parent_lib else None
+    routes = [("located", lambda i, p: list(ver.verify_batch_located(i, p))),
+              ("combined", lambda i, p: ver.verify_all(i, p)),
+              ("per-proof", lambda i, p: list(ver.verify_batch(i, p))),
+              ("fallback", lambda i, p: list(ver.verify_batch_combined(i, p)))]
+    if parent:
+        routes += [("parent-combined", lambda i, p: parent.verify_all(i, p)), ("parent-per-proof", lambda i, p: list(parent.verify_batch(i, p)))]
+    for _, fn in routes:
+        fn(pool_in[:1], pool[:1])                            # work space
+    # the per-proof route by count: what the cost rule takes for handing proofs over (its time rises in steps of 4,096 proofs)
+    steps = {}
+    for count in (1024, 2048, 4096, 4097, 6144, 8192, 8193, 12288, 12289, 16384):
+        idx = np.arange(count) % n_pool
+        inp, prf = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
+        ver.verify_batch(inp, prf)
+        ms = []
+        for _ in range(LOCATED_ROUNDS):
+            t = time.perf_counter()
+            assert ver.verify_batch(inp, prf).all()
+            ms.append((time.perf_counter() - t) * 1e3)
+        steps[count] = sorted(ms)[LOCATED_ROUNDS // 2]
+        say("per-proof route, %6d proofs: median %.1f ms (%.1f .. %.1f)" % (count, steps[count], min(ms), max(ms)))
+    say("%8s %8s %-16s %10s %10s %10s   %s" % ("count", "invalid", "route", "median ms", "min ms", "max ms", "the located route's last run"))
+    ok_all, cases, rounds_ms = True, {}, {}
+    for count in counts:
+        for spec in LOCATED_BAD:
+            nbad = max(1, count // 100) if spec == "1 %" else spec
+            where = np.random.RandomState(count + nbad).choice(count, nbad, replace=False)
+            idx = np.arange(count) % n_pool
+            inp, prf = np.ascontiguousarray(pool_in[idx]), np.ascontiguousarray(pool[idx])
+            inp[where], prf[where] = bad_in, bad_proof
+            want = np.ones(count, dtype=bool)
+            want[where] = False
+            for _, fn in routes:
+                fn(inp, prf)                                  # the work space of this size
+            ms = {name: [] for name, _ in routes}
+            for _ in range(LOCATED_ROUNDS):
+                for name, fn in routes:
+                    t = time.perf_counter()
+                    got = fn(inp, prf)
+                    ms[name].append((time.perf_counter() - t) * 1e3)
+                    if name.endswith("combined"):
+                        assert got is (nbad == 0), "%s verdict at count %d, %s invalid" % (name, count, spec)
+                    else:
+                        assert (np.array(got) == want).all(), "%s verdicts at count %d, %s invalid" % (name, count, spec)
+                    if name == "located":
+                        st = ver.last_locate_stats()
+            med = {name: sorted(v)[LOCATED_ROUNDS // 2] for name, v in ms.items()}
+            spread = {name: max(v) - min(v) for name, v in ms.items()}
+            for name, _ in routes:
+                note = ""
+                if name == "located":
+                    note = "chunks failed %d, rounds %d, node tests %d, to the per-proof route %d, descent %.1f ms, per-proof route %.1f ms" % (
+                        st["chunks_failed"], st["rounds"], st["node_tests"], st["finish_proofs"], st["descent_ms"], st["finish_ms"])
+                say("%8d %8s %-16s %10.2f %10.2f %10.2f   %s" % (count, spec, name, med[name], min(ms[name]), max(ms[name]), note))
+            if nbad == 0:
+                inside = abs(med["located"] - med["combined"]) <= spread["combined"]
+                say("%8d all valid: located - combined = %+.2f ms, spread of the combined repeats %.2f ms: %s" % (
+                    count, med["located"] - med["combined"], spread["combined"], "inside" if inside else "OUTSIDE"))
+                if parent:
+                    for a, b in (("combined", "parent-combined"), ("per-proof", "parent-per-proof")):
+                        agree = abs(med[a] - med[b]) <= spread[a]
+                        ok_all = ok_all and agree
+                        say("%8d no regression: %s - parent's = %+.2f ms, spread of its repeats %.2f ms: %s" % (count, a, med[a] - med[b], spread[a],
+                                                                                                              "within" if agree else "OUTSIDE"))
+            else:
+                say("%8d %s invalid: located / fallback = %.3f (%.1f ms below; spreads %.1f and %.1f ms)" % (
+                    count, spec, med["located"] / med["fallback"], med["fallback"] - med["located"], spread["located"], spread["fallback"]))
+                cases[(count, spec)] = (med["located"], med["fallback"], spread["located"], spread["fallback"], dict(st))
+    # the conditions, once every count has its one-proof descent: a node round of a count is that descent over its paid rounds (every
+    # round of a one-proof descent is one load of the threads; a batch of one chunk knows its root already)
+    for count in counts:
+        if (count, 1) not in cases:
+            continue
+        loc, fall, s_loc, s_fall, st = cases[(count, 1)]
+        paid = st["rounds"] - (1 if count <= 16384 else 0)
+        rounds_ms[count] = st["descent_ms"] / paid
+        line = "%8d one node round = %.1f ms (the one-proof descent, %.1f ms / %d paid rounds)" % (count, rounds_ms[count], st["descent_ms"], paid)
+        if count >= 16384:
+            gate = fall - loc > s_loc + s_fall
+            ok_all = ok_all and gate
+            line += "; CONDITION one invalid: below the fallback by more than both spreads (%.1f > %.1f + %.1f ms): %s" % (
+                fall - loc, s_loc, s_fall, "met" if gate else "MISSED")
+        say(line)
+        if (count, "1 %") in cases:
+            loc, fall, _, _, st = cases[(count, "1 %")]
+            gate = loc <= fall + rounds_ms[count]
+            ok_all = ok_all and gate
+            say("%8d CONDITION 1 %% invalid: within one node round of the fallback (%+.1f ms against %.1f ms; its descent took %.1f ms): %s" % (
+                count, loc - fall, rounds_ms[count], st["descent_ms"], "met" if gate else "MISSED"))
+    node_round = rounds_ms.get(16384)
+    if node_round is not None:
+        say("the cost rule's constants from this run (csrc/pairing_locate.hpp LOCATE_COST): node test %.1f ms; per-proof route on up to 4,096 / 8,192 / "
+            "12,288 / 16,384 proofs %.1f / %.1f / %.1f / %.1f ms" % (node_round, steps[4096], steps[8192], steps[12288], steps[16384]))
+    if parent:
+        parent.free()
+    ver.free()
+    return ok_all
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "verify_gpu.txt"))
@@ -128,10 +250,14 @@ def main():
     ap.add_argument("--gpu-slots", type=int, default=24)
     ap.add_argument("--pool", type=int, default=16, help="distinct proofs (the batches repeat them; the last one gets a bumped input)")
     ap.add_argument("--combined", action="store_true", help="the combined check against the per-proof route; writes profiles/verify_combined.txt")
-    ap.add_argument("--parent-lib", default=None, help="with --combined: a libzkhip.so built from the parent commit, for its per-proof route in the same turns")
+    ap.add_argument("--parent-lib", default=None, help="with --combined or --located: a libzkhip.so built from the parent commit, for its routes in the same turns")
+    ap.add_argument("--located", action="store_true", help="the located route against the combined check, the per-proof route and the fallback; writes profiles/verify_locate.txt")
+    ap.add_argument("--located-counts", default=None, help="with --located: batch sizes, comma separated (default 1024,16384,65536)")
     args = ap.parse_args()
     if args.combined and args.out.endswith("verify_gpu.txt"):
         args.out = os.path.join(os.path.dirname(args.out), "verify_combined.txt")
+    if args.located and args.out.endswith("verify_gpu.txt"):
+        args.out = os.path.join(os.path.dirname(args.out), "verify_locate.txt")
     import bench
     from zecale_amd import zkhip
     zkhip.init(0)
@@ -155,6 +281,16 @@ def main():
     prover.free()
     pool_in = np.tile(prim, (args.pool, 1, 1))
     pool_in[-1, 0, 0] ^= np.uint64(1)                       # one invalid statement in the pool
+    if args.located:
+        say("# Groth16 verification, batch-2 wrapping key (%d primary inputs): per-proof verdicts by way of the combined check (located) vs the combined "
+            "check alone, the per-proof route and today's fallback; medians of %d alternating runs" % (n_in, LOCATED_ROUNDS))
+        counts = tuple(int(c) for c in args.located_counts.split(",")) if args.located_counts else LOCATED_COUNTS
+        ok = located_table(say, zkhip, vk, pool[:-1], pool_in[:-1], pool[-1], pool_in[-1], args.parent_lib, counts)
+        crs.free(); kp.free(); agg.free()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return 0 if ok else 1
     if args.combined:
         say("# Groth16 verification, batch-2 wrapping key (%d primary inputs): one combined check per batch vs the per-proof route, all-valid batches" % n_in)
         ok = combined_table(say, zkhip, vk, pool[:-1], pool_in[:-1], args.parent_lib)

@@ -2,10 +2,12 @@
 #include <string.h>
 
 #include "api_internal.hpp"
+#include "device_buffer.hpp"
 #include "ec.cuh"
 #include "pairing_host.hpp"
 #include "pairing.cuh"
 #include "pairing.h"
+#include "pairing_locate.hpp"
 
 using namespace zkhip::api;
 
@@ -14,6 +16,7 @@ using namespace zkhip::api;
 struct zkhip_verifier {
   PairingCtx* ctx;
   int device;
+  std::vector<host::LocateTraceNode> trace;      // of the last located call (zkhip_internal_locate_trace)
 };
 
 // ---- Groth16 verification in batches on the device (pairing.hip)
@@ -25,7 +28,7 @@ static int verifier_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2,
   PairingCtx* ctx = nullptr;
   const int rc = pairing_ctx_new(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs, checked, &ctx, t_err, sizeof t_err);
   if (rc != ZKHIP_OK) return rc;
-  *out = new zkhip_verifier{ctx, cur_dev()};
+  *out = new zkhip_verifier{ctx, cur_dev(), {}};
   return ZKHIP_OK;
 }
 
@@ -52,6 +55,54 @@ static void verify_all_host(const host::CombineKey& key, const uint64_t* inputs,
   HJac s_c = HJac::infinity();
   combined_proofs_host(key.n_inputs, inputs, proofs, count, rho, skip, hw > 16 ? 16 : hw, product, s_c, sums);
   fq6_to_limbs(combined_value(key, sums, s_c, product), value);
+}
+
+static void add_locate_stats(zkhip_locate_stats& sum, const zkhip_locate_stats& s) {
+  sum.chunks_failed += s.chunks_failed; sum.rounds += s.rounds; sum.node_tests += s.node_tests; sum.finish_proofs += s.finish_proofs;
+  sum.invalid += s.invalid; sum.descent_ms += s.descent_ms; sum.finish_ms += s.finish_ms;
+}
+
+// The located route on the host alone, cut into located batches.  left_out: null, or per proof the byte a proof that is left out
+// everywhere gets (0: it takes part).  bytes: the verdicts are status bytes (ACCEPT 0 / REJECT 1), else 1 / 0.  The per-proof route of
+// the host is verify_one_host, the proofs dealt to the threads of a round.
+static int located_host(const host::CombineKey& key, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho,
+                        const uint8_t* left_out, bool bytes, uint8_t* verdict, zkhip_locate_stats* stats, std::vector<host::LocateTraceNode>* trace,
+                        uint64_t* value_out = nullptr) {
+  using namespace host;
+  const uint8_t accept = bytes ? (uint8_t)ZKHIP_VERIFY_ACCEPT : 1, reject = bytes ? (uint8_t)ZKHIP_VERIFY_REJECT : 0;
+  const unsigned threads = locate_threads();
+  const size_t ni = key.n_inputs;
+  zkhip_locate_stats sum = zkhip_locate_stats();
+  const int rc = for_each_chunk(count, PAIRING_LOCATE_MAX, [&](size_t lo, size_t m) -> int {
+    const uint64_t *in = inputs + lo * ni * 6, *pr = proofs + lo * 72;
+    const uint8_t* skip = left_out ? left_out + lo : nullptr;
+    std::vector<uint8_t> state;
+    zkhip_locate_stats s;
+    uint64_t value[72];
+    auto finish = [&](const std::vector<size_t>& list) -> int {
+      const unsigned nt = threads > list.size() ? (unsigned)list.size() : threads;
+      auto work = [&](unsigned t) {
+        for (size_t i = t; i < list.size(); i += nt)
+          if (!skip || !skip[list[i]]) verdict[lo + list[i]] = verify_one_host(key, in + list[i] * ni * 6, pr + list[i] * 72) ? accept : reject;
+      };
+      std::vector<std::thread> pool;
+      for (unsigned t = 1; t < nt; t++) pool.emplace_back(work, t);
+      work(0);
+      for (auto& th : pool) th.join();
+      return 0;
+    };
+    for (size_t i = 0; i < m; i++) verdict[lo + i] = skip && skip[i] ? skip[i] : accept;
+    const int r = located_batch_host(key, in, pr, m, rho + lo * 2, skip, threads, LOCATE_COST, finish, state, s, trace, value);
+    if (r) return r;
+    for (size_t i = 0; i < m; i++)
+      if (state[i] == locate::INVALID) verdict[lo + i] = reject;
+    for (size_t i = 0; i < m; i++) s.invalid += verdict[lo + i] == reject && (!skip || !skip[i]);
+    add_locate_stats(sum, s);
+    if (value_out) memcpy(value_out, value, sizeof value);
+    return ZKHIP_OK;
+  });
+  if (stats) *stats = sum;
+  return rc;
 }
 
 #pragma GCC visibility pop
@@ -102,6 +153,29 @@ int zkhip_groth16_verify_all(const uint64_t vk_alpha_g1[24], const uint64_t vk_b
   const host::CombineKey key = {vk_alpha_g1, neg_g2, neg_beta, neg_delta, vk_abc, n_inputs};
   verify_all_host(key, inputs, proofs_affine, count, rho, nullptr, value);
   *all_ok = host::gt_is_one(value) ? 1 : 0;
+  return ZKHIP_OK;
+}
+
+// ---- located batches on the host alone (pairing_locate.hpp): the route zkhip_verifier_verify_batch_located is pinned on
+int zkhip_groth16_verify_batch_located(const uint64_t vk_alpha_g1[24], const uint64_t vk_beta_g2[24], const uint64_t vk_delta_g2[24], const uint64_t* vk_abc,
+                                       size_t n_inputs, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, const uint64_t* rho,
+                                       uint8_t* ok, zkhip_locate_stats* stats) {
+  if (!vk_alpha_g1 || !vk_beta_g2 || !vk_delta_g2 || !vk_abc) return fail(ZKHIP_ERR_ARG, "null pointer");
+  if (stats) *stats = zkhip_locate_stats();
+  if (count == 0) return ZKHIP_OK;
+  if (!proofs_affine || !ok || (n_inputs && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  int rc = combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  // well-formedness first, as zkhip_groth16_verify: a point off its curve never enters the pairing arithmetic
+  if (!host::key_on_curve(vk_alpha_g1, vk_beta_g2, vk_delta_g2, vk_abc, n_inputs)) { memset(ok, 0, count); return ZKHIP_OK; }
+  std::vector<uint8_t> off(count);
+  for (size_t i = 0; i < count; i++) off[i] = host::proof_on_curve(proofs_affine + i * 72) ? 0 : 0xFF;
+  uint64_t neg_g2[24], neg_beta[24], neg_delta[24];
+  host::neg_g2_generator(neg_g2); host::neg_point_abi(vk_beta_g2, neg_beta); host::neg_point_abi(vk_delta_g2, neg_delta);
+  const host::CombineKey key = {vk_alpha_g1, neg_g2, neg_beta, neg_delta, vk_abc, n_inputs};
+  if ((rc = located_host(key, inputs, proofs_affine, count, rho, off.data(), false, ok, stats, nullptr)) != ZKHIP_OK) return fail(rc, "located batch");
+  for (size_t i = 0; i < count; i++) if (off[i]) ok[i] = 0;
   return ZKHIP_OK;
 }
 
@@ -174,6 +248,65 @@ int zkhip_verifier_verify_all(zkhip_verifier* v, const uint64_t* inputs, const u
   bool ok = host::gt_is_one(value);
   for (size_t i = 0; status && ok && i < count; i++) ok = status[i] == 0;      // a refused proof is left out of the product and fails the batch
   *all_ok = ok ? 1 : 0;
+  return ZKHIP_OK;
+}
+int zkhip_internal_verify_batch_located(int route, zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count,
+                                        const uint64_t* rho, uint8_t* verdict, zkhip_locate_stats* stats, uint64_t* value) {
+  if (route != 0 && route != 1) return fail(ZKHIP_ERR_ARG, "route 0 (host) or 1 (GPU)");
+  if (!v) return fail(ZKHIP_ERR_ARG, "null verifier");
+  zkhip_locate_stats sum = zkhip_locate_stats();
+  if (stats) *stats = sum;
+  v->trace.clear();
+  if (count == 0) return ZKHIP_OK;
+  const size_t ni = pairing_ctx_num_inputs(v->ctx);
+  if (!proofs_affine || !verdict || (ni && !inputs)) return fail(ZKHIP_ERR_ARG, "null pointer");
+  std::vector<uint64_t> own;
+  int rc = combine_scalars(rho, count, own, &rho);
+  if (rc != ZKHIP_OK) return rc;
+  const bool checked = pairing_ctx_checked(v->ctx);
+  if (route == 0) {
+    host::CombineKey key;
+    key.n_inputs = ni;
+    pairing_ctx_key(v->ctx, &key.alpha, &key.neg_g2, &key.neg_beta, &key.neg_delta, &key.abc);
+    std::vector<uint8_t> refused;
+    if (checked) {                                 // the checked route's refusals, on the host: such a proof is left out
+      refused.resize(count);
+      for (size_t i = 0; i < count; i++) {
+        uint8_t e[4];
+        host::proof_check_codes_host(proofs_affine + i * 72, inputs + i * ni * 6, ni, e);
+        refused[i] = verify_refusal(e);
+      }
+    }
+    if ((rc = located_host(key, inputs, proofs_affine, count, rho, checked ? refused.data() : nullptr, checked, verdict, stats, &v->trace, value)) != ZKHIP_OK)
+      return fail(rc, "located batch");
+    return ZKHIP_OK;
+  }
+  BIND(v);
+  rc = for_each_chunk(count, PAIRING_LOCATE_MAX, [&](size_t lo, size_t m) -> int {      // a batch above the bound: consecutive located batches
+    zkhip_locate_stats s;
+    uint64_t piece[72];
+    const int r = pairing_verify_located(v->ctx, inputs + lo * ni * 6, proofs_affine + lo * 72, m, rho + lo * 2, checked, verdict + lo, &s, piece, &v->trace,
+                                         t_err, sizeof t_err);
+    if (r == ZKHIP_OK) add_locate_stats(sum, s);
+    if (r == ZKHIP_OK && value) memcpy(value, piece, sizeof piece);
+    return r;
+  });
+  if (stats) *stats = sum;
+  return rc;
+}
+int zkhip_verifier_verify_batch_located(zkhip_verifier* v, const uint64_t* inputs, const uint64_t* proofs_affine, size_t count, const uint64_t* rho,
+                                        uint8_t* verdict, zkhip_locate_stats* stats) {
+  return zkhip_internal_verify_batch_located(1, v, inputs, proofs_affine, count, rho, verdict, stats, nullptr);
+}
+int zkhip_internal_locate_trace(const zkhip_verifier* v, zkhip_locate_node* out, size_t cap, size_t* count) {
+  if (!v || !count) return fail(ZKHIP_ERR_ARG, "null pointer");
+  *count = v->trace.size();
+  for (size_t i = 0; out && i < v->trace.size() && i < cap; i++) {
+    const host::LocateTraceNode& t = v->trace[i];
+    out[i].chunk = t.node.chunk; out[i].level = t.node.level; out[i].passed = t.passed ? 1 : 0; out[i].reserved = 0;
+    out[i].index = t.node.index;
+    memcpy(out[i].value, t.value, sizeof t.value);
+  }
   return ZKHIP_OK;
 }
 void zkhip_verifier_free(zkhip_verifier* v) {

@@ -54,6 +54,24 @@ constexpr int pairing_tree_levels(size_t n) {
   for (; pairing_strips(n) > 1; n = pairing_strips(n)) levels++;
   return levels;
 }
+// located batches keep every level of a chunk's trees in ONE buffer, level after level: level 0 holds the n values the tree starts
+// from, level k + 1 the pairing_strips of level k that launch k writes, the last level (number pairing_tree_levels(n)) the one root.
+// Node s of level k covers the values [s 8^k, min((s + 1) 8^k, n)).
+constexpr size_t pairing_level_size(size_t n, int k) {
+  for (; k > 0; k--) n = pairing_strips(n);
+  return n;
+}
+// where level k starts in that buffer: the sizes of the levels below it
+constexpr size_t pairing_level_offset(size_t n, int k) {
+  size_t off = 0;
+  for (; k > 0; k--, n = pairing_strips(n)) off += n;
+  return off;
+}
+// values in that buffer: every level, the root included
+constexpr size_t pairing_tree_nodes(size_t n) { return pairing_level_offset(n, pairing_tree_levels(n)) + 1; }
+// a call of the located route retains at most this many proofs' trees at a time (1.2 KB per proof: 1.3 GB); a larger batch is cut
+// into consecutive located batches
+constexpr size_t PAIRING_LOCATE_MAX = (size_t)1 << 20;
 
 ZK_HD ZK_INL Fq fq_select(bool c, const Fq& a, const Fq& b) {
   Fq r;

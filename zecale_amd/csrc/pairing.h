@@ -3,9 +3,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/zkhip.h"
 
 namespace zkhip {
+namespace host {
+struct LocateTraceNode;      // pairing_locate.hpp
+}
 
 // A stream and the device work space of one batch in flight, plus (verifier handles) the key: everything a zkhip_verifier owns.
 // Lives on the device that was current when it was made; the caller binds its thread to that device before every call.
@@ -33,6 +38,12 @@ int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* 
 // refusal byte, 0 for a proof nothing refuses.  status without checked: ZKHIP_ERR_STATE.
 int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
                        uint8_t* status, uint64_t* value, char* errbuf, size_t errlen);
+// Per-proof verdicts by way of the combined check (zkhip.h "located batches"), count <= PAIRING_LOCATE_MAX: pairing_verify_all with the
+// levels of its trees retained, and on a batch that fails the descent of locate.hpp.  verdict[i]: 1 / 0, or with checked the status
+// byte of pairing_verify_batch.  value: the batch's reduced GT value.  trace: null, or where every node tested goes.
+int pairing_verify_located(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                           uint8_t* verdict, zkhip_locate_stats* stats, uint64_t* value, std::vector<host::LocateTraceNode>* trace, char* errbuf,
+                           size_t errlen);
 // the host's time behind the last chunk of the last pairing_verify_all: the shared pairs and the final exponentiation
 double pairing_ctx_last_finish_ms(const PairingCtx* c);
 // the key of a verifier context in the form of pairing_host.hpp's CombineKey (G2 points negated), for the host route on a handle

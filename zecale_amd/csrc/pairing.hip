@@ -15,6 +15,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <chrono>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -25,6 +26,7 @@
 #include "pairing.cuh"
 #include "pairing.h"
 #include "pairing_host.hpp"
+#include "pairing_locate.hpp"
 
 namespace zkhip {
 
@@ -317,6 +319,25 @@ __global__ void __launch_bounds__(64) k_g1_sum(const XYZZ* __restrict__ in, size
   else out[s] = acc;
 }
 
+// ---- located batches: the values of `count` tree nodes as ABI limbs, 96 per node: the unreduced product (6 x 12, as the last
+// k_gt_product launch writes it) and the sum as an affine point (24, all zero for infinity, as the last k_g1_sum launch).  The host
+// names each node by where its values lie in the retained buffers.  A group of eight lanes owns a node, the cut of the kernels
+// above: six coefficient lanes reduce one coefficient each, the seventh inverts for the point, the eighth idles.  No LDS, no barrier;
+// a round has a few hundred nodes at the most, so the launch is latency, and the lanes of one node write 768 contiguous bytes.
+struct TreeNodeRef {
+  const Fq* f;         // six coefficients [4]
+  const XYZZ* c;       // X [10], Y [4]
+};
+__global__ void __launch_bounds__(64) k_tree_nodes_abi(const TreeNodeRef* __restrict__ refs, size_t count, uint64_t* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t node = t / PAIRING_GROUP;
+  const int k = (int)(t % PAIRING_GROUP);
+  if (node >= count) return;
+  const TreeNodeRef r = refs[node];
+  if (k < 6) fp_to_abi<FqParams>(r.f[k], out + node * 96 + k * 12);         // [4] -> canonical
+  else if (k == 6) xyzz_to_affine_abi(*r.c, out + node * 96 + 72);
+}
+
 namespace {
 int bit_length(const uint64_t* e, int limbs) {
   int top = limbs * 64 - 1;
@@ -352,6 +373,14 @@ struct PairingCtx {
   DeviceBuffer<Fq> d_f2;                            // the other buffer of the product tree
   std::vector<uint64_t> h_b;
   double finish_ms = 0;
+  // located batches (pairing_verify_located): every level of a chunk's two trees, chunk after chunk of the batch in flight
+  struct KeptTrees {
+    DeviceBuffer<Fq> f;                             // pairing_tree_nodes(m) x 6 coefficients
+    DeviceBuffer<XYZZ> c;                           // pairing_tree_nodes(m)
+  };
+  std::vector<std::unique_ptr<KeptTrees>> kept;
+  DeviceBuffer<TreeNodeRef> d_refs;                 // the nodes of a round and their values (k_tree_nodes_abi)
+  DeviceBuffer<uint64_t> d_nodes;
 };
 
 void pairing_ctx_free(PairingCtx* c) { delete c; }     // every buffer, then the stream
@@ -453,14 +482,15 @@ int pairing_ctx_new(const uint64_t* vk_alpha_g1, const uint64_t* vk_beta_g2, con
 // ---- the stages of a chunk.  `combined` is pairing_verify_all's route, `checked` the one with k_point_check in front.
 
 // The work space of a chunk of m products.  The inputs are on the device for k_acc_terms and for k_point_check; only the per-proof
-// route has terms, only the combined route its scalars, scaled points and the second buffers of its trees.
-static int reserve_chunk(PairingCtx* c, size_t m, bool combined, bool checked, char* errbuf, size_t errlen) {
+// route has terms, only the combined route its scalars, scaled points and the two buffers of each of its trees.  keep >= 0, the
+// located route: the trees of this chunk of the batch go, every level, into retained buffers of their own instead.
+static int reserve_chunk(PairingCtx* c, size_t m, bool combined, bool checked, char* errbuf, size_t errlen, int keep = -1) {
   ZK_HIP_TRY("pairing", c->d_g1.reserve(m * 4 * 24));
   ZK_HIP_TRY("pairing", c->d_g2.reserve(m * 4 * 24));
   ZK_HIP_TRY("pairing", c->d_gt.reserve(m * 72));
   ZK_HIP_TRY("pairing", c->d_pairs.reserve(m * 4));
   ZK_HIP_TRY("pairing", c->d_inf.reserve(m * 4));
-  ZK_HIP_TRY("pairing", c->d_f.reserve(m * 6));
+  if (keep < 0) ZK_HIP_TRY("pairing", c->d_f.reserve(m * 6));      // (a kept chunk's Miller values are level 0 of its retained tree)
   ZK_HIP_TRY("pairing", c->d_codes.reserve(m * 4));
   if (!combined || checked) ZK_HIP_TRY("pairing", c->d_inputs.reserve(m * c->n_inputs * 6));
   if (!combined) {
@@ -470,6 +500,12 @@ static int reserve_chunk(PairingCtx* c, size_t m, bool combined, bool checked, c
   ZK_HIP_TRY("pairing", c->d_rho.reserve(m * 2));
   ZK_HIP_TRY("pairing", c->d_ra.reserve(m * 24));
   ZK_HIP_TRY("pairing", c->d_b.reserve(m * 24));
+  if (keep >= 0) {
+    while (c->kept.size() <= (size_t)keep) c->kept.emplace_back(new PairingCtx::KeptTrees());
+    ZK_HIP_TRY("pairing", c->kept[keep]->f.reserve(pairing_tree_nodes(m) * 6));
+    ZK_HIP_TRY("pairing", c->kept[keep]->c.reserve(pairing_tree_nodes(m)));
+    return ZKHIP_OK;
+  }
   ZK_HIP_TRY("pairing", c->d_res.reserve(72 + 24));
   ZK_HIP_TRY("pairing", c->d_rc.reserve(m));
   ZK_HIP_TRY("pairing", c->d_rc2.reserve(pairing_strips(m)));
@@ -592,6 +628,25 @@ int pairing_verify_batch(PairingCtx* c, const uint64_t* inputs, const uint64_t* 
   });
 }
 
+// The front of a combined chunk, up to the values its trees start from: the chunk staged and uploaded, the point checks on the checked
+// route, rho A and rho C (k_rho_scale), and the one-pair Miller loop.  f0: m x 6 unreduced Miller values; rc0: m sums' summands.
+static int enqueue_combined_leaves(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, const uint64_t* rho, size_t m, bool checked, Fq* f0,
+                                   XYZZ* rc0, char* errbuf, size_t errlen) {
+  int rc;
+  stage_chunk(c, proofs, m, true, checked);
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_b, c->h_b.data(), m * 192, hipMemcpyHostToDevice, c->st));
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_rho, rho, m * 16, hipMemcpyHostToDevice, c->st));
+  if (checked && (rc = upload_g2_and_inputs(c, inputs, m, errbuf, errlen)) != ZKHIP_OK) return rc;
+  const uint32_t* flags = checked ? enqueue_point_check(c, m) : nullptr;
+  hipLaunchKernelGGL(k_rho_scale, dim3(blocks_for(2 * m, 64)), dim3(64), 0, c->st, c->d_g1.get(), c->d_rho.get(), m, c->d_ra.get(), rc0, flags);
+  hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_ra.get(), c->d_b.get(), c->d_const + 72, m, c->d_pairs.get(),
+                     c->d_inf.get(), flags, 1);
+  hipLaunchKernelGGL(k_miller, dim3(blocks_for(m, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs.get(), c->d_inf.get(), 1, m,
+                     c->d_const.get(), f0);
+  return ZKHIP_OK;
+}
+
 // One random-combination check of the whole batch.  Per chunk the device scales A and C by rho (k_rho_scale), runs the existing
 // Miller loop with ONE pair per proof on (rho_i A_i, B_i) and reduces the unreduced values to one product (k_gt_product) and the
 // rho_i C_i to one sum (k_g1_sum), relaunched until one value is left; the host multiplies and adds the chunks' results, forms the
@@ -615,17 +670,8 @@ int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* pr
   const int rc_all = for_each_chunk(count, PAIRING_CHUNK, [&](size_t lo, size_t m) -> int {
     int rc = reserve_chunk(c, m, true, checked, errbuf, errlen);
     if (rc != ZKHIP_OK) return rc;
-    stage_chunk(c, proofs + lo * 72, m, true, checked);
-    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_g1, c->h_g1.data(), m * 96 * 8, hipMemcpyHostToDevice, c->st));
-    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_b, c->h_b.data(), m * 192, hipMemcpyHostToDevice, c->st));
-    ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_rho, rho + lo * 2, m * 16, hipMemcpyHostToDevice, c->st));
-    if (checked && (rc = upload_g2_and_inputs(c, inputs + lo * ni * 6, m, errbuf, errlen)) != ZKHIP_OK) return rc;
-    const uint32_t* flags = checked ? enqueue_point_check(c, m) : nullptr;
-    hipLaunchKernelGGL(k_rho_scale, dim3(blocks_for(2 * m, 64)), dim3(64), 0, c->st, c->d_g1.get(), c->d_rho.get(), m, c->d_ra.get(), c->d_rc.get(), flags);
-    hipLaunchKernelGGL(k_pair_prep, dim3(blocks_for(m, 64)), dim3(64), 0, c->st, c->d_ra.get(), c->d_b.get(), c->d_const + 72, m, c->d_pairs.get(),
-                       c->d_inf.get(), flags, 1);
-    hipLaunchKernelGGL(k_miller, dim3(blocks_for(m, PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, c->d_pairs.get(), c->d_inf.get(), 1, m,
-                       c->d_const.get(), c->d_f.get());
+    if ((rc = enqueue_combined_leaves(c, inputs + lo * ni * 6, proofs + lo * 72, rho + lo * 2, m, checked, c->d_f.get(), c->d_rc.get(), errbuf, errlen)) != ZKHIP_OK)
+      return rc;
     reduce_tree(c->d_f.get(), c->d_f2.get(), m, [&](const Fq* in, size_t n, Fq* out, bool last) {
       hipLaunchKernelGGL(k_gt_product, dim3(blocks_for(pairing_strips(n), PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, in, n, out,
                          last ? c->d_res.get() : nullptr);
@@ -652,6 +698,175 @@ int pairing_verify_all(PairingCtx* c, const uint64_t* inputs, const uint64_t* pr
   const CombineKey key = {c->alpha, c->neg_g2, c->neg_beta, c->neg_delta, c->abc.data(), ni};
   fq6_to_limbs(combined_value(key, sums, s_c, product), value);
   c->finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return ZKHIP_OK;
+}
+
+// ---- located batches.  The combined check with every level of every chunk's trees retained; a batch that fails is searched from the
+// chunk roots down (locate.hpp): a round's nodes come back through k_tree_nodes_abi in one launch and one copy, the host finishes
+// each (pairing_locate.hpp test_nodes), and what the cost rule hands over goes through pairing_verify_batch.
+
+// k_tree_nodes_abi on `n` nodes, and their 96 limbs each on the way to `out`; the caller synchronises
+static int enqueue_tree_nodes(PairingCtx* c, const TreeNodeRef* refs, size_t n, uint64_t* out, char* errbuf, size_t errlen) {
+  ZK_HIP_TRY("pairing", c->d_refs.reserve(n));
+  ZK_HIP_TRY("pairing", c->d_nodes.reserve(n * 96));
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(c->d_refs, refs, n * sizeof(TreeNodeRef), hipMemcpyHostToDevice, c->st));
+  hipLaunchKernelGGL(k_tree_nodes_abi, dim3(blocks_for(n * PAIRING_GROUP, 64)), dim3(64), 0, c->st, c->d_refs.get(), n, c->d_nodes.get());
+  ZK_HIP_TRY("pairing", hipGetLastError());
+  ZK_HIP_TRY("pairing", hipMemcpyAsync(out, c->d_nodes, n * 96 * 8, hipMemcpyDeviceToHost, c->st));
+  return ZKHIP_OK;
+}
+
+int pairing_verify_located(PairingCtx* c, const uint64_t* inputs, const uint64_t* proofs, size_t count, const uint64_t* rho, bool checked,
+                           uint8_t* verdict, zkhip_locate_stats* stats, uint64_t* value, std::vector<host::LocateTraceNode>* trace, char* errbuf,
+                           size_t errlen) {
+  using namespace host;
+  if (checked && !c->checked) {
+    if (errbuf) snprintf(errbuf, errlen, "checked batches need a handle of zkhip_verifier_new_checked");
+    return ZKHIP_ERR_STATE;
+  }
+  if (count > PAIRING_LOCATE_MAX) {
+    if (errbuf) snprintf(errbuf, errlen, "a located batch holds at most %zu proofs", PAIRING_LOCATE_MAX);
+    return ZKHIP_ERR_ARG;
+  }
+  const size_t ni = c->n_inputs;
+  *stats = zkhip_locate_stats();
+  if (trace) trace->clear();
+  struct ReleaseKept {               // the retained trees stay until the call returns, on every path, and no longer
+    PairingCtx* c;
+    ~ReleaseKept() { c->kept.clear(); }
+  } release_kept = {c};
+  std::vector<size_t> chunks, first;
+  std::vector<uint8_t> refused(checked ? count : 0);               // the refusal byte of every proof, 0 where nothing refuses it
+  const uint8_t* skip = checked ? refused.data() : nullptr;
+  std::vector<CombineSums> sums;                                   // chunk by chunk: a chunk's root is tested with its own
+  std::vector<Fq6> root_f;
+  std::vector<HJac> root_c;
+  const int rc_all = for_each_chunk(count, PAIRING_CHUNK, [&](size_t lo, size_t m) -> int {
+    const size_t ci = chunks.size();
+    int rc = reserve_chunk(c, m, true, checked, errbuf, errlen, (int)ci);
+    if (rc != ZKHIP_OK) return rc;
+    Fq* const tf = c->kept[ci]->f.get();
+    XYZZ* const tc = c->kept[ci]->c.get();
+    if ((rc = enqueue_combined_leaves(c, inputs + lo * ni * 6, proofs + lo * 72, rho + lo * 2, m, checked, tf, tc, errbuf, errlen)) != ZKHIP_OK) return rc;
+    size_t n = m;
+    for (int k = 0, levels = pairing_tree_levels(m); k < levels; k++, n = pairing_strips(n)) {      // level k -> level k + 1, at its offset
+      const size_t in = pairing_level_offset(m, k), out = pairing_level_offset(m, k + 1);
+      hipLaunchKernelGGL(k_gt_product, dim3(blocks_for(pairing_strips(n), PAIRING_WG)), dim3(PAIRING_BLOCK), 0, c->st, tf + in * 6, n, tf + out * 6,
+                         (uint64_t*)nullptr);
+      hipLaunchKernelGGL(k_g1_sum, dim3(blocks_for(pairing_strips(n), 64)), dim3(64), 0, c->st, tc + in, n, tc + out, (uint64_t*)nullptr);
+    }
+    ZK_HIP_TRY("pairing", hipGetLastError());
+    const size_t root = pairing_tree_nodes(m) - 1;
+    const TreeNodeRef ref = {tf + root * 6, tc + root};
+    uint64_t res[96];
+    if ((rc = enqueue_tree_nodes(c, &ref, 1, res, errbuf, errlen)) != ZKHIP_OK) return rc;
+    if (checked) ZK_HIP_TRY("pairing", hipMemcpyAsync(c->h_codes.data(), c->d_codes, m * 4, hipMemcpyDeviceToHost, c->st));
+    if (!checked) sums.push_back(range_sums(ni, inputs, rho, nullptr, lo, lo + m));
+    ZK_HIP_TRY("pairing", hipStreamSynchronize(c->st));
+    if (checked) {
+      for (size_t j = 0; j < m; j++) refused[lo + j] = verify_refusal(&c->h_codes[j * 4]);
+      sums.push_back(range_sums(ni, inputs, rho, skip, lo, lo + m));
+    }
+    root_f.push_back(fq6_from_limbs(res));
+    root_c.push_back(jac_from_limbs(res + 72));
+    chunks.push_back(m);
+    first.push_back(lo);
+    return ZKHIP_OK;
+  });
+  if (rc_all != ZKHIP_OK) return rc_all;
+  auto t0 = std::chrono::steady_clock::now();
+  const CombineKey key = {c->alpha, c->neg_g2, c->neg_beta, c->neg_delta, c->abc.data(), ni};
+  CombineSums all(ni);
+  Fq6 product = Fq6::one();
+  HJac s_c = HJac::infinity();
+  for (size_t i = 0; i < chunks.size(); i++) {
+    all.sigma = all.sigma + sums[i].sigma;
+    for (size_t j = 0; j < ni; j++) all.s[j] = all.s[j] + sums[i].s[j];
+    product = product * root_f[i];
+    s_c = s_c.add(root_c[i]);
+  }
+  const Fq6 total = combined_value(key, all, s_c, product);
+  fq6_to_limbs(total, value);
+  c->finish_ms = ms_since(t0);
+  const uint8_t accept = checked ? (uint8_t)ZKHIP_VERIFY_ACCEPT : 1, reject = checked ? (uint8_t)ZKHIP_VERIFY_REJECT : 0;
+  for (size_t i = 0; i < count; i++) verdict[i] = checked && refused[i] ? refused[i] : accept;
+  if (total.is_one()) return ZKHIP_OK;
+
+  t0 = std::chrono::steady_clock::now();
+  const unsigned threads = locate_threads();
+  const std::vector<uint8_t> known(1, 0);                          // one chunk: the batch's value is its root's, and it is not one
+  if (trace && chunks.size() == 1) {
+    LocateTraceNode tn;
+    tn.node = {0, (uint32_t)pairing_tree_levels(count), 0};
+    tn.passed = false;
+    fq6_to_limbs(total, tn.value);
+    trace->push_back(tn);
+  }
+  std::vector<uint8_t> state;
+  locate::Stats st;
+  char* const eb = errbuf;
+  const size_t el = errlen;
+  const int rc = locate::descend(
+      chunks, PAIRING_STRIP, LOCATE_COST, threads, chunks.size() == 1 ? &known : nullptr,
+      [&](const std::vector<locate::Node>& nodes, std::vector<uint8_t>& passed) -> int {
+        char* errbuf = eb;
+        const size_t errlen = el;
+        const size_t n = nodes.size();
+        std::vector<size_t> lo(n), hi(n);
+        std::vector<Fq6> f(n);
+        std::vector<HJac> sc(n);
+        std::vector<TreeNodeRef> refs(n);
+        std::vector<uint64_t> limbs(n * 96);
+        bool roots = true;
+        for (size_t i = 0; i < n; i++) {
+          const locate::Node& nd = nodes[i];
+          const size_t m = chunks[nd.chunk];
+          if ((int)nd.level > pairing_tree_levels(m) || nd.index >= pairing_level_size(m, (int)nd.level)) {
+            if (errbuf) snprintf(errbuf, errlen, "located batch: a node outside its tree");
+            return ZKHIP_ERR_STATE;
+          }
+          node_range(nd, first[nd.chunk], m, &lo[i], &hi[i]);
+          const size_t at = pairing_level_offset(m, (int)nd.level) + nd.index;
+          refs[i] = {c->kept[nd.chunk]->f.get() + at * 6, c->kept[nd.chunk]->c.get() + at};
+          roots = roots && (int)nd.level == pairing_tree_levels(m);
+        }
+        std::vector<const CombineSums*> given;
+        if (roots) {                                               // the chunk round: the roots came back with their chunks, the sums are kept
+          for (size_t i = 0; i < n; i++) { f[i] = root_f[nodes[i].chunk]; sc[i] = root_c[nodes[i].chunk]; given.push_back(&sums[nodes[i].chunk]); }
+        } else {
+          const int r = enqueue_tree_nodes(c, refs.data(), n, limbs.data(), errbuf, errlen);
+          if (r != ZKHIP_OK) return r;
+          ZK_HIP_TRY("pairing", hipStreamSynchronize(c->st));
+          for (size_t i = 0; i < n; i++) { f[i] = fq6_from_limbs(&limbs[i * 96]); sc[i] = jac_from_limbs(&limbs[i * 96 + 72]); }
+        }
+        test_nodes(key, inputs, rho, skip, nodes, lo, hi, f, sc, threads, passed, trace, given);
+        return ZKHIP_OK;
+      },
+      [&](const std::vector<size_t>& list) -> int {                // the per-proof route on the proofs still in doubt, gathered
+        const auto t1 = std::chrono::steady_clock::now();
+        int r;
+        if (list.back() - list.front() + 1 == list.size()) {      // one run of proofs: they stand gathered where they are
+          r = pairing_verify_batch(c, inputs + list.front() * ni * 6, proofs + list.front() * 72, list.size(), checked, verdict + list.front(), eb, el);
+        } else {
+          std::vector<uint64_t> gi(list.size() * ni * 6), gp(list.size() * 72);
+          std::vector<uint8_t> out(list.size());
+          for (size_t i = 0; i < list.size(); i++) {
+            if (ni) memcpy(&gi[i * ni * 6], inputs + list[i] * ni * 6, ni * 48);
+            memcpy(&gp[i * 72], proofs + list[i] * 72, 576);
+          }
+          r = pairing_verify_batch(c, gi.data(), gp.data(), list.size(), checked, out.data(), eb, el);
+          for (size_t i = 0; r == ZKHIP_OK && i < list.size(); i++) verdict[list[i]] = out[i];
+        }
+        stats->finish_ms = ms_since(t1);
+        return r;
+      },
+      state, st);
+  if (rc != ZKHIP_OK) return rc;
+  for (size_t i = 0; i < count; i++)
+    if (state[i] == locate::INVALID) verdict[i] = reject;
+  for (size_t i = 0; i < count; i++) stats->invalid += verdict[i] == reject;
+  stats->chunks_failed = st.chunks_failed; stats->rounds = st.rounds; stats->node_tests = st.node_tests; stats->finish_proofs = st.finish_proofs;
+  stats->descent_ms = ms_since(t0) - stats->finish_ms;
   return ZKHIP_OK;
 }
 

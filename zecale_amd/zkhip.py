@@ -50,6 +50,7 @@ EXPORTS = [
     "zkhip_verifier_verify_all", "zkhip_groth16_verify_all", "zkhip_internal_verify_all_value", "zkhip_internal_verify_all_finish_ms",
     "zkhip_nested_verifier_verify_all", "zkhip_nested_verifier_last_degenerate", "zkhip_bls12_377_groth16_verify_all",
     "zkhip_internal_nested_verify_all_value", "zkhip_internal_nested_verify_all_finish_ms",
+    "zkhip_verifier_verify_batch_located", "zkhip_groth16_verify_batch_located", "zkhip_internal_verify_batch_located", "zkhip_internal_locate_trace",
     "zkhip_prover_set_checked", "zkhip_prover_last_refusal", "zkhip_crs_check", "zkhip_crs_check_host", "zkhip_internal_key_check_set_chunk", "zkhip_internal_key_check_last_ms",
 ]
 
@@ -143,6 +144,21 @@ class KeyReport(ctypes.Structure):
             where = "its length" if self.structure_first == NONE_INDEX else "index %d" % self.structure_first
             out.append("%s: %s disagrees with the constraint system" % (KEY_ELEMENTS[self.structure], where))
         return "key check: " + "; ".join(out)
+
+
+class LocateStats(ctypes.Structure):
+    """zkhip_locate_stats: what a located batch did"""
+    _fields_ = [("chunks_failed", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("node_tests", ctypes.c_uint32), ("finish_proofs", ctypes.c_uint32),
+                ("invalid", ctypes.c_uint32), ("descent_ms", ctypes.c_double), ("finish_ms", ctypes.c_double)]
+
+    def fields(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class LocateNode(ctypes.Structure):
+    """zkhip_locate_node: one tested node of a located batch"""
+    _fields_ = [("chunk", ctypes.c_uint32), ("level", ctypes.c_uint32), ("passed", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("index", ctypes.c_uint64), ("value", ctypes.c_uint64 * 72)]
 
 
 class WitnessProgram(ctypes.Structure):
@@ -300,6 +316,13 @@ def load():
                                                        ctypes.POINTER(ctypes.c_int)]
     lib.zkhip_internal_nested_verify_all_value.argtypes = [ctypes.c_int, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p]
     lib.zkhip_internal_nested_verify_all_finish_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    if hasattr(lib, "zkhip_verifier_verify_batch_located"):      # (as below: an older build has no located batches)
+        stp = ctypes.POINTER(LocateStats)
+        lib.zkhip_verifier_verify_batch_located.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.c_void_p, stp]
+        lib.zkhip_groth16_verify_batch_located.argtypes = [c_u64p, c_u64p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, c_u64p, ctypes.c_size_t, c_u64p,
+                                                           ctypes.c_void_p, stp]
+        lib.zkhip_internal_verify_batch_located.argtypes = [ctypes.c_int, ctypes.c_void_p, c_u64p, c_u64p, ctypes.c_size_t, c_u64p, ctypes.c_void_p, stp, c_u64p]
+        lib.zkhip_internal_locate_trace.argtypes = [ctypes.c_void_p, ctypes.POINTER(LocateNode), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     if hasattr(lib, "zkhip_crs_check"):      # (ZKHIP_LIB may name an older build of the library: tools/key_check_ab.py measures against one)
         for f in (lib.zkhip_crs_check, lib.zkhip_crs_check_host):
             f.argtypes = [ctypes.POINTER(CrsDesc), c_u64p, ctypes.POINTER(R1csDesc), c_u64p, ctypes.POINTER(KeyReport)]
@@ -901,14 +924,38 @@ class Verifier:
                                                 None if st is None else st.ctypes.data))
         return (bool(ok.value), st[:pr.shape[0]].tobytes()) if status else bool(ok.value)
 
-    def verify_batch_combined(self, inputs, proofs):
+    def verify_batch_located(self, inputs, proofs, rho=None):
+        """Per-proof verdicts by way of the combined check with its trees retained (zkhip_verifier_verify_batch_located): an
+        all-valid batch costs what verify_all costs; a batch that fails is searched from the chunk roots down, one host finish per
+        round, and the proofs a cost rule finds cheaper to check one by one go through verify_batch's kernels.  Returns what
+        verify_batch returns, or on a handle made with checked=True what verify_batch_checked returns (the point checks run in
+        front).  rho and the precondition on an unchecked handle: as verify_all."""
+        pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], self.n_inputs, 6)
+        rl = _rho_limbs(rho, pr.shape[0])
+        out = np.zeros(pr.shape[0], dtype=np.uint8)
+        self._locate_stats = LocateStats()
+        _check(load().zkhip_verifier_verify_batch_located(self.handle, _p(inp), _p(pr), pr.shape[0], None if rl is None else _p(rl), out.ctypes.data,
+                                                          ctypes.byref(self._locate_stats)))
+        return (out & np.uint8(0x0F), out & np.uint8(0xF0)) if self.checked else out.astype(bool)
+
+    def last_locate_stats(self):
+        """Of the last verify_batch_located on this handle: dict of chunks_failed, rounds, node_tests (the chunk round included),
+        finish_proofs (proofs handed to the per-proof route), invalid, descent_ms, finish_ms; None before the first call."""
+        st = getattr(self, "_locate_stats", None)
+        return None if st is None else st.fields()
+
+    def verify_batch_combined(self, inputs, proofs, locate=False):
         """Per-proof verdicts by way of the combined check: all ones when verify_all passes, and only otherwise the per-proof
         route - verify_batch's bool array, or on a handle made with checked=True verify_batch_checked's (codes, masks), in front
         of which verify_all runs with the point checks.  Measured (profiles/verify_combined.txt) an all-valid batch is
         cheaper this way at EVERY size from one proof on (0.57 of the per-proof batch at 1 proof, 0.54 at 1,024, 0.39 at 16,384): there
         is no batch size below which it does not pay; a batch with an invalid proof costs both routes (1.4 to 1.5 x the per-proof
-        one), so it pays where batches are mostly valid."""
+        one), so it pays where batches are mostly valid.  locate=True: verify_batch_located instead, which finds the invalid proofs
+        of a failed batch from the combined check's own trees (profiles/verify_locate.txt)."""
         pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+        if locate:
+            return self.verify_batch_located(inputs, pr)
         if self.checked:
             if self.verify_all(inputs, pr, status=True)[0]:
                 return np.zeros(pr.shape[0], dtype=np.uint8), np.zeros(pr.shape[0], dtype=np.uint8)
@@ -938,6 +985,45 @@ def verify_all_value(route, verifier, inputs, proofs, rho):
     out = np.zeros((6, 12), dtype=np.uint64)
     _check(load().zkhip_internal_verify_all_value({"host": 0, "gpu": 1}[route], verifier.handle, _p(inp), _p(pr), pr.shape[0], _p(rl), _p(out)))
     return out
+
+
+def verify_batch_located_value(route, verifier, inputs, proofs, rho):
+    """Test hook: Verifier.verify_batch_located by route - "gpu", or "host": the host route under the handle's key - with the batch's
+    reduced GT value.  Returns (verdicts as verify_batch_located gives them, value 6 x 12 ABI limbs); Verifier.last_locate_stats and
+    locate_trace tell about this call."""
+    pr = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 72)
+    inp = np.ascontiguousarray(inputs, dtype=np.uint64).reshape(pr.shape[0], verifier.n_inputs, 6)
+    rl = _rho_limbs(rho, pr.shape[0])
+    out, value = np.zeros(pr.shape[0], dtype=np.uint8), np.zeros((6, 12), dtype=np.uint64)
+    verifier._locate_stats = LocateStats()
+    _check(load().zkhip_internal_verify_batch_located({"host": 0, "gpu": 1}[route], verifier.handle, _p(inp), _p(pr), pr.shape[0], _p(rl),
+                                                      out.ctypes.data, ctypes.byref(verifier._locate_stats), _p(value)))
+    return ((out & np.uint8(0x0F), out & np.uint8(0xF0)) if verifier.checked else out.astype(bool)), value
+
+
+def locate_trace(verifier):
+    """Test hook: every node the last verify_batch_located on the handle tested, in the order of the rounds: a list of dicts chunk,
+    level (0: a single proof), index, passed, value (the reduced value of the node's combined check, 6 x 12 ABI limbs)."""
+    n = ctypes.c_size_t(0)
+    _check(load().zkhip_internal_locate_trace(verifier.handle, None, 0, ctypes.byref(n)))
+    buf = (LocateNode * max(n.value, 1))()
+    _check(load().zkhip_internal_locate_trace(verifier.handle, buf, n.value, ctypes.byref(n)))
+    return [{"chunk": int(b.chunk), "level": int(b.level), "index": int(b.index), "passed": bool(b.passed),
+             "value": np.array(b.value, dtype=np.uint64).reshape(6, 12)} for b in buf[:n.value]]
+
+
+def groth16_verify_batch_located(vk, inputs, proofs, rho=None):
+    """Per-proof verdicts by way of the combined check on the host alone (zkhip_groth16_verify_batch_located; works without a GPU):
+    the route Verifier.verify_batch_located is pinned on.  Arguments as groth16_verify_all.  Returns (bool array, stats dict)."""
+    c = lambda a: np.ascontiguousarray(a, dtype=np.uint64)
+    abc = c(vk["ABC"]).reshape(-1, 24)
+    pr = c(proofs).reshape(-1, 72)
+    inp = c(inputs).reshape(pr.shape[0], abc.shape[0] - 1, 6)
+    rl = _rho_limbs(rho, pr.shape[0])
+    ok, st = np.zeros(pr.shape[0], dtype=np.uint8), LocateStats()
+    _check(load().zkhip_groth16_verify_batch_located(_p(c(vk["alpha"])), _p(c(vk["beta"])), _p(c(vk["delta"])), _p(abc), abc.shape[0] - 1, _p(inp), _p(pr),
+                                                     pr.shape[0], None if rl is None else _p(rl), ok.ctypes.data, ctypes.byref(st)))
+    return ok.astype(bool), st.fields()
 
 
 def fq6_selftest(op, a, b):
