@@ -66,6 +66,26 @@ inline std::string key_report_message(const zkhip_key_report& rep) {
   return out;
 }
 
+// One phase-2 contribution on top of a keypair (zkhip_keypair_contribute): delta times a secret drawn from the OS, h_query and l_query
+// by its inverse.  Returns the new keypair (the caller frees it with zkhip_keypair_free); rec and new_digest are the transcript's next
+// entry.  Phase 2 re-randomises delta only: tau, alpha and beta stay whoever's they were (zkhip.h states the scope).
+inline zkhip_keypair* contribute(const zkhip_keypair* before, const uint8_t prev_digest[32], zkhip_phase2_contribution& rec, uint8_t new_digest[32],
+                                 bool host = false) {
+  zkhip_keypair* after = nullptr;
+  if (host) zk_check(zkhip_keypair_contribute_host(before, nullptr, nullptr, prev_digest, &after, &rec, new_digest), "zkhip_keypair_contribute_host");
+  else zk_check(zkhip_keypair_contribute(before, nullptr, nullptr, prev_digest, &after, &rec, new_digest), "zkhip_keypair_contribute");
+  return after;
+}
+// zkhip_phase2_verify: is `after` an honest contribution on top of `before` (a key check_key or an earlier accepted contribution has
+// validated)?  The verdict is report.ok; new_digest is written only then.  Throws only when the check could not run.
+inline zkhip_phase2_report verify_contribution(const zkhip_crs_desc& before, const zkhip_crs_desc& after, const zkhip_phase2_contribution& rec,
+                                               const uint8_t prev_digest[32], uint8_t new_digest[32], bool host = false) {
+  zkhip_phase2_report rep;
+  if (host) zk_check(zkhip_phase2_verify_host(&before, &after, &rec, prev_digest, nullptr, &rep, new_digest), "zkhip_phase2_verify_host");
+  else zk_check(zkhip_phase2_verify(&before, &after, &rec, prev_digest, nullptr, &rep, new_digest), "zkhip_phase2_verify");
+  return rep;
+}
+
 // A Groth16 proof over BW6-761 in the ABI's affine Montgomery limbs: A in G1, B in G2, C in G1.
 struct groth16_proof {
   std::array<uint64_t, 24> a, b, c;

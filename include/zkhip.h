@@ -306,6 +306,66 @@ typedef struct {
 int zkhip_crs_check(const zkhip_crs_desc* key, const uint64_t* vk_abc, const zkhip_r1cs_desc* cs, const uint64_t* rho, zkhip_key_report* out);
 int zkhip_crs_check_host(const zkhip_crs_desc* key, const uint64_t* vk_abc, const zkhip_r1cs_desc* cs, const uint64_t* rho, zkhip_key_report* out);
 
+/* ---- phase-2 contributions: re-randomise delta of a key, and verify somebody else's re-randomisation ----------------------------
+ * stands beside: the circuit-specific ("phase 2") round of a setup ceremony.  zkhip_groth16_setup* is a single-party setup whose caller
+ * knows delta; a party who RECEIVES a key can add its own randomness with zkhip_keypair_contribute, and whoever coordinates checks that
+ * turn with zkhip_phase2_verify.  As long as ONE contributor of the chain discards its s, nobody knows delta.
+ * SCOPE.  Phase 2 re-randomises delta ONLY.  A key is sound only if tau, alpha and beta are unknown as well: that takes a
+ * powers-of-tau ceremony and the linear-combination step that turns its output into this circuit's queries, neither of which this
+ * library has.  A key from zkhip_groth16_setup* with contributions on top still has a tau, alpha and beta that the first party knew.
+ * THE MATHS (Groth16 without gamma, as zkhip_groth16_setup builds it): H_j = tau^j Z(tau) / delta g1 and
+ * L_i = (beta A_i + alpha B_i + C_i)(tau) / delta g1.  A contribution with the secret s in [1, r) gives
+ *   delta_g1' = s delta_g1, delta_g2' = s delta_g2, H'_j = s^-1 H_j, L'_i = s^-1 L_i (a base at infinity stays there);
+ * everything else, the verification key's ABC included, is unchanged: the new verification key differs in delta_g2 only, and
+ * setup(tau, alpha, beta, delta s) equals contribute(setup(tau, alpha, beta, delta), s) limb for limb.
+ * On the device the 2 x up to 2^22 multiplications by the ONE scalar s^-1 run one lane per point of a staged chunk, every lane on the
+ * same recoded digits (csrc/phase2.hip k_common_scalar_mul: s^-1 = k1 + k2 lambda along G1's endomorphism, half the doublings); the
+ * digits, and the call's own copies of s, k and s^-1, are cleared on the device and the host before the call returns.
+ * A contribution before -> after with its record is ACCEPTED iff all five hold:
+ *   1. UNCHANGED.  n_vars, n_primary, domain_size, alpha_g1, beta_g1, beta_g2, a_query, b_g2_query, b_g1_query are byte-identical (and
+ *      the record's delta_g1 / delta_g2 are the new key's).
+ *   2. POINTS.  delta_g1', delta_g2', every H'_j, every L'_i and the record's commitment T pass the checks of zkhip_crs_check (same
+ *      codes); delta' or T at infinity is refused; the infinity pattern of H' and L' equals that of H and L index by index.
+ *   3. DELTA PAIR.  t(delta_g1', g2) t(-g1, delta_g2') == 1.
+ *   4. RATIO.  With 128-bit non-zero rho over the concatenation H | L, the same scalars on both keys, S = sum rho_i (H | L)_i and
+ *      S' = sum rho_i (H' | L')_i: t(S', delta_g2') t(-S, delta_g2) == 1.  Evaluated ONLY when step 2 refused nothing - the rule of
+ *      zkhip_crs_check and zkhip_verifier_verify_all, for the same reason: with a point of small order among the summands the error
+ *      term can have small order and be cancelled by its scalar with noticeable probability.
+ *   5. PROOF OF KNOWLEDGE of s (Schnorr on the base delta_g1, Fiat-Shamir).  T = k delta_g1; c = the first 16 bytes, little endian, of
+ *      SHA-256("zkhip phase2 pok v1" | prev_digest | delta_g1 | delta_g1' | T); z = k + c s mod r, canonical (NOT Montgomery) and
+ *      below r; the check is [z] delta_g1 == T + [c] delta_g1'.  Points are hashed as their 24 ABI limbs, little endian.
+ * The transcript link: new_digest = SHA-256("zkhip phase2 link v1" | prev_digest | the record's 624 bytes).
+ * PRECONDITION: `before` is a key that zkhip_crs_check, or an earlier accepted contribution, has validated; its points are not checked
+ * again (and the multiplication kernel assumes points of order r).
+ * s, k: six limbs in Montgomery form, non-zero and below r (ZKHIP_ERR_ARG otherwise), or NULL to draw them from the OS (getrandom;
+ * ZKHIP_ERR_STATE if that fails: there is no weaker generator behind it).  Passing them is for tests: whoever knows s knows the
+ * contribution's share of delta.  rho: ((domain_size - 1) + (n_vars - n_primary - 1)) x 2 words, none zero (ZKHIP_ERR_ARG), for
+ * tests and reproducible runs only - scalars that the contributor knows or can predict prove nothing -, or NULL to draw them.
+ * zkhip_keypair_contribute: *after is a new keypair (zkhip_keypair_free; _vk carries the new delta_g2, _write / _read work on it).
+ * zkhip_phase2_verify returns ZKHIP_OK whenever it RAN: the verdict is out->ok; new_digest is written only when ok.  Keys whose sizes
+ * differ are a report (changed bit 31, nothing else evaluated), not an error.  The device route checks the points with
+ * k_key_point_check and sums with the MSM engine; pairings and the proof of knowledge run on the host.
+ * The _host forms: the same results on the host alone (no device, no zkhip_init, up to 16 threads): what the device route is pinned on. */
+typedef struct zkhip_keypair zkhip_keypair;      /* zkhip_groth16_setup, zkhip_keypair_read (below) */
+typedef struct { uint64_t delta_g1[24], delta_g2[24], pok_commit[24], pok_response[6]; } zkhip_phase2_contribution;
+typedef struct {
+  int changed;                 /* bit per element of step 1 that differs (ZKHIP_KEY_* numbering; the DELTA bits: the record's delta is not the
+                                  new key's), sizes: bit 31 */
+  zkhip_key_element_report delta_g1, delta_g2, h, l, pok_commit;   /* the NEW points; first_refused / first_code as in the key check */
+  int infinity_mismatch;       /* 0, or ZKHIP_KEY_H / ZKHIP_KEY_L */
+  size_t infinity_mismatch_first;   /* its first index, (size_t)-1: none */
+  int relations, relations_evaluated;   /* bit 0 delta pair, bit 1 ratio, bit 2 proof of knowledge: set = FAILS / was evaluated */
+  int ok;
+} zkhip_phase2_report;
+int zkhip_keypair_contribute(const zkhip_keypair* before, const uint64_t s[6], const uint64_t k[6], const uint8_t prev_digest[32],
+                             zkhip_keypair** after, zkhip_phase2_contribution* rec, uint8_t new_digest[32]);
+int zkhip_keypair_contribute_host(const zkhip_keypair* before, const uint64_t s[6], const uint64_t k[6], const uint8_t prev_digest[32],
+                                  zkhip_keypair** after, zkhip_phase2_contribution* rec, uint8_t new_digest[32]);
+int zkhip_phase2_verify(const zkhip_crs_desc* before, const zkhip_crs_desc* after, const zkhip_phase2_contribution* rec,
+                        const uint8_t prev_digest[32], const uint64_t* rho, zkhip_phase2_report* out, uint8_t new_digest[32]);
+int zkhip_phase2_verify_host(const zkhip_crs_desc* before, const zkhip_crs_desc* after, const zkhip_phase2_contribution* rec,
+                             const uint8_t prev_digest[32], const uint64_t* rho, zkhip_phase2_report* out, uint8_t new_digest[32]);
+
 /* replaces: wsnarkT::generate_proof(pk, pb) = libsnark::r1cs_gg_ppzksnark_prover (called at
  * libzecale/circuits/aggregator_circuit.tcc:168), with the randomisers (r, s) injected so that
  * results can be compared bit for bit.  z: n_vars x 6 limbs.  proof_affine: A (G1), B (G2), C (G1). */
@@ -804,8 +864,7 @@ void zkhip_aggregator_pipeline_free(zkhip_pipeline* p);
  * aggregator_circuit::generate_trusted_setup (libzecale/circuits/aggregator_circuit.tcc:100-109).
  * QAP evaluation at tau on the host, the batch exponentiations on the GPU (zkhip_fixed_base_mul).
  * The toxic waste is an argument so that tests can reproduce keys; a deployment passes fresh randomness and
- * forgets it.  All four scalars: 6 limbs, Montgomery form, non-zero. */
-typedef struct zkhip_keypair zkhip_keypair;
+ * forgets it.  All four scalars: 6 limbs, Montgomery form, non-zero.  (zkhip_keypair: declared with the phase-2 section above.) */
 int zkhip_groth16_setup(const zkhip_r1cs_desc* cs, const uint64_t tau[6], const uint64_t alpha[6], const uint64_t beta[6],
                         const uint64_t delta[6], zkhip_keypair** out);
 /* the same with the evaluation domain as an argument (see zkhip_r1cs_upload_ex): ZKHIP_DOMAIN_DEFAULT = the forced power of two that
@@ -937,6 +996,17 @@ int zkhip_internal_verify_all_value(int route, zkhip_verifier* v, const uint64_t
  * the host's pairings, [4 + e] of the point checks of element e, milliseconds. */
 int zkhip_internal_key_check_set_chunk(size_t points);
 int zkhip_internal_key_check_last_ms(double out_ms[4 + ZKHIP_KEY_ELEMENTS]);
+/* phase2_last_ms: of the calling thread's last phase-2 call: [0] the device time of its longest single launch (contribute: the
+ * multiplication kernel, verify: the point check; 0 on the host routes), [3] the whole call, wall time.  contribute: [1] / [2] h_query /
+ * l_query (staging included), [4] the copy of the key, [5] delta' in both groups, [6] commitment, response and hashes, [7] the device
+ * time of ALL launches of the multiplication kernel (what [1] + [2] exceeds it by is all that overlapping copies could hide).
+ * verify: [1] the byte comparison of step 1, [2] the infinity patterns, [4] point checks, [5] four sums, [6] host relations.  Milliseconds.
+ * The chunk of the multiplication kernel is the key check's (zkhip_internal_key_check_set_chunk). */
+int zkhip_internal_phase2_last_ms(double out_ms[8]);
+/* phase2_set_form: which form of the multiplication kernel zkhip_keypair_contribute runs, process-wide: 0 the build's default (the
+ * endomorphism form), 2 the same by name, 1 the signed-binary baseline over all of s^-1 - only in a build with
+ * -DZKHIP_PHASE2_BOTH_FORMS (tools/phase2_ab.py measures the two against each other), ZKHIP_ERR_STATE otherwise.  Outputs are identical. */
+int zkhip_internal_phase2_set_form(int form);
 int zkhip_internal_verify_all_finish_ms(const zkhip_verifier* v, double* ms);
 /* verify_batch_located: zkhip_verifier_verify_batch_located by route - 1: the device route; 0: the host route of
  * zkhip_groth16_verify_batch_located under the handle's key, without its curve check, and on a checked handle behind the host's point

@@ -99,6 +99,81 @@ def edwards_params():
     return {"s": s, "A": A, "t": t, "d": d, "c1": -3 * t * t * inv(4) % q, "c2": 3 * t * inv(2) % q, "half_r": pow(2, -1, R)}
 
 
+def _ec_mul(k, P):
+    """k P on y^2 = x^3 - 1 over Fq, affine (None: the point at infinity): only to tell the two endomorphism eigenvalues apart"""
+    def add(A, Bp):
+        if A is None:
+            return Bp
+        if Bp is None:
+            return A
+        if A[0] == Bp[0]:
+            if (A[1] + Bp[1]) % Q == 0:
+                return None
+            l = 3 * A[0] * A[0] * pow(2 * A[1], -1, Q) % Q
+        else:
+            l = (Bp[1] - A[1]) * pow(Bp[0] - A[0], -1, Q) % Q
+        x = (l * l - A[0] - Bp[0]) % Q
+        return (x, (l * (A[0] - x) - A[1]) % Q)
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = add(acc, acc)
+        if bit == "1":
+            acc = add(acc, P)
+    return acc
+
+
+def glv_params(t_bits=576):
+    """G1 is y^2 = x^3 - 1 (j = 0) and q = r = 1 mod 3: phi(x, y) = (omega x, y), omega^3 = 1 in Fq, acts on G1 as a cube root of unity
+    lambda in Fr.  Of the two omega and two lambda the pair with phi(G1_GEN) = lambda G1_GEN is taken.  The decomposition
+    k = k1 + k2 lambda (mod r) with |k1|, |k2| < 2^bits: v1 = (a1, b1), v2 = (a2, b2) is a reduced basis of the lattice
+    {(a, b): a + b lambda = 0 mod r} from the extended Euclidean algorithm on (r, lambda); (k1, k2) = (k, 0) - c1 v1 - c2 v2 with
+    c1 = round(k b2 / det), c2 = round(-k b1 / det), the quotients as floor((k g_i + 2^(t-1)) / 2^t), g_i = round(2^t |.| / r)."""
+    assert Q % 3 == 1 and R % 3 == 1
+    g = 2
+    while pow(g, (Q - 1) // 3, Q) == 1:
+        g += 1
+    omegas = [pow(g, (Q - 1) // 3, Q)]
+    omegas.append(omegas[0] * omegas[0] % Q)
+    g = 2
+    while pow(g, (R - 1) // 3, R) == 1:
+        g += 1
+    lam = pow(g, (R - 1) // 3, R)
+    lams = [lam, lam * lam % R]
+    pair = [(w, l) for w in omegas for l in lams if _ec_mul(l, G1) == (w * G1[0] % Q, G1[1])]
+    omega, lam = min(pair)                       # (both omegas have their lambda: the smaller omega, for a fixed choice)
+    assert (lam * lam + lam + 1) % R == 0 and pow(omega, 3, Q) == 1 and omega != 1
+    # extended Euclid on (r, lambda): remainders r_i = s_i r + t_i lambda, so (r_i, -t_i) is in the lattice
+    rs, ts = [R, lam], [0, 1]
+    while rs[-1] * rs[-1] >= R:
+        qt = rs[-2] // rs[-1]
+        rs.append(rs[-2] - qt * rs[-1]); ts.append(ts[-2] - qt * ts[-1])
+    qt = rs[-2] // rs[-1]
+    rs.append(rs[-2] - qt * rs[-1]); ts.append(ts[-2] - qt * ts[-1])
+    v1 = (rs[-2], -ts[-2])
+    cands = [(rs[-3], -ts[-3]), (rs[-1], -ts[-1])]
+    v2 = min(cands, key=lambda v: v[0] * v[0] + v[1] * v[1])
+    for a, b in (v1, v2):
+        assert (a + b * lam) % R == 0
+    det = v1[0] * v2[1] - v2[0] * v1[1]
+    assert abs(det) == R
+    sgn = 1 if det > 0 else -1
+    n1, n2 = sgn * v2[1], -sgn * v1[1]           # c1 = round(k n1 / r), c2 = round(k n2 / r)
+    rnd = lambda n: ((abs(n) << t_bits) + R // 2) // R
+    # |k_i| <= (|a1| + |a2|) / 2 resp. (|b1| + |b2|) / 2 for exact rounding; the truncated quotients are off by at most one each
+    bound = max(abs(v1[0]) + abs(v2[0]), abs(v1[1]) + abs(v2[1])) * 3 // 2 + 2
+    bits = bound.bit_length()
+    assert bits <= 192
+    return dict(omega=omega, omega2=omega * omega % Q, lam=lam, v1=v1, v2=v2, n=(n1, n2), g=(rnd(n1), rnd(n2)), t=t_bits, bits=bits)
+
+
+def glv_decompose(k, gp):
+    """the host's decomposition (csrc/phase2.cuh phase2_glv_decompose), in Python: the generator checks it on a few thousand scalars"""
+    c = [((k * g + (1 << (gp["t"] - 1))) >> gp["t"]) * (1 if n > 0 else -1) for g, n in zip(gp["g"], gp["n"])]
+    k1 = k - c[0] * gp["v1"][0] - c[1] * gp["v2"][0]
+    k2 = -c[0] * gp["v1"][1] - c[1] * gp["v2"][1]
+    return k1, k2
+
+
 def main():
     out = "// GENERATED by tools/gen_params.py - do not edit.\n"
     out += "// BW6-761 field constants (moduli: reference client/test_commands/test_bw6_761_groth16_contract.py:26-27).\n"
@@ -127,6 +202,15 @@ def main():
     # psi's constants once more in the host's form: the window result of an Edwards launch is mapped back on the host (msm.hip edw_abi_to_jac)
     extra_q += arr("EDW_C1_64", limbs(ep["c1"] * Rabi_q % Q, 12, 64), "uint64_t", 3, "0x%016xull")
     extra_q += arr("EDW_C2_64", limbs(ep["c2"] * Rabi_q % Q, 12, 64), "uint64_t", 3, "0x%016xull")
+    # the endomorphism phi(x, y) = (omega x, y) of G1 and the decomposition of a scalar along it (glv_params; phase2.cuh)
+    gp = glv_params()
+    import random
+    rng = random.Random(1)
+    for k in [0, 1, 2, R - 1, gp["lam"], R - gp["lam"], (R + 1) // 2] + [rng.randrange(R) for _ in range(2000)]:
+        k1, k2 = glv_decompose(k, gp)
+        assert (k1 + k2 * gp["lam"] - k) % R == 0 and abs(k1) < 1 << gp["bits"] and abs(k2) < 1 << gp["bits"], k
+    extra_q += arr("GLV_OMEGA", mont(gp["omega"]))                  # phi(x, y) = (omega x, y) = lambda (x, y) on G1
+    extra_q += arr("GLV_OMEGA2", mont(gp["omega2"]))                # omega^2 = 1 / omega: back from omega x to x
     out += field("FqParams", Q, 27, 12, extra_q)
     Rabi_r = 1 << 384
     two_adic = pow(FR_GEN, (R - 1) >> 46, R)
@@ -136,6 +220,18 @@ def main():
     extra_r += arr("ROOT_2_46_64", limbs(two_adic * Rabi_r % R, 6, 64), "uint64_t", 3, "0x%016xull")
     # 1/2 mod r = (r + 1) / 2 as an integer in 29-bit limbs: the scalar that halves the bases of an Edwards table (msm.hip k_half_bases)
     extra_r += arr("HALF_RAW", limbs(pow(2, -1, R), 14, B))
+    u64 = lambda name, v, n: arr(name, limbs(v, n, 64), "uint64_t", 3, "0x%016xull")
+    extra_r += u64("GLV_LAMBDA64", gp["lam"], 6)                    # canonical (not Montgomery)
+    extra_r += "  static constexpr int GLV_BITS = %d;      // |k1|, |k2| < 2^GLV_BITS\n" % gp["bits"]
+    extra_r += "  static constexpr int GLV_SHIFT = %d;     // c_i = (k GLV_G_i + 2^(GLV_SHIFT - 1)) >> GLV_SHIFT\n" % gp["t"]
+    extra_r += u64("GLV_G1_64", gp["g"][0], 9) + u64("GLV_G2_64", gp["g"][1], 9)
+    # magnitudes of the basis (a1, b1), (a2, b2); GLV_SIGNS bit j set: term j of (c1 a1, c2 a2, c1 b1, c2 b2) is NEGATIVE, the sign of
+    # c_i included, so that k1 = k - (+-)c1 |a1| - (+-)c2 |a2| and k2 = -(+-)c1 |b1| - (+-)c2 |b2| with c_i >= 0
+    (a1, b1), (a2, b2) = gp["v1"], gp["v2"]
+    sg = lambda n: 1 if n > 0 else -1
+    terms = (sg(gp["n"][0]) * a1, sg(gp["n"][1]) * a2, sg(gp["n"][0]) * b1, sg(gp["n"][1]) * b2)
+    extra_r += u64("GLV_A1_64", abs(a1), 3) + u64("GLV_A2_64", abs(a2), 3) + u64("GLV_B1_64", abs(b1), 3) + u64("GLV_B2_64", abs(b2), 3)
+    extra_r += "  static constexpr int GLV_SIGNS = %d;\n" % sum(1 << j for j, v in enumerate(terms) if v < 0)
     out += field("FrParams", R, 14, 6, extra_r)
     out += "}  // namespace zkhip\n"
     print(out, end="")

@@ -49,6 +49,12 @@ struct zkhip_crs {
   mutable std::unique_ptr<TailTables> tail;
 };
 
+// a key pair on the host (api_key.hip makes, writes and reads them; phase2.hip makes the re-randomised one)
+struct zkhip_keypair {
+  size_t n_vars, n_primary, domain_size;
+  std::vector<uint64_t> alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, A, B2, B1, H, L, ABC;
+};
+
 namespace zkhip {
 namespace api {
 // Everything one proof in flight needs on the device: a stream for the QAP map, the witness buffer, five MSM contexts

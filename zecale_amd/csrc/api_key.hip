@@ -9,11 +9,6 @@ using namespace zkhip::api;
 
 #pragma GCC visibility push(hidden)      // this file's own helpers and handle structs
 
-struct zkhip_keypair {
-  size_t n_vars, n_primary, domain_size;
-  std::vector<uint64_t> alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, A, B2, B1, H, L, ABC;
-};
-
 // The options of a key, resolved once at upload against the process-wide defaults (zkhip_set_*), then carried by the handle:
 // two threads loading keys with different options never see each other's choice.
 struct ResolvedOpts { int precompute, naf, window, batch, model; };

@@ -22,6 +22,7 @@
 #include "device_buffer.hpp"
 #include "domain.hpp"
 #include "ec.cuh"
+#include "key_check_internal.hpp"
 #include "pairing.cuh"
 #include "pairing_host.hpp"
 
@@ -31,12 +32,6 @@ namespace zkhip {
 
 constexpr uint8_t KEY_CODE_INFINITY = 0x80;       // k_key_point_check's byte for a point that passes as the point at infinity
 constexpr uint32_t KEY_FIRST_NONE = 0xFFFFFFFFu;  // no refused point: above every (index << 2 | code - 2), index < 2^30
-
-struct KeyCheckCounters {
-  unsigned long long infinity, refused[3], points;
-  uint32_t first;       // min over the refused points of (index in the element << 2) | (code - ZKHIP_VERIFY_ENCODING)
-  uint32_t pad;
-};
 
 // ---- encoding, curve and order of `n` points of one element (pts: n x 24 raw ABI limbs, 16-byte aligned), one lane per point
 __global__ void __launch_bounds__(64) k_key_point_check(const uint64_t* __restrict__ pts, size_t n, int g2, const uint64_t* __restrict__ r_order,
@@ -93,17 +88,17 @@ __global__ void __launch_bounds__(256) k_key_codes_reduce(const uint8_t* __restr
 
 }  // namespace zkhip
 
-#pragma GCC visibility push(hidden)      // this file's own helpers
-namespace {
+#pragma GCC visibility push(hidden)      // this file's own helpers, and those phase2.hip shares (key_check_internal.hpp)
+namespace zkhip {
+namespace keycheck {
 
 using namespace zkhip::host;
 
-std::atomic<size_t> g_chunk_hook{0};                 // zkhip_internal_key_check_set_chunk
-thread_local double t_last_ms[4 + ZKHIP_KEY_ELEMENTS] = {0};     // zkhip_internal_key_check_last_ms
+static std::atomic<size_t> g_chunk_hook{0};                 // zkhip_internal_key_check_set_chunk
+static thread_local double t_last_ms[4 + ZKHIP_KEY_ELEMENTS] = {0};     // zkhip_internal_key_check_last_ms
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-struct Element { const uint64_t* p; size_t n; bool g2; };
+size_t chunk_hook() { return g_chunk_hook.load(); }
 
 void key_elements(const zkhip_crs_desc* d, const uint64_t* vk_abc, Element e[ZKHIP_KEY_ELEMENTS]) {
   const size_t m = d->n_vars, l = d->n_primary;
@@ -158,14 +153,15 @@ void host_check_element(const Element& el, zkhip_key_element_report* rep) {
 }
 
 // ---- the same on the device: the element's points staged chunk by chunk, one wait per element
-struct KeyCheckDev {
-  DeviceStream st;
-  DeviceBuffer<uint64_t> d_pts, d_r;
-  DeviceBuffer<uint8_t> d_codes;
-  DeviceBuffer<KeyCheckCounters> d_cnt;
-  std::vector<hipEvent_t> ev;
-  ~KeyCheckDev() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-};
+int dev_open(KeyCheckDev& w) {
+  char* errbuf = t_err;
+  const size_t errlen = sizeof t_err;
+  ZK_HIP_TRY("key check", w.st.create());
+  ZK_HIP_TRY("key check", w.d_r.reserve(6));
+  ZK_HIP_TRY("key check", w.d_cnt.reserve(1));
+  ZK_HIP_TRY("key check", hipMemcpyAsync(w.d_r.get(), FqParams::R_ORDER64, 48, hipMemcpyHostToDevice, w.st));
+  return ZKHIP_OK;
+}
 
 int dev_check_element(KeyCheckDev& w, const Element& el, size_t chunk, zkhip_key_element_report* rep, double* longest_ms) {
   char* errbuf = t_err;
@@ -307,13 +303,8 @@ int crs_check(const zkhip_crs_desc* d, const uint64_t* vk_abc, const zkhip_r1cs_
   // 1. points
   double t0 = now_ms();
   if (device) {
-    char* errbuf = t_err;
-    const size_t errlen = sizeof t_err;
     KeyCheckDev w;
-    ZK_HIP_TRY("key check", w.st.create());
-    ZK_HIP_TRY("key check", w.d_r.reserve(6));
-    ZK_HIP_TRY("key check", w.d_cnt.reserve(1));
-    ZK_HIP_TRY("key check", hipMemcpyAsync(w.d_r.get(), FqParams::R_ORDER64, 48, hipMemcpyHostToDevice, w.st));
+    if ((rc = dev_open(w)) != ZKHIP_OK) return rc;
     const size_t chunk = key_check_chunk(g_chunk_hook.load());
     for (int k = 0; k < ZKHIP_KEY_ELEMENTS; k++) {
       const double te = now_ms();
@@ -382,8 +373,11 @@ int crs_check(const zkhip_crs_desc* d, const uint64_t* vk_abc, const zkhip_r1cs_
   return ZKHIP_OK;
 }
 
-}  // namespace
+}  // namespace keycheck
+}  // namespace zkhip
 #pragma GCC visibility pop
+
+using namespace zkhip::keycheck;
 
 extern "C" {
 

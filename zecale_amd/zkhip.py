@@ -52,6 +52,7 @@ EXPORTS = [
     "zkhip_internal_nested_verify_all_value", "zkhip_internal_nested_verify_all_finish_ms",
     "zkhip_verifier_verify_batch_located", "zkhip_groth16_verify_batch_located", "zkhip_internal_verify_batch_located", "zkhip_internal_locate_trace",
     "zkhip_prover_set_checked", "zkhip_prover_last_refusal", "zkhip_crs_check", "zkhip_crs_check_host", "zkhip_internal_key_check_set_chunk", "zkhip_internal_key_check_last_ms",
+    "zkhip_keypair_contribute", "zkhip_keypair_contribute_host", "zkhip_phase2_verify", "zkhip_phase2_verify_host", "zkhip_internal_phase2_last_ms", "zkhip_internal_phase2_set_form",
 ]
 
 
@@ -144,6 +145,65 @@ class KeyReport(ctypes.Structure):
             where = "its length" if self.structure_first == NONE_INDEX else "index %d" % self.structure_first
             out.append("%s: %s disagrees with the constraint system" % (KEY_ELEMENTS[self.structure], where))
         return "key check: " + "; ".join(out)
+
+
+class Contribution(ctypes.Structure):
+    """zkhip_phase2_contribution: the record of one phase-2 contribution - the new delta in both groups, the commitment T and the
+    response z (canonical) of the proof of knowledge.  to_bytes() / from_bytes(): the 624 bytes the transcript link hashes."""
+    _fields_ = [("delta_g1", ctypes.c_uint64 * 24), ("delta_g2", ctypes.c_uint64 * 24), ("pok_commit", ctypes.c_uint64 * 24),
+                ("pok_response", ctypes.c_uint64 * 6)]
+
+    def to_bytes(self):
+        return bytes(self)
+
+    @classmethod
+    def from_bytes(cls, b):
+        if len(b) != ctypes.sizeof(cls):
+            raise ZkhipError("a contribution record is %d bytes" % ctypes.sizeof(cls), -1)
+        return cls.from_buffer_copy(b)
+
+
+PHASE2_ELEMENTS = ("delta_g1", "delta_g2", "h", "l", "pok_commit")
+PHASE2_RELATIONS = ("delta_g1'/delta_g2'", "ratio of H | L to delta", "proof of knowledge of s")
+
+
+class Phase2Report(ctypes.Structure):
+    """zkhip_phase2_report (include/zkhip.h: zkhip_phase2_verify).  `ok` is the verdict; fields() is the whole report as plain Python
+    values ((size_t)-1 as None), describe() names what was refused."""
+    _fields_ = [("changed", ctypes.c_int)] + [(k, KeyElementReport) for k in PHASE2_ELEMENTS] + [
+        ("infinity_mismatch", ctypes.c_int), ("infinity_mismatch_first", ctypes.c_size_t), ("relations", ctypes.c_int),
+        ("relations_evaluated", ctypes.c_int), ("ok", ctypes.c_int)]
+
+    def fields(self):
+        none = lambda v: None if v == NONE_INDEX else int(v)
+        return dict(changed=int(self.changed) & 0xFFFFFFFF, elements={k: getattr(self, k).fields() for k in PHASE2_ELEMENTS},
+                    infinity_mismatch=int(self.infinity_mismatch), infinity_mismatch_first=none(self.infinity_mismatch_first),
+                    relations=int(self.relations), relations_evaluated=int(self.relations_evaluated), ok=int(self.ok))
+
+    def describe(self):
+        if self.ok:
+            return "phase 2: ok"
+        out = []
+        changed = int(self.changed) & 0xFFFFFFFF
+        if changed >> 31:
+            return "phase 2: the two keys have different sizes"
+        for k, name in enumerate(KEY_ELEMENTS):
+            if changed >> k & 1:
+                out.append("%s: %s" % (name, "the record's is not the new key's" if name.startswith("delta") else "changed"))
+        for name in PHASE2_ELEMENTS:
+            e = getattr(self, name)
+            if e.first_refused != NONE_INDEX:
+                out.append("%s'[%d]: %s (%d of %d points refused)" % (name, e.first_refused, VERIFY_CODES[e.first_code], sum(e.refused), e.points))
+            elif name in ("delta_g1", "delta_g2", "pok_commit") and e.infinity:
+                out.append("%s': the point at infinity" % name)
+        if self.infinity_mismatch:
+            out.append("%s[%d]: at infinity in exactly one of the two keys" % (KEY_ELEMENTS[self.infinity_mismatch], self.infinity_mismatch_first))
+        for b, name in enumerate(PHASE2_RELATIONS):
+            if self.relations >> b & 1:
+                out.append("%s: fails" % name)
+            elif not self.relations_evaluated >> b & 1:
+                out.append("%s: not evaluated (a point was refused)" % name)
+        return "phase 2: " + "; ".join(out)
 
 
 class LocateStats(ctypes.Structure):
@@ -330,6 +390,15 @@ def load():
         lib.zkhip_prover_last_refusal.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]
         lib.zkhip_internal_key_check_set_chunk.argtypes = [ctypes.c_size_t]
         lib.zkhip_internal_key_check_last_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    if hasattr(lib, "zkhip_keypair_contribute"):      # (as above: an older build has no phase-2 contributions)
+        u8p = ctypes.c_char_p
+        for f in (lib.zkhip_keypair_contribute, lib.zkhip_keypair_contribute_host):
+            f.argtypes = [ctypes.c_void_p, c_u64p, c_u64p, u8p, vpp, ctypes.POINTER(Contribution), ctypes.c_void_p]
+        for f in (lib.zkhip_phase2_verify, lib.zkhip_phase2_verify_host):
+            f.argtypes = [ctypes.POINTER(CrsDesc), ctypes.POINTER(CrsDesc), ctypes.POINTER(Contribution), u8p, c_u64p, ctypes.POINTER(Phase2Report),
+                          ctypes.c_void_p]
+        lib.zkhip_internal_phase2_last_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+        lib.zkhip_internal_phase2_set_form.argtypes = [ctypes.c_int]
     _lib = lib
     return lib
 
@@ -1848,6 +1917,22 @@ class Keypair:
         n = load().zkhip_keypair_vk(self.handle, _p(a), _p(b), _p(dl), ctypes.byref(abc))
         return dict(alpha=a, beta=b, delta=dl, ABC=np.ctypeslib.as_array(abc, (n, 24)).copy())
 
+    def contribute(self, s=None, k=None, prev_digest=b"\0" * 32, host=False):
+        """zkhip_keypair_contribute / _host (host=True: no device): one phase-2 contribution on top of this key ->
+        (the new Keypair, its Contribution record, the new transcript digest).  delta is multiplied by the secret s, every point of H
+        and L by s^-1; tau, alpha and beta stay whoever's they were (include/zkhip.h states the scope).  s, k: six Montgomery limbs
+        each, for tests; None draws them from the OS, and nobody ever sees them."""
+        lib = load()
+        if len(prev_digest) != 32:
+            raise ZkhipError("prev_digest is 32 bytes", -1)
+        c = lambda a: _p(np.ascontiguousarray(a, dtype=np.uint64)) if a is not None else None
+        h, rec, digest = ctypes.c_void_p(), Contribution(), ctypes.create_string_buffer(32)
+        _check((lib.zkhip_keypair_contribute_host if host else lib.zkhip_keypair_contribute)(self.handle, c(s), c(k), bytes(prev_digest), ctypes.byref(h),
+                                                                                           ctypes.byref(rec), digest))
+        kp = Keypair.__new__(Keypair)
+        kp.handle = h
+        return kp, rec, digest.raw
+
     def free(self):
         if self.handle:
             load().zkhip_keypair_free(self.handle)
@@ -1912,6 +1997,56 @@ def key_check_last_ms():
     the host's pairings (wall time), then the point checks of each of the eleven elements, milliseconds."""
     out = (ctypes.c_double * (4 + len(KEY_ELEMENTS)))()
     _check(load().zkhip_internal_key_check_last_ms(out))
+    return [float(v) for v in out]
+
+
+def _key_desc(key):
+    """A Keypair, a CrsDesc or (pk dict, n_vars, n_primary, domain_size) -> (CrsDesc, what must stay alive beside it)."""
+    if isinstance(key, Keypair):
+        d = CrsDesc()
+        _check(load().zkhip_keypair_crs_desc(key.handle, ctypes.byref(d)))
+        if d.n_vars and not d.a_query:
+            raise ZkhipError("this keypair holds no query vectors (Keypair.setup_slice): there is nothing to check")
+        return d, key
+    if isinstance(key, CrsDesc):
+        return key, None
+    return make_crs_desc(*key)
+
+
+def phase2_verify(before, after, contribution, prev_digest, rho=None, host=False):
+    """zkhip_phase2_verify / _host (host=True: no device): is `after` an honest phase-2 contribution on top of `before`? ->
+    (Phase2Report, the new transcript digest or None when the report is not ok).  before, after: as check_key takes a key; `before`
+    must have been validated already (check_key, or an earlier accepted contribution).  rho: (domain_size - 1) + (n_vars -
+    n_primary - 1) 128-bit scalars for tests and reproducible runs; None: drawn from the OS."""
+    lib = load()
+    if len(prev_digest) != 32:
+        raise ZkhipError("prev_digest is 32 bytes", -1)
+    db, keep_b = _key_desc(before)
+    da, keep_a = _key_desc(after)
+    rl = _rho_limbs(rho, (db.domain_size - 1) + (db.n_vars - db.n_primary - 1)) if rho is not None else None
+    rep, digest = Phase2Report(), ctypes.create_string_buffer(32)
+    _check((lib.zkhip_phase2_verify_host if host else lib.zkhip_phase2_verify)(ctypes.byref(db), ctypes.byref(da), ctypes.byref(contribution),
+                                                                             bytes(prev_digest), _p(rl) if rl is not None else None,
+                                                                             ctypes.byref(rep), digest))
+    del keep_b, keep_a
+    return rep, (digest.raw if rep.ok else None)
+
+
+def phase2_set_form(form):
+    """Test / measurement hook: the kernel form of contribute's device route - 0 the default (endomorphism), 1 the baseline (only in a
+    build with both forms: ZkhipError otherwise), 2 the endomorphism form."""
+    _check(load().zkhip_internal_phase2_set_form(int(form)))
+
+
+def phase2_last_ms():
+    """Of this thread's last contribute / phase2_verify, milliseconds (zkhip_internal_phase2_last_ms): [0] the device time of its
+    longest single launch (contribute: the multiplication kernel, verify: the point check; 0 on the host routes), [3] the whole call.
+    contribute: [1] / [2] h_query / l_query (wall time, staging included), [4] the copy of the key, [5] delta' in both groups,
+    [6] commitment, response and hashes, [7] the device time of ALL launches of the multiplication kernel.
+    verify: [1] the byte comparison of the unchanged elements, [2] the infinity patterns, [4] point checks, [5] the four sums,
+    [6] the host relations."""
+    out = (ctypes.c_double * 8)()
+    _check(load().zkhip_internal_phase2_last_ms(out))
     return [float(v) for v in out]
 
 
