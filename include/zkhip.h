@@ -946,6 +946,26 @@ int zkhip_internal_field_selftest(int field, const uint32_t* limbs_in, size_t n,
  *   32 + log2 K: fp_sub_k<K>(a, b) for the K the library itself uses (Fq: 1, 32; Fr: 2, 4, 8, 16, 64, 128)
  * An op the field does not have gives ZKHIP_ERR_ARG.  Operands must respect each function's documented contract. */
 int zkhip_internal_field_ops_selftest(int field, int op, const uint32_t* limbs_in, size_t n, uint32_t* limbs_out);
+/* Test hook (no counterpart): the device build's point layer (csrc/ec.cuh, ec_mem.cuh, ec_edw.cuh) on raw limbs, one function per call.
+ * One GPU lane per case, 64 lanes a workgroup (case i is lane i % 64 of wave i / 64); the quad forms take four lanes a case (lanes
+ * 4 (i % 16) .. 4 (i % 16) + 3 of wave i / 16).  Operands are staged in the form the function takes in the library - registers, a packed
+ * point in global memory, a memory reference (mem 0: limb-major array, stride n; mem 1: the slot structure), the LDS images and a
+ * register Y - and nothing is converted, reduced or normalised on the way.
+ * limbs_in, per case 224 words: A = X | Y | ZZ | ZZZ (Edwards: X | Y | Z | T), 27 limbs of 29 bits each; B = the same, or x | y of a
+ * register affine operand, or the words of a packed operand (48 / 72); neg; three entries (index | neg << 31 into `table`, n_table
+ * precomputed Edwards points of 72 words) and their count, for op 18.
+ * limbs_out, per case 217 words: the accumulator's four coordinates (an X kept packed in LDS: its 24 words and three zeros; op 17: the
+ * 72 packed words), a flag word - the function's return value, for a void function whether the result's ZZ / Z tests as zero - and B
+ * as it stands afterwards.  op:
+ *   0 xyzz_dbl_affine(B)   1 xyzz_dbl(A)   2 xyzz_madd(A, B)   3 xyzz_add(A, B)   4 xyzz_neg(A)
+ *   5 madd_mem   6 madd_lds_regy   7 add_lds_regy   8 add_mem_s   9 dbl_mem   10 add_mem_quad   11 dbl_mem_quad
+ *   12 edw_madd_lds_regy   13 edw_add_lds_regy   14 edw_add_mem   15 edw_add_mem_quad   16 edw_dbl_mem_quad   17 edw_from_affine(B)
+ *   18 edw_pre_issue, edw_open_lds_pre, then count - 1 edw_madd_lds_pre, driven as k_accumulate_edw_lock drives them (count 1 .. 3,
+ *      descending inside a wave)
+ * mem 1 is for the ops that take a memory reference (5 .. 11, 13 .. 16).  An unknown op, a mem the op does not take or an entry
+ * past the table gives ZKHIP_ERR_ARG and nothing is launched.  Operands must respect each function's documented contract. */
+int zkhip_internal_point_ops_selftest(int op, int mem, const uint32_t* limbs_in, size_t n, const uint32_t* table, size_t n_table,
+                                      uint32_t* limbs_out);
 /* Test hooks of the Edwards accumulation's lockstep route (no counterpart).  A single MSM over a table in the Edwards model always
  * enqueues two accumulations, one bucket per lane (k_accumulate_edw_lock) and sliced (k_accumulate_edw); a word the device writes
  * per launch decides which of them runs.

@@ -598,6 +598,13 @@ int zkhip_internal_field_ops_selftest(int field, int op, const uint32_t* limbs_i
   return msm_field_ops_selftest(field, op, limbs_in, n, limbs_out, t_err, sizeof t_err);
 }
 
+int zkhip_internal_point_ops_selftest(int op, int mem, const uint32_t* limbs_in, size_t n, const uint32_t* table, size_t n_table, uint32_t* limbs_out) {
+  BIND_CUR();
+  if (n && (!limbs_in || !limbs_out)) return fail(ZKHIP_ERR_ARG, "n cases need their operands and a place for the results");
+  std::lock_guard<std::mutex> lk(g.dev[cur_dev()].mu);
+  return msm_point_ops_selftest(op, mem, limbs_in, n, table, n_table, limbs_out, t_err, sizeof t_err);
+}
+
 // Test hook of the bucket reduction's tail (msm.hip enqueue_tail)
 int zkhip_internal_msm_tail(int edw, const uint64_t* items_affine, int W, unsigned N, int lo_bits, int total, uint64_t* out_jac) {
   BIND_CUR();

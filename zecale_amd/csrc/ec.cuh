@@ -6,7 +6,10 @@
 // Coordinates: extended Jacobian "XYZZ" (x = X/ZZ, y = Y/ZZZ, ZZ^3 = ZZZ^2), infinity <=> ZZ = 0.
 //   mixed add  (XYZZ + affine): 8M + 2S      full add (XYZZ + XYZZ): 12M + 2S     double: 6M + 4S
 // Lazy bounds (multiples of p) are tracked in the comments: [k] means value < k*p.  Every fp_mul
-// output is [2]; stored points keep X [10], Y [4], ZZ [2], ZZZ [2].
+// output is [2]; stored points keep X [10], Y [4], ZZ [2], ZZZ [2].  Y's bound is CLOSED, Y <= 4p: xyzz_neg of Y = 0 (the limbs
+// xyzz_infinity() leaves) gives exactly 4p.  Every consumer takes it: Y is a factor of a product, doubled into one (U = 2Y <= 8p),
+// or the subtrahend of an fp_sub<4>, whose condition is b <= 4p.  A ZZ = 0 (mod p) may be the limbs of p instead of zeros (a
+// product with a factor = 0 (mod p)); every infinity test goes through fp_is_zero_2p, which takes both.
 #pragma once
 #include "fp29.cuh"
 
@@ -150,7 +153,7 @@ ZK_HD ZK_INL void xyzz_add(XYZZ& a, const XYZZ& b) {
 }
 
 ZK_HD ZK_INL void xyzz_neg(XYZZ& a) {
-  a.Y = fp_sub<FqParams, 4>(fp_zero<FqParams>(), a.Y);   // [4]
+  a.Y = fp_sub<FqParams, 4>(fp_zero<FqParams>(), a.Y);   // 4p - Y <= 4p, with equality for Y = 0 (see the bounds above)
 }
 
 // ---- memory forms -------------------------------------------------------------------------

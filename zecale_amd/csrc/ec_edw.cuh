@@ -357,8 +357,27 @@ __device__ __forceinline__ void edw_dbl_mem_quad(const XyzzRef& A, uint32_t q) {
 
 // chi for one affine point of G1 (device form, canonical), written out in precomputed form.  With X = x - 1:
 //   x_e = t s y / (3 - X^2),  y_e = (y^2 - s X^2) / (y^2 + s X^2)        (one inversion of the product of the two denominators)
-// Returns false when the point is not on G1's curve y^2 = x^3 - 1 (a G2 base set) or hits a denominator that vanishes (a point of
-// even order): the caller then keeps the base set on the XYZZ path.
+// Returns false when the point is not on G1's curve y^2 = x^3 - 1 (a G2 base set), hits a denominator that vanishes, maps to
+// x_e = 0 (the points of order 2) or has an x - 1 that is not a square: the caller then keeps the base set on the XYZZ path.
+// The square test is what refuses P + (1, 0): (1, 0) generates chi's kernel, so chi(P + (1, 0)) = chi(P) with no denominator
+// vanishing, and nothing in the image tells the two apart.  x - 1 is the 2-descent coordinate at (1, 0): a square for every point
+// of 2 E(Fq) - all of G1, whose order is odd - and for P + (1, 0) it is x(P) - 1 times (1 - w)(1 - w^2) = 3, w^3 = 1, which is
+// not a square (s^2 = -3 and p = 3 mod 4).  Euler's criterion, X^((p-1)/2) = 1: 759 squarings and 344 products in one rolled loop.
+// (Odd order is still not ESTABLISHED here - P + (w, 0) passes the square test and maps to a proper point of even order; order r
+// is k_half_bases' check, 2 [1/2 mod r] P = P.)
+__device__ __forceinline__ bool fq_is_square_nonzero(const Fq& X) {          // X [4]
+  Fq acc = X;                                                                // bit 759 of (p - 1) / 2 = bit 760 of p
+#pragma unroll 1
+  for (int j = 758; j >= 0; j--) {
+    acc = fp_sqr(acc);
+    if ((FqParams::P[(j + 1) / 29] >> ((j + 1) % 29)) & 1u) acc = fp_mul(acc, X);      // (uniform: the bits of p)
+  }
+  const Fq c = fp_cond_sub_p(acc), one = fp_one<FqParams>();                 // canonical: 1, p - 1 or 0 (Montgomery form)
+  uint32_t d = 0;
+#pragma unroll
+  for (int i = 0; i < 27; i++) d |= c.l[i] ^ one.l[i];
+  return d == 0;
+}
 __device__ __forceinline__ bool edw_from_affine(const Fq& x, const Fq& y, EdwPacked* out) {
   const Fq one = fp_one<FqParams>();
   const Fq yy = fp_mul(y, y);
@@ -376,7 +395,7 @@ __device__ __forceinline__ bool edw_from_affine(const Fq& x, const Fq& y, EdwPac
   const Fq xe = fp_mul(fp_mul(fp_mul(y, fp_const<FqParams>(FqParams::EDW_TS)), D2), inv);
   const Fq ye = fp_mul(fp_mul(N2, D1), inv);
   const Fq t2d = fp_mul(fp_mul(xe, ye), fp_const<FqParams>(FqParams::EDW_D2));
-  const bool ok = on_curve && !fp_is_zero_2p(den) && !fp_is_zero_2p(xe);
+  const bool ok = on_curve && fq_is_square_nonzero(X) && !fp_is_zero_2p(den) && !fp_is_zero_2p(xe);
   fp_pack32<FqParams>(fp_canon(fp_sub<FqParams, 2>(ye, xe)), out->ymx);
   fp_pack32<FqParams>(fp_canon(fp_add(ye, xe)), out->ypx);
   fp_pack32<FqParams>(fp_canon(t2d), out->t2d);

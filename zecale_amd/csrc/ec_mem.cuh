@@ -134,7 +134,8 @@ __device__ __forceinline__ void mem_copy(const XyzzRef& dst, const XyzzRef& src)
   for (int c = 0; c < 4; c++) mem_st(dst, c, mem_ld(src, c));
 }
 
-// packed affine point (device form) coordinate loads; neg: return p - y (as a [2] value)
+// packed affine point (device form) coordinate loads; neg: return 2p - y, in (p, 2p] - exactly 2p for y = 0 (a point of order 2,
+// (1, 0) on G1): the value is only ever a factor of a product or doubled into one (xyzz_dbl_affine), never a subtrahend
 __device__ __forceinline__ Fq aff_ld_x(const AffPacked* p) {
   uint32_t w[24];
 #pragma unroll

@@ -152,6 +152,11 @@ int msm_field_selftest(int field, const uint32_t* in_host, size_t n, uint32_t* o
 // test hook: one function of the field layer (fp29.cuh, fp_inv.cuh) per launch on n cases of three raw-limb operands; out: n x (NL words
 // and a flag word).  ZKHIP_ERR_ARG for an op the field does not have (msm.hip FieldOp)
 int msm_field_ops_selftest(int field, int op, const uint32_t* in_host, size_t n, uint32_t* out_host, char* errbuf, size_t errlen);
+// test hook (point_ops_selftest.hip): one point operation of ec.cuh / ec_mem.cuh / ec_edw.cuh per launch on n cases of raw-limb
+// operands (224 words in, 217 words out per case; mem 0: limb-major references, 1: slot references).  ZKHIP_ERR_ARG for an unknown op,
+// for mem 1 with an op that takes no memory reference, and for a lockstep run whose entries leave its table; nothing is launched then
+int msm_point_ops_selftest(int op, int mem, const uint32_t* in_host, size_t n, const uint32_t* table_host, size_t n_table, uint32_t* out_host,
+                           char* errbuf, size_t errlen);
 int msm_measure_fqmul_rate(double* fq_mul_per_s, char* errbuf, size_t errlen);
 // test hook: the tail of the bucket reduction (bit planes, R * hi + lo) on 2W groups of N affine ABI points given on the host;
 // an Edwards run (edw != 0) returns twice the sums.  out_jac: W points (+ W plain totals of the lo groups if total), 36 limbs each

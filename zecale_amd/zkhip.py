@@ -31,7 +31,7 @@ EXPORTS = [
     "zkhip_groth16_setup", "zkhip_groth16_setup_slice", "zkhip_keypair_crs_desc", "zkhip_keypair_vk", "zkhip_keypair_free", "zkhip_keypair_write", "zkhip_keypair_read",
     "zkhip_jac_to_affine", "zkhip_jac_add", "zkhip_to_canonical",
     "zkhip_last_accumulate_interval", "zkhip_crs_upload_ex", "zkhip_crs_upload_slice_ex", "zkhip_bases_precompute_ex", "zkhip_crs_table_kind", "zkhip_crs_finite_terms",
-    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_field_ops_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_pipeline_witness_sizing", "zkhip_internal_witness_run_program", "zkhip_internal_witness_run_program_wide", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_internal_gpu_witness_run_wide", "zkhip_gpu_witness_set_waves", "zkhip_gpu_witness_plan", "zkhip_gpu_witness_last_ms", "zkhip_device_memory", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
+    "zkhip_bases_set_window", "zkhip_reset_time_base", "zkhip_measure_fq_mul_rate", "zkhip_internal_field_selftest", "zkhip_internal_field_ops_selftest", "zkhip_internal_point_ops_selftest", "zkhip_internal_tail_selftest", "zkhip_internal_pipeline_witness_sizing", "zkhip_internal_witness_run_program", "zkhip_internal_witness_run_program_wide", "zkhip_internal_witness_tape", "zkhip_internal_gpu_witness_run", "zkhip_internal_gpu_witness_run_wide", "zkhip_gpu_witness_set_waves", "zkhip_gpu_witness_plan", "zkhip_gpu_witness_last_ms", "zkhip_device_memory", "zkhip_last_prove_split", "zkhip_set_prove_split", "zkhip_host_alloc", "zkhip_host_free",
     "zkhip_msm_stream_new", "zkhip_msm_stream_submit", "zkhip_msm_stream_submit_host", "zkhip_msm_stream_collect", "zkhip_msm_stream_last_accumulate_ms",
     "zkhip_msm_stream_last_accumulate_interval", "zkhip_msm_stream_free", "zkhip_prover_new_slice", "zkhip_prover_prove_partial",
     "zkhip_dispatcher_new", "zkhip_dispatcher_size", "zkhip_dispatcher_submit", "zkhip_dispatcher_wait", "zkhip_dispatcher_stats", "zkhip_dispatcher_free",
@@ -2203,6 +2203,22 @@ def field_ops_selftest(field, op, operands):
     lib = load()
     lib.zkhip_internal_field_ops_selftest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     _check(lib.zkhip_internal_field_ops_selftest(int(field), int(op), x.ctypes.data, x.shape[0], out.ctypes.data))
+    return out
+
+
+def point_ops_selftest(op, mem, rows, table=None):
+    """Test hook: one function of the device's point layer on raw limbs (zkhip_internal_point_ops_selftest; the op codes and the row
+    layouts are listed in include/zkhip.h).  rows: uint32 [n][224], one case per GPU lane (four lanes for the quad forms) in order;
+    mem 0 / 1: limb-major / slot references; table: uint32 [m][72] precomputed Edwards points for the lockstep run.  Returns uint32
+    [n][217]: the accumulator, a flag word, and B afterwards."""
+    x = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 224)
+    out = np.zeros((x.shape[0], 217), dtype=np.uint32)
+    tab = None if table is None else np.ascontiguousarray(table, dtype=np.uint32).reshape(-1, 72)
+    lib = load()
+    lib.zkhip_internal_point_ops_selftest.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                      ctypes.c_void_p]
+    _check(lib.zkhip_internal_point_ops_selftest(int(op), int(mem), x.ctypes.data, x.shape[0], None if tab is None else tab.ctypes.data,
+                                                 0 if tab is None else tab.shape[0], out.ctypes.data))
     return out
 
 
